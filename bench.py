@@ -1,8 +1,10 @@
-"""bench.py — LAP-3B bf16 train-step throughput on MI355X (BASELINE.json metric, config[1] / config[2]) and, at N = 1,
-the batch-1 action-chunk latency (config[3]) in the same JSON line.
+"""bench.py — LAP-3B bf16 train-step throughput on MI355X (BASELINE.json metric, config[1] / config[2]) and, with --full at
+N = 1, the batch-1 action-chunk latency (config[3]) in the same JSON line.
 
     python bench.py --gpus N --steps K --warmup W          (N > 1 without a launcher: re-executes itself under
                                                             torch.distributed.run on 127.0.0.1, one rank per GPU)
+    python bench.py --gpus 1 --steps K --warmup W --full   (+ roofline, serving latency, CPU baseline)
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -11,7 +13,11 @@ LAP-3B (SigLIP So400m/14 + Gemma-2B + Gemma-300M action expert, random-init weig
 samples per GPU: 2 x 224x224 images, 48-token prompt (last 16 = language-action tokens), 50-step action chunk
 (SURVEY.md §8d).  Weak scaling: per-GPU batch fixed, parameters/optimizer FSDP-sharded over RCCL.
 
-Prints ONE JSON line on rank 0.  `roofline` describes the dominant kernel (the bf16 MFMA GEMM family, csrc/gemm.hip: gemm_sp_kernel + gemm_pq_kernel + gemm_kernel):
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline (`value`,
+`ms_per_step`, `final_loss`); `--dump-outputs DIR` also writes what the last timed step returned (see dump_outputs).
+`--full` adds the side figures below, each of which costs runs of its own: `roofline`, `serve` and `cpu_baseline`.
+
+`roofline` describes the dominant kernel (the bf16 MFMA GEMM family, csrc/gemm.hip: gemm_sp_kernel + gemm_pq_kernel + gemm_kernel):
 achieved = sum of 2*M*N*K over the GEMM launches of the timed steps / their summed durations, measured with HIP
 events on the launch stream; `cpu_baseline` times the CPU oracle (oracle/lap_oracle.py, kind "port") on the host
 cores on a bounded slice of the same workload.  `serve` is the second half of the metric: prefix prefill + 10 denoise
@@ -86,6 +92,9 @@ def synthetic_batch(cfg, B, device, seed):
         loss_rows_max=int(la[:, 1:].sum(-1).max()))     # host-side hint the data loaders attach: 16 loss-carrying tokens per sample
     actions = torch.randn(B, cfg.action_horizon, cfg.action_dim, generator=g).to(device)
     return obs, actions
+
+
+METER_STEPS = 2     # --full: length of the event-timed pass behind the timed steps
 
 
 class GemmMeter:
@@ -375,6 +384,83 @@ def serve_latency(cfg, dev, reps: int = 20):
             "graph_equals_eager": same, "replays": reps, "prompt_len": cfg.max_token_len, "action_horizon": cfg.action_horizon}
 
 
+def roofline_figures(meter, dev, step_s, per_gpu_value):
+    """`roofline` of the --full line, from the metered pass behind the timed steps (GemmMeter) and the isolated re-runs."""
+    n_launch, t_gemm, fl_gemm = meter.summary()
+    GEMM_TRAFFIC = gemm_traffic()
+    in_situ = fl_gemm / t_gemm / 1e12 if t_gemm > 0 else 0.0
+    union_s = meter.union_seconds()
+    second_fl = sum(meter.second)
+    # the family's rate by isolated per-shape timing (see GemmMeter.isolated): the train state stays resident, operands are fresh
+    iso_f, iso_t, iso_rows = meter.isolated(dev)
+    achieved = iso_f / iso_t / 1e12 if iso_t > 0 else 0.0
+    msteps = METER_STEPS        # the metered pass, not the timed steps, is what the per-step figures below are divided by
+    if os.environ.get("LAP_BENCH_SHAPES"):      # the whole table, for tools / profiles (stderr: stdout carries the one JSON line)
+        for tt, nm, c, t, r in iso_rows:
+            print(f"  {nm:28s} x{c // msteps:3d}  {t * 1e6:8.1f} us  {r:7.0f} TF/s  {tt / msteps * 1e3:7.2f} ms/step", file=sys.stderr)
+    return {"bound": "mfma", "kernel": "lap_gemm_asm_* (csrc/gemm_asm_kernels.s) / gemm_pq_kernel / gemm_sp_kernel / gemm_kernel (bf16 MFMA GEMM family, csrc/gemm.hip)", "achieved": round(in_situ, 1),
+                 "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(in_situ / MFMA_PEAK_TFLOPS, 4),
+                 "definition": "IN THE STEP: sum of 2MNK over the compute stream's GEMM launches / sum of their durations, HIP events on the "
+                               "launch stream around every launch of a separate 2-step pass behind the timed steps (the timed steps carry no "
+                               "events); includes what the co-running optimizer / action-expert / weight-gradient streams cost each launch; "
+                               "GEMMs with a fused GeGLU / GELU epilogue count 2MNK and carry their epilogue in the duration.  This is the "
+                               "figure profiles/*_per_queue_step_breakdown.txt reproduces.",
+                 "gemm_ms_per_step": round(t_gemm / msteps * 1e3, 2),
+                 "isolated": {"achieved": round(achieved, 1), "frac": round(achieved / MFMA_PEAK_TFLOPS, 4),
+                              "gemm_ms_per_step": round(iso_t / msteps * 1e3, 2),
+                              "note": "side figure: every distinct call signature of the step re-run ALONE in this process (fresh operands, HIP events), "
+                                      "the step's mix priced with those durations: sum count x 2MNK / sum count x t_isolated"},
+                 "distinct_shapes": len(iso_rows),
+                 "plain_signatures_only": (lambda pl: {"achieved": round(sum(r * tt_ for tt_, _, _, _, r in pl) / max(sum(tt_ for tt_, *_ in pl), 1e-12), 1),
+                                                       "ms_per_step": round(sum(tt_ for tt_, *_ in pl) / msteps * 1e3, 2),
+                                                       "note": "the ISOLATED sum without the four fused-epilogue signatures (gate|up + GeGLU, down dgrad + GeGLU "
+                                                               "backward, SigLIP fc1 + GELU, fc2 dgrad + GELU backward), whose durations contain elementwise work "
+                                                               "that used to be separate HBM-bound kernels"})([x for x in iso_rows if "+" not in x[1]]),
+                 "top_shapes_isolated": [{"shape": nm, "launches_per_step": c // msteps, "us": round(t * 1e6, 1), "TFLOPs": round(r, 0)}
+                                for _, nm, c, t, r in iso_rows[:8]],
+                 "traffic": GEMM_TRAFFIC["bytes_per_launch"], "traffic_unit": "L2-to-fabric bytes per launch (FETCH_SIZE x 2 + WRITE_SIZE; Infinity-Cache hits included)",
+                 "traffic_shape": GEMM_TRAFFIC["shape"], "traffic_algorithmic_bytes": GEMM_TRAFFIC["algorithmic_bytes_per_launch"],
+                 "traffic_source": GEMM_TRAFFIC["source"], "traffic_measured_in_run": False,
+                 "launches_per_step": n_launch // msteps,
+                 "second_stream": {"launches_per_step": len(meter.second) // msteps,
+                                   "flop_frac": round(second_fl / max(fl_gemm + second_fl, 1.0), 4),
+                                   "note": "action-expert GEMMs co-running on a second HIP stream: counted, not in the timed sums"},
+                 "union_of_launch_intervals": {"achieved": round((fl_gemm + second_fl) / max(union_s, 1e-9) / 1e12, 1),
+                                               "note": "all GEMM FLOPs of both streams / time during which any GEMM launch was in flight (informative)"},
+                 "avg_launch_us": round(iso_t / max(sum(c for _, _, c, _, _ in iso_rows), 1) * 1e6, 2),
+                 "gemm_time_frac_of_step": round(t_gemm / msteps / step_s, 4),
+                 "step_mfu": round(per_gpu_value * TRAIN_FLOP_PER_SAMPLE / 1e12 / MFMA_PEAK_TFLOPS, 4)}
+
+
+DUMP_SAMPLES_PER_UNIT = 40_000
+
+
+def dump_outputs(path, state, info):
+    """`--dump-outputs DIR`: what the last timed step handed its caller, as float32 .npy files — every tensor of the step's
+    `info` (`loss.npy`, `grad_norm.npy`, the loss metrics) and, of the new train state, the same fixed sample of every parameter
+    unit's f32 master weights, AdamW moments and EMA weights (`params.npy`, `adam_m.npy`, `adam_v.npy`, `ema.npy`: up to
+    DUMP_SAMPLES_PER_UNIT positions per unit, drawn from a generator of fixed seed, units in store order; LAP-3B: 49 units, 1.96 M
+    values, 7.8 MB per file).  The inputs depend on the arguments only, so two builds can be compared file by file."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    ps = state.model.ps
+    ps.quiesce()                 # the optimizer of the last step may still be in flight on the side stream
+    torch.cuda.synchronize()
+    for k, v in info.items():
+        if torch.is_tensor(v):
+            np.save(os.path.join(path, f"{k}.npy"), v.detach().float().cpu().numpy())
+    g = torch.Generator(device="cpu").manual_seed(0)
+    idx = {}
+    for u in ps.units:
+        n = ps.master[u.name].numel()
+        i = torch.arange(n) if n <= DUMP_SAMPLES_PER_UNIT else torch.randint(0, n, (DUMP_SAMPLES_PER_UNIT,), generator=g).sort().values
+        idx[u.name] = i.to(ps.master[u.name].device)
+    for name, bufs in (("params", ps.master), ("adam_m", ps.m), ("adam_v", ps.v), ("ema", ps.ema)):
+        if bufs:
+            np.save(os.path.join(path, f"{name}.npy"), torch.cat([bufs[u.name][idx[u.name]] for u in ps.units]).float().cpu().numpy())
+
+
 def _self_launch(args) -> int:
     """`python bench.py --gpus N` with N > 1 and no launcher environment: start one rank per GPU under
     torch.distributed.run (rendezvous on 127.0.0.1, a free port) and pass the JSON line through."""
@@ -402,13 +488,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=32, help="per-GPU batch")
     ap.add_argument("--config", default="lap_bench")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-serve", action="store_true", help="skip the batch-1 action-chunk latency leg (N = 1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the side figures: roofline (event-timed GEMM pass + isolated re-runs), serve, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy (N = 1 only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-serve", action="store_true", help="with --full: skip the batch-1 action-chunk latency leg (N = 1 only)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp8"],
                     help="bf16 = the headline metric; fp8 = BASELINE.json config 5 (fp8 forward / data-gradient GEMMs of the VLM "
                          "expert, everything else bf16) — reported with dtype 'fp8', a NON-headline line")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for --gpus > 1 (nccl = RCCL; gloo only for flow tests)")
     args = ap.parse_args()
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs needs --gpus 1 (the parameter store is sharded over the ranks otherwise)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(_self_launch(args))
@@ -454,8 +545,9 @@ def main():
     state = init_train_state(tc, device=dev, world_size=world, rank=rank, use_fsdp=world > 1)
     runner = TrainingStepRunner(tc)
     batches = [synthetic_batch(tc.model, args.batch, dev, seed=1000 * rank + i) for i in range(2)]
-    meter = GemmMeter(hip)
-    meter.install()
+    if args.full:
+        meter = GemmMeter(hip)
+        meter.install()
 
     def sync():   # barrier + device synchronize (all streams: compute, optimizer / collective side stream)
         torch.cuda.synchronize()
@@ -467,20 +559,22 @@ def main():
         state, info = runner(0, state, batches[i % 2], state.step)
     sync()
     # The timed steps run WITHOUT the meter (772 event pairs per step are measurement overhead inside the
-    # headline number): `enabled` is False, the wrappers pass straight through.
+    # headline number): with --full it is installed but `enabled` is False, the wrappers pass straight through.
     t0 = time.perf_counter()
     for i in range(args.steps):
         state, info = runner(0, state, batches[i % 2], state.step)
     sync()
     dt = time.perf_counter() - t0
     loss_t = info["loss"]
-    # ... and the in-situ figure and the step's call signatures come from a separate, short, event-timed pass behind them
-    METER_STEPS = 2
-    meter.start()
-    for i in range(METER_STEPS):
-        state, info = runner(0, state, batches[i % 2], state.step)
-    sync()
-    meter.enabled = False
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, state, info)
+    if args.full:
+        # ... and the in-situ figure and the step's call signatures come from a separate, short, event-timed pass behind them
+        meter.start()
+        for i in range(METER_STEPS):
+            state, info = runner(0, state, batches[i % 2], state.step)
+        sync()
+        meter.enabled = False
     info = {"loss": loss_t}
     if world > 1:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
@@ -488,20 +582,8 @@ def main():
         dt = tt.item()
     loss = info["loss"].item()
     if rank == 0:
-        n_launch, t_gemm, fl_gemm = meter.summary()
-        GEMM_TRAFFIC = gemm_traffic()
         samples = args.batch * world * args.steps
         value = samples / dt
-        in_situ = fl_gemm / t_gemm / 1e12 if t_gemm > 0 else 0.0
-        union_s = meter.union_seconds()
-        second_fl = sum(meter.second)
-        # the family's rate by isolated per-shape timing (see GemmMeter.isolated): the train state stays resident, operands are fresh
-        iso_f, iso_t, iso_rows = meter.isolated(dev)
-        achieved = iso_f / iso_t / 1e12 if iso_t > 0 else 0.0
-        msteps = METER_STEPS        # the metered pass, not the timed steps, is what the per-step figures below are divided by
-        if os.environ.get("LAP_BENCH_SHAPES"):      # the whole table, for tools / profiles (stderr: stdout carries the one JSON line)
-            for tt, nm, c, t, r in iso_rows:
-                print(f"  {nm:28s} x{c // msteps:3d}  {t * 1e6:8.1f} us  {r:7.0f} TF/s  {tt / msteps * 1e3:7.2f} ms/step", file=sys.stderr)
         out = {
             "metric": "train-step samples/sec LAP-3B bf16", "value": round(value, 3), "unit": "samples/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
@@ -514,45 +596,15 @@ def main():
                         else f"NON-HEADLINE flow test: config {args.config}"),
                        "global_batch": args.batch * world, "per_gpu_batch": args.batch, "seq_len": 610,
                        "parallelism": f"fsdp{world}" if world > 1 else "single"},
-            "roofline": {"bound": "mfma", "kernel": "lap_gemm_asm_* (csrc/gemm_asm_kernels.s) / gemm_pq_kernel / gemm_sp_kernel / gemm_kernel (bf16 MFMA GEMM family, csrc/gemm.hip)", "achieved": round(in_situ, 1),
-                         "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(in_situ / MFMA_PEAK_TFLOPS, 4),
-                         "definition": "IN THE STEP: sum of 2MNK over the compute stream's GEMM launches / sum of their durations, HIP events on the "
-                                       "launch stream around every launch of a separate 2-step pass behind the timed steps (the timed steps carry no "
-                                       "events); includes what the co-running optimizer / action-expert / weight-gradient streams cost each launch; "
-                                       "GEMMs with a fused GeGLU / GELU epilogue count 2MNK and carry their epilogue in the duration.  This is the "
-                                       "figure profiles/*_per_queue_step_breakdown.txt reproduces.",
-                         "gemm_ms_per_step": round(t_gemm / msteps * 1e3, 2),
-                         "isolated": {"achieved": round(achieved, 1), "frac": round(achieved / MFMA_PEAK_TFLOPS, 4),
-                                      "gemm_ms_per_step": round(iso_t / msteps * 1e3, 2),
-                                      "note": "side figure: every distinct call signature of the step re-run ALONE in this process (fresh operands, HIP events), "
-                                              "the step's mix priced with those durations: sum count x 2MNK / sum count x t_isolated"},
-                         "distinct_shapes": len(iso_rows),
-                         "plain_signatures_only": (lambda pl: {"achieved": round(sum(r * tt_ for tt_, _, _, _, r in pl) / max(sum(tt_ for tt_, *_ in pl), 1e-12), 1),
-                                                               "ms_per_step": round(sum(tt_ for tt_, *_ in pl) / msteps * 1e3, 2),
-                                                               "note": "the ISOLATED sum without the four fused-epilogue signatures (gate|up + GeGLU, down dgrad + GeGLU "
-                                                                       "backward, SigLIP fc1 + GELU, fc2 dgrad + GELU backward), whose durations contain elementwise work "
-                                                                       "that used to be separate HBM-bound kernels"})([x for x in iso_rows if "+" not in x[1]]),
-                         "top_shapes_isolated": [{"shape": nm, "launches_per_step": c // msteps, "us": round(t * 1e6, 1), "TFLOPs": round(r, 0)}
-                                        for _, nm, c, t, r in iso_rows[:8]],
-                         "traffic": GEMM_TRAFFIC["bytes_per_launch"], "traffic_unit": "L2-to-fabric bytes per launch (FETCH_SIZE x 2 + WRITE_SIZE; Infinity-Cache hits included)",
-                         "traffic_shape": GEMM_TRAFFIC["shape"], "traffic_algorithmic_bytes": GEMM_TRAFFIC["algorithmic_bytes_per_launch"],
-                         "traffic_source": GEMM_TRAFFIC["source"], "traffic_measured_in_run": False,
-                         "launches_per_step": n_launch // msteps,
-                         "second_stream": {"launches_per_step": len(meter.second) // msteps,
-                                           "flop_frac": round(second_fl / max(fl_gemm + second_fl, 1.0), 4),
-                                           "note": "action-expert GEMMs co-running on a second HIP stream: counted, not in the timed sums"},
-                         "union_of_launch_intervals": {"achieved": round((fl_gemm + second_fl) / max(union_s, 1e-9) / 1e12, 1),
-                                                       "note": "all GEMM FLOPs of both streams / time during which any GEMM launch was in flight (informative)"},
-                         "avg_launch_us": round(iso_t / max(sum(c for _, _, c, _, _ in iso_rows), 1) * 1e6, 2),
-                         "gemm_time_frac_of_step": round(t_gemm / msteps / (dt / args.steps), 4),
-                         "step_mfu": round(value / world * TRAIN_FLOP_PER_SAMPLE / 1e12 / MFMA_PEAK_TFLOPS, 4)},
-            "final_loss": round(loss, 5),
         }
-        if world == 1 and not args.no_serve and args.config == "lap_bench" and args.dtype == "bf16":
+        if args.full:
+            out["roofline"] = roofline_figures(meter, dev, dt / args.steps, value / world)
+        out["final_loss"] = round(loss, 5)
+        if args.full and world == 1 and not args.no_serve and args.config == "lap_bench" and args.dtype == "bf16":
             del state, runner, batches
             torch.cuda.empty_cache()
             out["serve"] = serve_latency(tc.model, dev)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # 32 host threads: torch-CPU matmuls of this size stop scaling (and get slower) well beyond that (256 threads on
             # the GPU box took 166 s for a 6-layer slice that 16 threads finish in 9 s)
             out["cpu_baseline"], serve_cpu = cpu_baseline(min(os.cpu_count() or 1, 32))
