@@ -36,18 +36,31 @@ class GemmaConfig:
     num_heads: int
     num_kv_heads: int
     head_dim: int
+    # LoRA adapters (gemma.py:55,88-108, lora.LoRAConfig): (rank, alpha) on the attention einsums (q / kv / attn_vec) and on the
+    # FeedForward (gating_einsum / linear), or None.  scaling = alpha / rank (rslora=False).
+    lora_attn: tuple | None = None
+    lora_ffn: tuple | None = None
+    reference: bool = True      # False: an engine-only test variant the reference does not define
+
+    @property
+    def has_lora(self) -> bool:
+        return self.lora_attn is not None or self.lora_ffn is not None
 
 
 _GEMMA = {
     "dummy": GemmaConfig(64, 4, 128, 8, 1, 16),
     "gemma_300m": GemmaConfig(1024, 18, 4096, 8, 1, 256),
     "gemma_2b": GemmaConfig(2048, 18, 16384, 8, 1, 256),
+    "gemma_2b_lora": GemmaConfig(2048, 18, 16384, 8, 1, 256, lora_attn=(16, 16.0), lora_ffn=(16, 16.0)),    # gemma.py:88-97
+    "gemma_300m_lora": GemmaConfig(1024, 18, 4096, 8, 1, 256, lora_attn=(32, 32.0), lora_ffn=(32, 32.0)),   # gemma.py:98-107
+    # engine-only: the `dummy` widths with rank-16 adapters and alpha = 2 * rank (scaling 2, so tests see s != 1)
+    "dummy_lora": GemmaConfig(64, 4, 128, 8, 1, 16, lora_attn=(16, 32.0), lora_ffn=(16, 32.0), reference=False),
 }
 
 
 def get_gemma_config(variant: str) -> GemmaConfig:
     if variant not in _GEMMA:
-        raise ValueError(f"Unknown variant: {variant}")  # gemma.py:109 (LoRA / gemma3 variants are out of scope)
+        raise ValueError(f"Unknown variant: {variant}")  # gemma.py:109 (gemma3 variants are out of scope)
     return _GEMMA[variant]
 
 
@@ -156,7 +169,15 @@ class LAPConfig:
         return "lap_fast" if self.use_fast else "lap"
 
     def get_freeze_filter(self):
-        """lap_config.py:132-169: only the LoRA variants (out of scope here) freeze anything -> nnx.Nothing."""
+        """lap_config.py:132-169: the base weights of each LoRA expert are frozen, its adapters stay trainable —
+        All(.*llm.*, [Not(.*llm.*_1.*) when the action expert is not LoRA], Not(.*lora.*)) for a LoRA VLM,
+        All(.*llm.*_1.*, Not(.*lora.*)) when only the action expert is LoRA, None (nnx.Nothing) without LoRA.  SigLIP, the
+        action heads and a non-LoRA expert stay trainable; the embedder and the final norm are frozen with a LoRA VLM."""
+        vlm, expert = "lora" in self.paligemma_variant, "lora" in self.action_expert_variant
+        if vlm:
+            return PathFilter(all_of=(".*llm.*",), none_of=(() if expert else (".*llm.*_1.*",)) + (".*lora.*",))
+        if expert:
+            return PathFilter(all_of=(".*llm.*_1.*",), none_of=(".*lora.*",))
         return None
 
     def get_vlm_freeze_filter(self):

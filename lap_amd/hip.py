@@ -192,6 +192,10 @@ SIGNATURES: dict[str, list] = {
     "lap_swish_bwd": [_vp, _vp, _vp, _ll, _vp],
     "lap_mse_fwd_bwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
     "lap_axpy_f32": [_vp, _vp, _f, _ll, _vp],
+    "lap_lora_down": [_vp, _i, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _f, _vp],
+    "lap_lora_up_add": [_vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _f, _vp],
+    "lap_lora_wgrad": [_vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _ll, _vp],
+    "lap_lora_merge": [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _f, _vp],
 }
 
 _fn = {}
@@ -1132,3 +1136,72 @@ def stream_with_hip_priority(device, level: str):
     if rc != 0 or not handle.value:
         raise LapHipError(f"hipStreamCreateWithPriority failed: {rc}")
     return torch.cuda.ExternalStream(handle.value, device=dev)
+
+
+# ------------------------------------------------------------------------------ LoRA (csrc/lora.hip)
+def _req2(t, dtype, name):
+    _req(t, dtype, name)
+    if t.dim() != 2 or t.stride(1) != 1:
+        raise ValueError(f"{name}: expected a row-major 2-D tensor, got shape {tuple(t.shape)} strides {t.stride()}")
+
+
+def lora_down(x, w, *, G=1, nsum=1, xg=0, s=1.0, out=None):
+    """t[M, G*R] = bf16(x . w^T) per group (include/lap_hip.h lap_lora_down): the forward down projection t = x A^T (G = 1, w = A),
+    or the data gradient dt of t (x = dy, xg = the group's column stride in dy, w = B with `nsum` stacked copies, s = the adapter
+    scaling: dy is taken as bf16(s dy))."""
+    _req2(x, torch.bfloat16, "x"); _req2(w, torch.bfloat16, "w")
+    M = x.shape[0]
+    R = w.shape[0] // (G * nsum)
+    K = w.shape[1]
+    if out is None:
+        out = torch.empty((M, G * R), dtype=torch.bfloat16, device=x.device)
+    _req2(out, torch.bfloat16, "out")
+    call("lap_lora_down", _p(x), x.stride(0), xg, _p(w), w.stride(0), nsum, _p(out), out.stride(0), M, K, G, R, float(s))
+    return out
+
+
+def lora_up_add(y, t, b, *, G=1, nsum=1, s=1.0):
+    """y[:, g*Ng:(g+1)*Ng] = bf16(y + bf16(s bf16(t_g . B_g))) in place (lap_lora_up_add): the LoRA term of a projection (b = B,
+    `nsum` stacked copies summed), or the data-gradient add dx += bf16(dt . A) (b = A, G = 1)."""
+    _req2(y, torch.bfloat16, "y"); _req2(t, torch.bfloat16, "t"); _req2(b, torch.bfloat16, "b")
+    R = b.shape[0] // (G * nsum)
+    Ng = b.shape[1]
+    if y.shape[1] != G * Ng or t.shape[1] < G * R or t.shape[0] != y.shape[0]:
+        raise ValueError(f"lora_up_add: y {tuple(y.shape)}, t {tuple(t.shape)}, b {tuple(b.shape)}, G {G}")
+    call("lap_lora_up_add", _p(t), t.stride(0), _p(b), b.stride(0), nsum, _p(y), y.stride(0), y.shape[0], Ng, G, R, float(s))
+    return y
+
+
+def lora_wgrad(a, b, out, *, G=1, bg=0, ncopy=1, s=1.0, msplit=0):
+    """out[(n*G + g)*R + i][c] = sum_m a[m][g*R + i] bs[m][g*bg + c] for n < ncopy (lap_lora_wgrad): dA = dt^T x (G = 1) and
+    dB = t^T dy (bs = bf16(s dy)), into a bf16 or f32 gradient buffer.  msplit = 0: split M until the grid has ~1024 blocks."""
+    _req2(a, torch.bfloat16, "a"); _req2(b, torch.bfloat16, "b")
+    if out.dtype not in (torch.bfloat16, torch.float32) or out.dim() != 2 or out.stride(1) != 1:
+        raise TypeError("lora_wgrad: out must be a row-major 2-D bf16 / f32 tensor")
+    M = a.shape[0]
+    GR = out.shape[0] // ncopy
+    R, Ng = GR // G, out.shape[1]
+    if b.shape[0] != M:
+        raise ValueError("lora_wgrad: a and b need the same rows")
+    if msplit <= 0:
+        blocks = ((Ng + 63) // 64) * (GR // 16)
+        msplit = max(1, min((1024 + blocks - 1) // blocks, M // 256))
+    scratch = _gemm_scratch(a.device) if msplit > 1 else None
+    call("lap_lora_wgrad", _p(a), a.stride(0), _p(b), b.stride(0), bg, _p(out), out.stride(0), ncopy, int(out.dtype == torch.float32),
+         M, Ng, G, R, float(s), msplit, _p(scratch), scratch.numel() if scratch is not None else 0)
+    return out
+
+
+def lora_merge(w, a, b, out, *, G=1, nsum=1, s=1.0):
+    """out = bf16(w + s . (B^T A) per group) (lap_lora_merge): the merged bf16 weight of a LoRA'd projection from f32 w [G*Ng][I],
+    a [G*R][I], b [nsum*G*R][Ng] (the serving paths' weights)."""
+    for t, nm in ((w, "w"), (a, "a"), (b, "b")):
+        _req2(t, torch.float32, nm)
+    _req2(out, torch.bfloat16, "out")
+    R = a.shape[0] // G
+    Ng = b.shape[1]
+    if w.shape[0] != G * Ng or out.shape != w.shape or a.shape[1] != w.shape[1] or b.shape[0] != nsum * G * R:
+        raise ValueError(f"lora_merge: w {tuple(w.shape)}, a {tuple(a.shape)}, b {tuple(b.shape)}, G {G}, nsum {nsum}")
+    call("lap_lora_merge", _p(w), w.stride(0), _p(a), a.stride(0), _p(b), b.stride(0), nsum, _p(out), out.stride(0), w.shape[1], Ng, G,
+         R, float(s))
+    return out

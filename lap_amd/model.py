@@ -30,7 +30,7 @@ import torch
 from lap_amd import hip
 from lap_amd.config import LAPConfig, get_gemma_config, get_siglip_config
 from lap_amd.observation import CoTObservation, preprocess_observation
-from lap_amd.params import ParamStore
+from lap_amd.params import LORA_PROJ, ParamStore, lora_geometry
 
 SUFFIX_IDX_BASE = 0x800000  # suffix ar-indices live above every prefix index (see _train_infos)
 
@@ -138,6 +138,18 @@ class LAP:
         self._wg = self._wg_obj = self._wg_main = None
         self._wg_dirty = False
         self._wg_ev: dict = {}
+        # LoRA adapters (config.GemmaConfig.lora_attn / lora_ffn): projection key ("wgu0", ...) -> (G, nsum, s), see params.lora_geometry.
+        # Training keeps base and adapters apart (csrc/lora.hip); the serving paths run on merged weights (`_serving_weights`)
+        self._lora_geo = {}
+        for i, c in enumerate((self.v, self.e)):
+            for proj in LORA_PROJ:
+                geo = lora_geometry(c, proj, self.v.num_heads, self.v.num_kv_heads, self.v.head_dim)
+                if geo is not None:
+                    self._lora_geo[f"{proj}{i}"] = (geo[0], geo[2], geo[3])
+        self._merge_depth = 0
+        self._merged_w: dict = {}   # "llm/{l}/<proj><i>" -> [store version, merged bf16 weight]
+        if self._lora_geo and gemm_dtype == "fp8":
+            raise ValueError("gemm_dtype='fp8' has no LoRA route: use gemm_dtype='bf16' with the LoRA Gemma variants")
         if gemm_dtype == "fp8":
             dims = (self.v.width, self.v.num_heads * self.v.head_dim, self.v.mlp_dim, (self.v.num_heads + 2 * self.v.num_kv_heads) * self.v.head_dim)
             if any(d % 128 for d in dims):
@@ -167,6 +179,8 @@ class LAP:
                     t.record_stream(dst)
 
     def W(self, name):
+        if self._merge_depth and name.rsplit("/", 1)[-1] in self._lora_geo:
+            return self._merged(name)
         return self.ps.w16(name)
 
     def F(self, name):
@@ -256,6 +270,85 @@ class LAP:
         self._wg_join()
         self._wg = None
 
+    # ---- LoRA adapters (lora.Einsum / lora.FeedForward, gemma.py:180-200,279-285,366-372; csrc/lora.hip)
+    def _lora(self, name):
+        """(A, B, G, nsum, s) of the adapters on projection `name` ("llm/{l}/wgu0", ...), or None: no adapters there, or the
+        serving paths are running on merged weights."""
+        if not self._lora_geo or self._merge_depth:
+            return None
+        _, l, key = name.split("/")
+        geo = self._lora_geo.get(key)
+        if geo is None:
+            return None
+        return (self.ps.w16(f"llm/{l}/lora_a_{key}"), self.ps.w16(f"llm/{l}/lora_b_{key}"), *geo)
+
+    def _lora_fwd(self, x, y, name):
+        """y += bf16(s * bf16(t B)) in place with t = bf16(x A^T), per group; returns t (kept for the backward) or None.
+        Where the base projection has a fused residual, y already holds it: the LoRA term is added after."""
+        lo = self._lora(name)
+        if lo is None:
+            return None
+        A, Bm, G, nsum, s = lo
+        t = hip.lora_down(x, A)
+        hip.lora_up_add(y, t, Bm, G=G, nsum=nsum, s=s)
+        return t
+
+    def _lora_bwd(self, dy, x, t, dx, name):
+        """The adapters' share of a projection's backward: dt = bf16(bf16(s dy) B^T) per group, dx += bf16(dt A) in place, and the
+        adapter gradients dA = dt^T x, dB = t^T bf16(s dy) (every stacked copy of B gets dB) like `_wgrad` (off the path where the
+        base projection's would be)."""
+        lo = self._lora(name)
+        if lo is None:
+            return
+        A, Bm, G, nsum, s = lo
+        Ng = Bm.shape[1]
+        dt = hip.lora_down(dy, Bm, G=G, nsum=nsum, xg=Ng if G > 1 else 0, s=s)
+        _, l, key = name.split("/")
+        na, nb = f"llm/{l}/lora_a_{key}", f"llm/{l}/lora_b_{key}"
+
+        def run():
+            if self.ps.is_trainable(na):
+                hip.lora_wgrad(dt, x, self.G(na))
+            if self.ps.is_trainable(nb):
+                hip.lora_wgrad(t, dy, self.G(nb), G=G, bg=Ng if G > 1 else 0, ncopy=nsum, s=s)
+        mode = self.wgrad_stream
+        if mode == "1" or ("q" if key in ("wqkv0", "wo0") else "g") in mode:
+            with self._off_path(dy, x, t, dt):
+                run()
+        else:
+            run()
+        if dx is not None:
+            hip.lora_up_add(dx, dt, A)
+
+    def _merged(self, name):
+        """bf16(W + s B^T A) of a LoRA'd projection from the f32 masters, rounded once (csrc/lora.hip lap_lora_merge): persistent
+        like `_serve_mods` and recomputed in place per parameter version."""
+        rec = self._merged_w.get(name)
+        if rec is None or rec[0] != self.ps.version:
+            if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("serving caches are stale inside a stream capture: call refresh_serve_caches() first")
+            _, l, key = name.split("/")
+            G, nsum, s = self._lora_geo[key]
+            out = rec[1] if rec is not None else torch.empty(self.ps.tensor_spec[name].shape, dtype=torch.bfloat16, device=self.device)
+            hip.lora_merge(self.F(name), self.F(f"llm/{l}/lora_a_{key}"), self.F(f"llm/{l}/lora_b_{key}"), out, G=G, nsum=nsum, s=s)
+            self._merged_w[name] = rec = [self.ps.version, out]
+        return rec[1]
+
+    @contextlib.contextmanager
+    def _serving_weights(self):
+        """The serving paths (sample_actions, sample_tokens, their caches) read every LoRA'd projection as ONE merged bf16 weight
+        (`_merged`) instead of base + adapters: every fused serving kernel applies unchanged.  The reference serves unmerged."""
+        if not self._lora_geo:
+            yield
+            return
+        if self.comm.world_size != 1:
+            raise NotImplementedError("LoRA serving merges the weights from the f32 masters: replicas only")
+        self._merge_depth += 1
+        try:
+            yield
+        finally:
+            self._merge_depth -= 1
+
     # ---- fp8 routing of the VLM expert's projections (BASELINE.json config 5; csrc/gemm_fp8.hip)
     def _w8_of(self, name):
         """(W8 [out][in], W8t [in][out], scale) of a VLM projection, re-quantised when the parameters changed."""
@@ -287,7 +380,8 @@ class LAP:
 
     def _prefix_frozen(self) -> bool:
         """True when no parameter reached by the prefix stream's backward is trainable (e.g. `get_vlm_freeze_filter`):
-        the language-head, VLM and SigLIP backward passes are then skipped altogether."""
+        the language-head, VLM and SigLIP backward passes are then skipped altogether.  The VLM's adapters
+        (`llm/{l}/lora_{a,b}_<proj>0`) end in "0" like its base weights: under `get_freeze_filter` they keep this False."""
         fr = self.ps.frozen
         if not fr:
             return False
@@ -703,9 +797,11 @@ class LAP:
             self.comm.wait_unit(f"llm{l}", also=sfx)
             p = f"llm/{l}/"
             q = [None, None]; k = [None, None]; vv = [None, None]; h = [None, None]; rstd_a = [None, None]
+            lt = [{}, {}]       # LoRA down products t per stream and projection (kept for the backward)
             if x0 is not None:
                 h[0], rstd_a[0] = hip.rmsnorm_fwd(x0, scale=self.F(p + "n_attn"), save_rstd=save)
                 qkv = self._lin0(h[0], p + "wqkv0")
+                lt[0]["wqkv"] = self._lora_fwd(h[0], qkv, p + "wqkv0")
                 q[0], k[0], vv[0] = hip.rope_split_fwd(qkv, pos, B, n0, Ttot, 0, NH, HD, HD ** -0.5)
                 del qkv
             elif kv_cache is not None:
@@ -717,6 +813,7 @@ class LAP:
                     else:
                         h[1], rstd_a[1] = hip.rmsnorm_fwd(x1, mod=self._mod_slot(mod, 2 * l), rows_per_sample=n1, save_rstd=save, mod_ld=mld)
                     qkv = hip.linear_fwd(h[1], self.W(p + "wqkv1"))
+                    lt[1]["wqkv"] = self._lora_fwd(h[1], qkv, p + "wqkv1")
                     q[1], k[1], vv[1] = hip.rope_split_fwd(qkv, pos, B, n1, Ttot, Ttot - n1, NH, HD, HD ** -0.5)
                     del qkv
                 self._handoff(sfx, main, q[1], k[1], vv[1])
@@ -731,24 +828,31 @@ class LAP:
             if x1 is not None and mod is None:       # pi0: plain residuals (gemma.py:577-583 with gate None)
                 with on_sfx():
                     xa[1] = hip.linear_fwd(o[1], self.W(p + "wo1"), residual=x1)
+                    lt[1]["wo"] = self._lora_fwd(o[1], xa[1], p + "wo1")
                     hf[1], rstd_f[1] = hip.rmsnorm_fwd(xa[1], scale=self.F(p + "n_ffw1"), save_rstd=save)
                     gu[1] = hip.linear_fwd(hf[1], self.W(p + "wgu1"))
+                    lt[1]["wgu"] = self._lora_fwd(hf[1], gu[1], p + "wgu1")
                     act[1] = hip.geglu_fwd(gu[1])
                     xn[1] = hip.linear_fwd(act[1], self.W(p + "wd1"), residual=xa[1])
+                    lt[1]["wd"] = self._lora_fwd(act[1], xn[1], p + "wd1")
             elif x1 is not None:     # (issued first: 8 short kernels that then run under the prefix stream's GEMMs)
                 with on_sfx():
                     y1 = hip.linear_fwd(o[1], self.W(p + "wo1"))
+                    lt[1]["wo"] = self._lora_fwd(o[1], y1, p + "wo1")
                     xa[1] = hip.gated_residual_fwd(x1, y1, self._mod_slot(mod, 2 * l)[:, 2 * e.width:], n1, mld)
                     hf[1], rstd_f[1] = hip.rmsnorm_fwd(xa[1], mod=self._mod_slot(mod, 2 * l + 1), rows_per_sample=n1, save_rstd=save, mod_ld=mld)
                     gu[1] = hip.linear_fwd(hf[1], self.W(p + "wgu1"))
+                    lt[1]["wgu"] = self._lora_fwd(hf[1], gu[1], p + "wgu1")
                     act[1] = hip.geglu_fwd(gu[1])
                     y1f = hip.linear_fwd(act[1], self.W(p + "wd1"))
+                    lt[1]["wd"] = self._lora_fwd(act[1], y1f, p + "wd1")
                     xn[1] = hip.gated_residual_fwd(xa[1], y1f, self._mod_slot(mod, 2 * l + 1)[:, 2 * e.width:], n1, mld)
             if x0 is not None:
                 xa[0] = self._lin0(o[0], p + "wo0", residual=x0)
+                lt[0]["wo"] = self._lora_fwd(o[0], xa[0], p + "wo0")
                 hf[0], rstd_f[0] = hip.rmsnorm_fwd(xa[0], scale=self.F(p + "n_ffw"), save_rstd=save)
                 self.comm.pace(f"llm{l}")     # optimizer units released here start under the longest MFMA-bound GEMM of the layer
-                if save and self.fuse_geglu_fwd and hip.linear_geglu_train_ok(hf[0], self.W(p + "wgu0")):
+                if save and self.fuse_geglu_fwd and self._lora(p + "wgu0") is None and hip.linear_geglu_train_ok(hf[0], self.W(p + "wgu0")):
                     # gate | up projection with the GeGLU in its epilogue: gu (kept for the backward pass) and act leave one launch
                     gu[0], act[0] = hip.linear_geglu_train(hf[0], self.W(p + "wgu0"))
                 else:
@@ -756,11 +860,13 @@ class LAP:
                     if save and self.fuse_geglu_bwd:    # rows padded like d(gate | up): the fused backward kernel shares one row stride
                         gu_out = hip._padded_rows(hf[0].shape[0], 2 * v.mlp_dim, hf[0].device, hip._row_pad(2 * v.mlp_dim))
                     gu[0] = self._lin0(hf[0], p + "wgu0", out=gu_out)
+                    lt[0]["wgu"] = self._lora_fwd(hf[0], gu[0], p + "wgu0")   # (before the GeGLU: lora.FeedForward's _dot)
                     act[0] = hip.geglu_fwd(gu[0], pad=self.gemm_dtype != "fp8")
                 xn[0] = self._lin0(act[0], p + "wd0", residual=xa[0])
+                lt[0]["wd"] = self._lora_fwd(act[0], xn[0], p + "wd0")
             if save:
                 ctx.append(dict(x=[x0, x1], h=h, rstd_a=rstd_a, q=q, k=k, v=vv, o=o, lse=lse, xa=xa, y1=y1, hf=hf, rstd_f=rstd_f,
-                                gu=gu, act=act, y1f=y1f))
+                                gu=gu, act=act, y1f=y1f, lt=lt))
             x0, x1 = xn
             if collect is not None:
                 collect[f"llm/layer{l:02d}/x0"], collect[f"llm/layer{l:02d}/x1"] = x0, x1
@@ -840,12 +946,15 @@ class LAP:
                 with on_sfx():      # xn = xa + act wd^T, xa = x + o wo^T: the residuals pass dx1 through, the norms add onto it in place
                     self._wgrad(dx1, c["act"][1], p + "wd1")
                     dact = hip.linear_dgrad(dx1, self.W(p + "wd1"))
+                    self._lora_bwd(dx1, c["act"][1], c["lt"][1].get("wd"), dact, p + "wd1")
                     dgu = hip.geglu_bwd(c["gu"][1], dact)
                     self._wgrad(dgu, c["hf"][1], p + "wgu1")
                     dhf = hip.linear_dgrad(dgu, self.W(p + "wgu1"))
+                    self._lora_bwd(dgu, c["hf"][1], c["lt"][1].get("wgu"), dhf, p + "wgu1")
                     hip.rmsnorm_bwd(c["xa"][1], dhf, c["rstd_f"][1], scale=self.F(p + "n_ffw1"), dx=dx1, dscale=self.G(p + "n_ffw1"), accum_dx=True)
                     self._wgrad(dx1, c["o"][1], p + "wo1")
                     d_o[1] = hip.linear_dgrad(dx1, self.W(p + "wo1"))
+                    self._lora_bwd(dx1, c["o"][1], c["lt"][1].get("wo"), d_o[1], p + "wo1")
                     del dact, dgu, dhf
             elif has_sfx:
                 with on_sfx():
@@ -853,34 +962,40 @@ class LAP:
                     dy1f = hip.gated_residual_bwd(dx1, c["y1f"], gate_f, n1, ldm, self._mod_slot(dmod, slot_f)[:, 2 * e.width:], dmod.stride(0))
                     self._wgrad(dy1f, c["act"][1], p + "wd1")
                     dact = hip.linear_dgrad(dy1f, self.W(p + "wd1"))
+                    self._lora_bwd(dy1f, c["act"][1], c["lt"][1].get("wd"), dact, p + "wd1")
                     dgu = hip.geglu_bwd(c["gu"][1], dact)
                     self._wgrad(dgu, c["hf"][1], p + "wgu1")
                     dhf = hip.linear_dgrad(dgu, self.W(p + "wgu1"))
+                    self._lora_bwd(dgu, c["hf"][1], c["lt"][1].get("wgu"), dhf, p + "wgu1")
                     hip.rmsnorm_bwd(c["xa"][1], dhf, c["rstd_f"][1], mod=self._mod_slot(mod, slot_f), rows_per_sample=n1, dx=dx1,
                                     dmod=self._mod_slot(dmod, slot_f), accum_dx=True)
                     gate_a = self._mod_slot(mod, slot_a)[:, 2 * e.width:]
                     dy1 = hip.gated_residual_bwd(dx1, c["y1"], gate_a, n1, ldm, self._mod_slot(dmod, slot_a)[:, 2 * e.width:], dmod.stride(0))
                     self._wgrad(dy1, c["o"][1], p + "wo1")
                     d_o[1] = hip.linear_dgrad(dy1, self.W(p + "wo1"))
+                    self._lora_bwd(dy1, c["o"][1], c["lt"][1].get("wo"), d_o[1], p + "wo1")
                     del dy1f, dact, dgu, dhf, dy1
             # ---- FFN, prefix stream: xn = xa + act @ wd^T   (dx0 is None: the whole prefix side is frozen)
             if dx0 is not None:
                 self._wgrad(dx0, c["act"][0], p + "wd0")
-                if self.fuse_geglu_bwd and hip.dgrad_geglu_bwd_ok(dx0, self.W(p + "wd0"), c["gu"][0]):
+                if self.fuse_geglu_bwd and self._lora(p + "wd0") is None and hip.dgrad_geglu_bwd_ok(dx0, self.W(p + "wd0"), c["gu"][0]):
                     # the down projection's data gradient with the GeGLU backward as its epilogue: d(act) never reaches memory
                     dgu = hip.linear_dgrad_geglu_bwd(dx0, self.W(p + "wd0"), c["gu"][0])
                 else:
                     dact = self._dgrad0(dx0, p + "wd0")
+                    self._lora_bwd(dx0, c["act"][0], c["lt"][0].get("wd"), dact, p + "wd0")
                     dgu = hip.geglu_bwd(c["gu"][0], dact, pad=self.gemm_dtype != "fp8")
                     del dact
                 self._wgrad(dgu, c["hf"][0], p + "wgu0")
                 dhf = self._dgrad0(dgu, p + "wgu0")
+                self._lora_bwd(dgu, c["hf"][0], c["lt"][0].get("wgu"), dhf, p + "wgu0")
                 del dgu
                 self._wg_join(dx0)   # (the down projection's weight gradient reads dx0)
                 hip.rmsnorm_bwd(c["xa"][0], dhf, c["rstd_f"][0], scale=self.F(p + "n_ffw"), dx=dx0, dscale=self.G(p + "n_ffw"), accum_dx=True)
                 del dhf
                 self._wgrad(dx0, c["o"][0], p + "wo0")
                 d_o[0] = self._dgrad0(dx0, p + "wo0")
+                self._lora_bwd(dx0, c["o"][0], c["lt"][0].get("wo"), d_o[0], p + "wo0")
             else:   # the attention backward still needs a dO for the prefix queries: zero (their dq / dk / dv are discarded)
                 if zero_do0 is None:
                     zero_do0 = torch.zeros_like(c["o"][0])
@@ -895,6 +1010,7 @@ class LAP:
                     dqkv = hip.rope_split_bwd(dq[1], dk[1], dv[1], pos, B, n1, Ttot, Ttot - n1, NH, HD, HD ** -0.5)
                     self._wgrad(dqkv, c["h"][1], p + "wqkv1")
                     dh = hip.linear_dgrad(dqkv, self.W(p + "wqkv1"))
+                    self._lora_bwd(dqkv, c["h"][1], c["lt"][1].get("wqkv"), dh, p + "wqkv1")
                     if ada:
                         hip.rmsnorm_bwd(c["x"][1], dh, c["rstd_a"][1], mod=self._mod_slot(mod, slot_a), rows_per_sample=n1, dx=dx1,
                                         dmod=self._mod_slot(dmod, slot_a), accum_dx=True)
@@ -905,6 +1021,7 @@ class LAP:
                 dqkv = hip.rope_split_bwd(dq[0], dk[0], dv[0], pos, B, n0, Ttot, 0, NH, HD, HD ** -0.5)
                 self._wgrad(dqkv, c["h"][0], p + "wqkv0")
                 dh = self._dgrad0(dqkv, p + "wqkv0")
+                self._lora_bwd(dqkv, c["h"][0], c["lt"][0].get("wqkv"), dh, p + "wqkv0")
                 self._wg_join(dx0)   # (the out projection's reads dx0)
                 hip.rmsnorm_bwd(c["x"][0], dh, c["rstd_a"][0], scale=self.F(p + "n_attn"), dx=dx0, dscale=self.G(p + "n_attn"), accum_dx=True)
                 del dqkv, dh
@@ -1229,6 +1346,11 @@ class LAP:
         expert attending to [cached prefix | fresh suffix] as two key segments (the reference concatenates, gemma.py:228-230).
         `fused`: True = the fastest denoise-step kernels the shapes allow ("skinny" fused projections for the LAP-3B action
         expert, else "partials" = split-K partial slabs + fused consumers); False = the generic layer path (A/B tests)."""
+        with self._serving_weights():
+            return self._sample_actions(rng, observation, num_steps=num_steps, noise=noise, collect=collect, fused=fused)
+
+    def _sample_actions(self, rng, observation, *, num_steps: int = 10, noise=None, collect=None, fused=True):
+        """`sample_actions` with the weights as `_serving_weights` presents them (merged when the model has adapters)."""
         cfg = self.config
         dev = self.device
         self.comm.wait_unit("small")
@@ -1436,8 +1558,15 @@ class LAP:
         return n, dt
 
     def refresh_serve_caches(self, num_steps: int = 10):
-        """Bring the sampler's parameter-derived caches (adaRMS modulations, packed expert weights) up to the current parameter
-        version, in place.  Eager `sample_actions` does this itself; a captured graph cannot — call it before a replay."""
+        """Bring the sampler's parameter-derived caches (merged LoRA weights, adaRMS modulations, packed expert weights) up to the
+        current parameter version, in place.  Eager `sample_actions` does this itself; a captured graph cannot — call it before a replay."""
+        with self._serving_weights():
+            self._refresh_serve_caches(num_steps)
+
+    def _refresh_serve_caches(self, num_steps: int):
+        for name in list(self._merged_w):      # (first: the packed images below are made from them)
+            self.comm.wait_unit("llm" + name.split("/")[1])
+            self._merged(name)
         n, dt = self._time_grid(num_steps)
         for name in list(self._prefill_pw):
             kind, l = name.split("/")[:2]
@@ -1506,6 +1635,11 @@ class LAP:
         rows, so decode logits differ from the reference in that case only (prefill logits still agree; tested).
         temperature > 0 samples with the Gumbel-max trick from a torch generator seeded by `rng` (the JAX PRNG stream of
         `jax.random.categorical` cannot be reproduced)."""
+        with self._serving_weights():
+            return self._sample_tokens(rng, observation, max_decoding_steps=max_decoding_steps, temperature=temperature, collect=collect)
+
+    def _sample_tokens(self, rng, observation, *, max_decoding_steps: int = 390, temperature: float = 0.0, collect=None):
+        """`sample_tokens` with the weights as `_serving_weights` presents them (merged when the model has adapters)."""
         cfg = self.config
         dev = self.device
         if self.comm.world_size != 1:

@@ -69,6 +69,42 @@ def siglip_mlp_pad(mlp_dim: int) -> int:
     return _align(mlp_dim, 256)
 
 
+LORA_PROJ = ("wqkv", "wo", "wgu", "wd")
+LORA_INIT_STD = 0.01    # lora.LoRAConfig.init_fn = normal(stddev=0.01) for both lora_a and lora_b [UPSTREAM-RECALL]
+
+
+def lora_geometry(c, proj: str, NH: int, KV: int, HD: int) -> tuple | None:
+    """(G, r, nsum, s) of projection `proj` of Gemma config `c` — G groups of rank r (q|k|v: one per head, gate|up: two), nsum stacked
+    copies of B that are summed (attn_vec_einsum: one per head), s the scaling of the LoRA term — or None without adapters.  Engine layouts
+    (lap_amd/csrc/lora.hip): A [G*r][in] (k contiguous, one down product serves every group), B [nsum*G*r][out per group]."""
+    lc = c.lora_attn if proj in ("wqkv", "wo") else c.lora_ffn
+    if lc is None:
+        return None
+    r, alpha = int(lc[0]), float(lc[1])
+    G, nsum = {"wqkv": (NH + 2 * KV, 1), "wo": (1, NH), "wgu": (2, 1), "wd": (1, 1)}[proj]
+    # lora.Einsum scales by alpha / rank; lora.FeedForward's _dot(x, w, (a, b)) = x w + (x a) b has no scaling [UPSTREAM-RECALL]
+    return G, r, nsum, (alpha / r if proj in ("wqkv", "wo") else 1.0)
+
+
+def lora_specs(cfg: LAPConfig, l: int) -> list:
+    """Adapter tensors of joint layer l (`llm/{l}/lora_a_<proj><i>`, `lora_b_...`; i = 0 VLM, 1 action expert), inside the
+    layer's unit so that FSDP gathers them with it.  The names end in the expert index like the base weights'."""
+    v, e = get_gemma_config(cfg.paligemma_variant), get_gemma_config(cfg.action_expert_variant)
+    NH, KV, HD = v.num_heads, v.num_kv_heads, v.head_dim
+    out = []
+    for i, c in enumerate((v, e)):
+        dims = {"wqkv": (c.width, HD), "wo": (NH * HD, c.width), "wgu": (c.width, c.mlp_dim), "wd": (c.mlp_dim, c.width)}
+        for proj in LORA_PROJ:
+            geo = lora_geometry(c, proj, NH, KV, HD)
+            if geo is None:
+                continue
+            G, r, nsum, _ = geo
+            din, dout = dims[proj]
+            out += [TensorSpec(f"llm/{l}/lora_a_{proj}{i}", (G * r, din), LORA_INIT_STD),
+                    TensorSpec(f"llm/{l}/lora_b_{proj}{i}", (nsum * G * r, dout), LORA_INIT_STD)]
+    return out
+
+
 def build_specs(cfg: LAPConfig) -> list[UnitSpec]:
     v, e, s = get_gemma_config(cfg.paligemma_variant), get_gemma_config(cfg.action_expert_variant), get_siglip_config(cfg.siglip_variant)
     if (v.depth, v.num_heads, v.num_kv_heads, v.head_dim) != (e.depth, e.num_heads, e.num_kv_heads, e.head_dim):
@@ -110,7 +146,7 @@ def build_specs(cfg: LAPConfig) -> list[UnitSpec]:
             TensorSpec(f"llm/{l}/wqkv1", (QKV, e.width), e.width ** -0.5),
             TensorSpec(f"llm/{l}/wo1", (e.width, NH * HD), (NH * HD) ** -0.5),
             TensorSpec(f"llm/{l}/wgu1", (2 * e.mlp_dim, e.width), e.width ** -0.5),
-            TensorSpec(f"llm/{l}/wd1", (e.width, e.mlp_dim), e.mlp_dim ** -0.5)], True))
+            TensorSpec(f"llm/{l}/wd1", (e.width, e.mlp_dim), e.mlp_dim ** -0.5)] + lora_specs(cfg, l), True))
     nslots = ADA_SLOTS_PER_LAYER * L + 1
     small += [TensorSpec("llm/final_norm", (v.width,), 0.0)]
     ad, w = cfg.action_dim, e.width
@@ -445,6 +481,11 @@ def engine_sources(cfg: LAPConfig) -> dict[str, list[str]]:
             out[f"llm/{l}/wo{i}"] = [f"{lay}/attn/attn_vec_einsum{sfx}/w"]
             out[f"llm/{l}/wgu{i}"] = [f"{lay}/mlp{sfx}/gating_einsum"]
             out[f"llm/{l}/wd{i}"] = [f"{lay}/mlp{sfx}/linear"]
+            for ab in ("a", "b"):
+                out[f"llm/{l}/lora_{ab}_wqkv{i}"] = [f"{lay}/attn/q_einsum{sfx}/lora_{ab}", f"{lay}/attn/kv_einsum{sfx}/lora_{ab}"]
+                out[f"llm/{l}/lora_{ab}_wo{i}"] = [f"{lay}/attn/attn_vec_einsum{sfx}/lora_{ab}"]
+                out[f"llm/{l}/lora_{ab}_wgu{i}"] = [f"{lay}/mlp{sfx}/gating_einsum_lora_{ab}"]
+                out[f"llm/{l}/lora_{ab}_wd{i}"] = [f"{lay}/mlp{sfx}/linear_lora_{ab}"]
         out[f"llm/{l}/n_attn"], out[f"llm/{l}/n_ffw"] = [f"{lay}/pre_attention_norm/scale"], [f"{lay}/pre_ffw_norm/scale"]
         if not cfg.pi05:
             out[f"llm/{l}/n_attn1"], out[f"llm/{l}/n_ffw1"] = [f"{lay}/pre_attention_norm_1/scale"], [f"{lay}/pre_ffw_norm_1/scale"]
@@ -452,7 +493,8 @@ def engine_sources(cfg: LAPConfig) -> dict[str, list[str]]:
         (("state", "state_proj"), ("atime_in", "action_time_mlp_in"), ("atime_out", "action_time_mlp_out"))
     for nm, ref in (("in", "action_in_proj"), *heads, ("out", "action_out_proj")):
         out[f"act/{nm}_w"], out[f"act/{nm}_b"] = [f"{ref}/kernel"], [f"{ref}/bias"]
-    return out
+    specs = {t.name for u in build_specs(cfg) for t in u.tensors}
+    return {k: v for k, v in out.items() if "/lora_" not in k or k in specs}
 
 
 def _is_action_expert_key(k: str) -> bool:
@@ -528,6 +570,21 @@ def reference_to_engine(cfg: LAPConfig, P: dict) -> dict[str, torch.Tensor]:
             ge = T(f"{lay}/mlp{sfx}/gating_einsum")[l]
             out[f"llm/{l}/wgu{i}"] = torch.cat([ge[0].t(), ge[1].t()], 0).contiguous()
             out[f"llm/{l}/wd{i}"] = T(f"{lay}/mlp{sfx}/linear")[l].t().contiguous()
+            if c.lora_attn is not None:
+                qa, kva = T(f"{lay}/attn/q_einsum{sfx}/lora_a")[l], T(f"{lay}/attn/kv_einsum{sfx}/lora_a")[l]    # [N,D,r], [2,K,D,r]
+                qb, kvb = T(f"{lay}/attn/q_einsum{sfx}/lora_b")[l], T(f"{lay}/attn/kv_einsum{sfx}/lora_b")[l]    # [N,r,H], [2,K,r,H]
+                r = qa.shape[-1]
+                out[f"llm/{l}/lora_a_wqkv{i}"] = torch.cat([qa.permute(0, 2, 1).reshape(-1, c.width),
+                                                           kva.permute(0, 1, 3, 2).reshape(-1, c.width)], 0).contiguous()
+                out[f"llm/{l}/lora_b_wqkv{i}"] = torch.cat([qb.reshape(-1, HD), kvb.reshape(-1, HD)], 0).contiguous()
+                out[f"llm/{l}/lora_a_wo{i}"] = T(f"{lay}/attn/attn_vec_einsum{sfx}/lora_a")[l].reshape(NH * HD, r).t().contiguous()
+                out[f"llm/{l}/lora_b_wo{i}"] = T(f"{lay}/attn/attn_vec_einsum{sfx}/lora_b")[l].reshape(NH * r, c.width).contiguous()
+            if c.lora_ffn is not None:
+                ga = T(f"{lay}/mlp{sfx}/gating_einsum_lora_a")[l]      # [2, D, r]
+                out[f"llm/{l}/lora_a_wgu{i}"] = ga.permute(0, 2, 1).reshape(-1, c.width).contiguous()
+                out[f"llm/{l}/lora_b_wgu{i}"] = T(f"{lay}/mlp{sfx}/gating_einsum_lora_b")[l].reshape(-1, c.mlp_dim).contiguous()
+                out[f"llm/{l}/lora_a_wd{i}"] = T(f"{lay}/mlp{sfx}/linear_lora_a")[l].t().contiguous()
+                out[f"llm/{l}/lora_b_wd{i}"] = T(f"{lay}/mlp{sfx}/linear_lora_b")[l].contiguous()
         out[f"llm/{l}/n_attn"] = T(f"{lay}/pre_attention_norm/scale")[l]
         out[f"llm/{l}/n_ffw"] = T(f"{lay}/pre_ffw_norm/scale")[l]
         if not cfg.pi05:
@@ -599,6 +656,22 @@ def _engine_to_reference_full(cfg: LAPConfig, E: dict) -> dict[str, torch.Tensor
         P[f"{lay}/attn/attn_vec_einsum{sfx}/w"] = sl(lambda l: E[f"llm/{l}/wo{i}"].t().reshape(NH, HD, c.width))
         P[f"{lay}/mlp{sfx}/gating_einsum"] = sl(lambda l: torch.stack([E[f"llm/{l}/wgu{i}"][:c.mlp_dim].t(), E[f"llm/{l}/wgu{i}"][c.mlp_dim:].t()], 0))
         P[f"{lay}/mlp{sfx}/linear"] = sl(lambda l: E[f"llm/{l}/wd{i}"].t())
+        if c.lora_attn is not None:
+            r = c.lora_attn[0]
+            A = lambda l: E[f"llm/{l}/lora_a_wqkv{i}"]
+            Bq = lambda l: E[f"llm/{l}/lora_b_wqkv{i}"]
+            P[f"{lay}/attn/q_einsum{sfx}/lora_a"] = sl(lambda l: A(l)[:NH * r].reshape(NH, r, c.width).permute(0, 2, 1))
+            P[f"{lay}/attn/kv_einsum{sfx}/lora_a"] = sl(lambda l: A(l)[NH * r:].reshape(2, KV, r, c.width).permute(0, 1, 3, 2))
+            P[f"{lay}/attn/q_einsum{sfx}/lora_b"] = sl(lambda l: Bq(l)[:NH * r].reshape(NH, r, HD))
+            P[f"{lay}/attn/kv_einsum{sfx}/lora_b"] = sl(lambda l: Bq(l)[NH * r:].reshape(2, KV, r, HD))
+            P[f"{lay}/attn/attn_vec_einsum{sfx}/lora_a"] = sl(lambda l: E[f"llm/{l}/lora_a_wo{i}"].t().reshape(NH, HD, r))
+            P[f"{lay}/attn/attn_vec_einsum{sfx}/lora_b"] = sl(lambda l: E[f"llm/{l}/lora_b_wo{i}"].reshape(NH, r, c.width))
+        if c.lora_ffn is not None:
+            r = c.lora_ffn[0]
+            P[f"{lay}/mlp{sfx}/gating_einsum_lora_a"] = sl(lambda l: E[f"llm/{l}/lora_a_wgu{i}"].reshape(2, r, c.width).permute(0, 2, 1))
+            P[f"{lay}/mlp{sfx}/gating_einsum_lora_b"] = sl(lambda l: E[f"llm/{l}/lora_b_wgu{i}"].reshape(2, r, c.mlp_dim))
+            P[f"{lay}/mlp{sfx}/linear_lora_a"] = sl(lambda l: E[f"llm/{l}/lora_a_wd{i}"].t())
+            P[f"{lay}/mlp{sfx}/linear_lora_b"] = sl(lambda l: E[f"llm/{l}/lora_b_wd{i}"])
     P[f"{lay}/pre_attention_norm/scale"] = sl(lambda l: E[f"llm/{l}/n_attn"])
     P[f"{lay}/pre_ffw_norm/scale"] = sl(lambda l: E[f"llm/{l}/n_ffw"])
     W3 = 3 * e.width

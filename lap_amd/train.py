@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import dataclasses
 import os
+import re
 
 import torch
 
@@ -111,6 +112,11 @@ def load_weights(config: TrainConfig, store: ParamStore):
         loaded = ck.restore_params(wl.params_path)           # '/value' suffixes and the 'params/' prefix are stripped there
         subset = {k: torch.as_tensor(v) for k, v in loaded.items() if k in expected}     # _merge_params: subset of the model's keys
         allow_partial = config.allow_partial_weights
+        # CheckpointWeightLoader merges missing `.*lora.*` keys from the init (weight_loaders.py:105): a base checkpoint loads into a
+        # LoRA model with its adapters at their initial values whatever `allow_partial_weights` says
+        lora_missing = {k for k in expected if k not in subset and re.fullmatch(".*lora.*", k)}
+        subset = validate_loaded_params({k: v for k, v in expected.items() if k not in lora_missing}, subset, allow_partial=allow_partial)
+        allow_partial = True
     elif wl.kind == "paligemma":
         subset = load_paligemma_npz(wl.resolve_paligemma_path(), expected)
         allow_partial = True
