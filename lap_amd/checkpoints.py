@@ -5,6 +5,7 @@ Mirrors the surface of src/lap/training/checkpoints.py (SURVEY.md §5, §8(f) ra
     save_state(mngr, state, data_loader, step, preserve_checkpoint=False, max_retries=...)         (:163-339)
     state = restore_state(mngr, state, data_loader, step=None)                                      (:342-437)
     params = restore_params(mngr_or_dir, step=None)                                                 (:440-474)
+    params = restore_eval_params(mngr_or_dir, step, "ema" | "live", model_config)   (scripts/eval.py:340-364)
     load_norm_stats(assets_dir)                                                                     (:477-497)
 and its three checkpoint items per step (:42-64, 529-547):
     params/       the parameters used for inference — the EMA parameters when EMA is on, else the live ones
@@ -254,6 +255,47 @@ def restore_params(checkpoint_manager, step: int | None = None) -> dict:
         p = p / "params" / "params.safetensors"
     flat = _strip_value(_load_tensors(p))
     return {(k[len("params/"):] if k.startswith("params/") else k): v for k, v in flat.items()}
+
+
+def restore_eval_params(checkpoint_manager, step: int, which: str, model_config=None) -> dict:
+    """The parameters scripts/eval.py:352-364 scores, as a reference tree (f32, CPU), from a checkpoint written at ANY world size.
+    which="ema": the `params/` item (it holds the EMA when the run had one).  which="live": the `params/` item when the run had no
+    EMA, else the f32 masters of `train_state/`: each rank's `master/<unit>` slice, concatenated in rank order for the sharded units
+    (a slice shorter than the unit's padded size in meta.json) and rank 0's copy of the replicated ones, mapped to the reference
+    tree with `model_config` (the LAPConfig the checkpoint was trained with; needed for that case only)."""
+    if which not in ("ema", "live"):
+        raise ValueError(f"which must be 'ema' or 'live', got {which!r}")
+    p = checkpoint_manager.directory if isinstance(checkpoint_manager, CheckpointManager) else pathlib.Path(checkpoint_manager)
+    d = CheckpointManager(p).step_dir(int(step))
+    if not (d / _COMMIT).exists():
+        raise FileNotFoundError(f"no committed checkpoint for step {step} under {p}")
+    meta = json.loads((d / "train_state" / "meta.json").read_text())
+    if which == "ema" or not meta["has_ema"]:
+        if which == "ema" and not meta["has_ema"]:
+            raise ValueError(f"checkpoint {d} has no EMA parameters")
+        return restore_params(d)
+    if model_config is None:
+        raise ValueError("the live parameters of a checkpoint with EMA come from train_state/: pass model_config")
+    from lap_amd.params import build_specs, engine_to_reference
+
+    lay, now = meta.get("layout"), _engine_layout(model_config)
+    if lay is not None and lay != now:
+        raise ValueError(f"train_state/ of step {step} was written with engine layout {lay}, this process runs {now}")
+    world = int(meta["world_size"])
+    shards = [_load_tensors(d / "train_state" / f"rank{r}_of{world}.safetensors") for r in range(world)]
+    eng = {}
+    for u in build_specs(model_config):
+        padded = meta["units"].get(u.name)
+        if padded is None or padded < u.numel:
+            raise ValueError(f"unit {u.name}: checkpoint geometry {padded} does not hold the model's {u.numel} values")
+        key = f"master/{u.name}"
+        first = shards[0][key]
+        full = torch.cat([s[key] for s in shards]) if first.numel() < padded else first
+        if full.numel() != padded:
+            raise ValueError(f"unit {u.name}: {world} slices hold {full.numel()} values, meta.json says {padded}")
+        for t in u.tensors:
+            eng[t.name] = full[t.offset:t.offset + t.numel].view(t.shape)
+    return engine_to_reference(model_config, eng)
 
 
 def restore_state(checkpoint_manager: CheckpointManager, state, data_loader=None, step: int | None = None,

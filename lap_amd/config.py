@@ -411,6 +411,14 @@ class TrainConfig:
     allow_partial_weights: bool = True
     use_validation: bool = False
     val_interval: int = 2000
+    # checkpoint evaluation (scripts/eval.py, lap_amd/evaluate.py): which steps, how many batches, EMA or live weights, split
+    eval_checkpoint_step: int | None = None
+    eval_checkpoint_steps: tuple[int, ...] | None = None
+    eval_all_checkpoints: bool = True
+    eval_start_from_step: int | None = None
+    num_eval_batches: int | None = 500
+    eval_use_ema: bool = True
+    eval_split: str = "val"
     # openpi TrainConfig.freeze_filter (scripts/train.py:225-240,358-363): parameters it selects are kept out of the
     # gradient / optimizer and stored at bf16 precision.  None = nnx.Nothing; a regex string (full match on the
     # reference's '/'-joined path), a PathFilter or any predicate over the path.

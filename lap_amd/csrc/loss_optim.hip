@@ -11,13 +11,23 @@ namespace {
 // ------------------------------------------------------------------- CE forward
 // One block per row.  Online (max, sum-exp) over this vocab chunk merged into the
 // running state, plus the target logit if the target falls inside the chunk.
+// ARGMAX (verbose metrics, lap.py:265-277 jnp.argmax(logits)): also the running index of the row maximum in amax[r],
+// lowest index among ties, from the same pass over the logits.  Each thread visits its elements in ascending order and
+// moves its index only on a strictly greater value; lane / wave combines take "greater, or equal with the lower index";
+// across chunks (issued in ascending v0) amax[r] moves only when the chunk maximum is strictly greater than the incoming
+// m[r].  The float arithmetic of m / l / tl is the same in both instantiations.  Rows holding NaN are outside the contract
+// (their loss is NaN already): the index reported for them is unspecified.
+template <bool ARGMAX>
 __global__ __launch_bounds__(256) void ce_update_kernel(const float* __restrict__ logits, int ldl,
                                                         const int32_t* __restrict__ target, float* __restrict__ m,
-                                                        float* __restrict__ l, float* __restrict__ tl, int v0, int vc) {
+                                                        float* __restrict__ l, float* __restrict__ tl, int32_t* __restrict__ amax,
+                                                        int v0, int vc) {
   __shared__ float red_m[4], red_l[4];
+  __shared__ int red_i[4];
   const int r = blockIdx.x;
   const float* x = logits + (long long)r * ldl;
   float mm = -3.0e38f, ll = 0.f;
+  int bi = 0x7fffffff;                                  // index (within the chunk) of mm; ARGMAX only
   for (int v = threadIdx.x * 4; v < vc; v += 1024) {
     float vals[4];
     int n = min(4, vc - v);
@@ -29,7 +39,10 @@ __global__ __launch_bounds__(256) void ce_update_kernel(const float* __restrict_
     }
     for (int e = 0; e < n; ++e) {
       const float xv = vals[e];
-      if (xv > mm) { ll = ll * __expf(mm - xv) + 1.0f; mm = xv; }
+      if (xv > mm) {
+        ll = ll * __expf(mm - xv) + 1.0f; mm = xv;
+        if (ARGMAX) bi = v + e;
+      }
       else ll += __expf(xv - mm);
     }
   }
@@ -37,15 +50,26 @@ __global__ __launch_bounds__(256) void ce_update_kernel(const float* __restrict_
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const float om = __shfl_xor(mm, o, 64), ol = __shfl_xor(ll, o, 64);
+    if (ARGMAX) {
+      const int oi = __shfl_xor(bi, o, 64);
+      if (om > mm || (om == mm && oi < bi)) bi = oi;
+    }
     const float nm = fmaxf(mm, om);
     ll = ll * __expf(mm - nm) + ol * __expf(om - nm);
     mm = nm;
   }
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) { red_m[w] = mm; red_l[w] = ll; }
+  if (lane == 0) { red_m[w] = mm; red_l[w] = ll; if (ARGMAX) red_i[w] = bi; }
   __syncthreads();
   if (threadIdx.x == 0) {
     float gm = m[r], gl = l[r];
+    if (ARGMAX) {
+      float cm = red_m[0];
+      int ci = red_i[0];
+      for (int i = 1; i < 4; ++i)
+        if (red_m[i] > cm || (red_m[i] == cm && red_i[i] < ci)) { cm = red_m[i]; ci = red_i[i]; }
+      if (cm > gm) amax[r] = v0 + ci;                   // strictly greater: an earlier chunk keeps a tie
+    }
     for (int i = 0; i < 4; ++i) {
       const float nm = fmaxf(gm, red_m[i]);
       gl = gl * __expf(gm - nm) + red_l[i] * __expf(red_m[i] - nm);
@@ -78,6 +102,53 @@ __global__ __launch_bounds__(256) void ce_grad_kernel(const float* __restrict__ 
     // the f32 cotangent as two bf16 planes (hi + lo carries 16 mantissa bits): gemma.py:153-154 keeps the logits — and with them
     // their gradient — in f32, the GEMMs that consume it here are bf16 MFMA products with f32 accumulation
     if (dlo) dlo[(long long)r * ldd + v + e] = f2bf(dv - round_bf16(dv));
+  }
+}
+
+// Verbose token metrics (metrics.py:7-45) of one sample per block, Lm = Lt - 1 target positions.  Row j of the Ls computed
+// rows of sample b is position sel[b][j] (sel NULL: position j, Ls = Lm).  per_token_loss[b][p] = nll * lm at the computed
+// positions, 0 elsewhere.  counts[b][k] = (correct, total) for k = loss mask (lm != 0), critical, number, direction: totals
+// over all Lm positions of the mask, correct over the computed rows (a mask position outside them is counted as wrong; the
+// caller's row selection covers every mask position or poisons the loss).  A NULL class mask (bool [B][Lm]) counts zero.
+__global__ __launch_bounds__(256) void token_metrics_kernel(const int32_t* __restrict__ pred, const int32_t* __restrict__ target,
+                                                            const float* __restrict__ nll, const int32_t* __restrict__ sel, int Ls,
+                                                            const float* __restrict__ lm, const uint8_t* __restrict__ crit,
+                                                            const uint8_t* __restrict__ num, const uint8_t* __restrict__ dir, int Lm,
+                                                            float* __restrict__ per_token_loss, float* __restrict__ counts) {
+  __shared__ float red[8][4];
+  const int b = blockIdx.x;
+  const long long mo = (long long)b * Lm;
+  float c[4] = {0.f, 0.f, 0.f, 0.f}, t[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int p = threadIdx.x; p < Lm; p += 256) {
+    t[0] += lm[mo + p] != 0.f ? 1.f : 0.f;
+    if (crit) t[1] += crit[mo + p] ? 1.f : 0.f;
+    if (num) t[2] += num[mo + p] ? 1.f : 0.f;
+    if (dir) t[3] += dir[mo + p] ? 1.f : 0.f;
+    if (sel) per_token_loss[mo + p] = 0.f;
+  }
+  __syncthreads();                                      // the zero fill lands before the scatter below (same block)
+  for (int j = threadIdx.x; j < Ls; j += 256) {
+    const long long r = (long long)b * Ls + j;
+    const int p = sel ? sel[r] : j;
+    if (p < 0 || p >= Lm) continue;
+    const float w = lm[mo + p];
+    per_token_loss[mo + p] = nll[r] * w;
+    const float ok = pred[r] == target[r] ? 1.f : 0.f;
+    c[0] += w != 0.f ? ok : 0.f;
+    if (crit && crit[mo + p]) c[1] += ok;
+    if (num && num[mo + p]) c[2] += ok;
+    if (dir && dir[mo + p]) c[3] += ok;
+  }
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float sc = wave_sum(c[k]), st = wave_sum(t[k]);
+    if (lane == 0) { red[2 * k][w] = sc; red[2 * k + 1][w] = st; }
+  }
+  __syncthreads();
+  if (threadIdx.x < 8) {                                // counts are integers below 2^24: exact in f32 in any order
+    const float s = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+    counts[(long long)b * 8 + threadIdx.x] = s;
   }
 }
 
@@ -321,7 +392,24 @@ __global__ __launch_bounds__(256) void gemv_f32_kernel(const float* __restrict__
 extern "C" int lap_ce_chunk_update(const float* logits, int ldl, const int32_t* target, float* m, float* l, float* tl,
                                    int rows, int v0, int vc, void* stream) {
   if (rows <= 0 || vc <= 0) return LAP_ERR_ARG;
-  hipLaunchKernelGGL(ce_update_kernel, dim3(rows), dim3(256), 0, S_, logits, ldl, target, m, l, tl, v0, vc);
+  hipLaunchKernelGGL(ce_update_kernel<false>, dim3(rows), dim3(256), 0, S_, logits, ldl, target, m, l, tl, (int32_t*)nullptr, v0, vc);
+  LAP_CHECK_LAUNCH();
+  return LAP_OK;
+}
+extern "C" int lap_ce_chunk_update_argmax(const float* logits, int ldl, const int32_t* target, float* m, float* l, float* tl,
+                                          int32_t* amax, int rows, int v0, int vc, void* stream) {
+  if (rows <= 0 || vc <= 0 || ldl < vc || !amax) return LAP_ERR_ARG;
+  hipLaunchKernelGGL(ce_update_kernel<true>, dim3(rows), dim3(256), 0, S_, logits, ldl, target, m, l, tl, amax, v0, vc);
+  LAP_CHECK_LAUNCH();
+  return LAP_OK;
+}
+extern "C" int lap_token_metrics(const int32_t* pred, const int32_t* target, const float* nll, const int32_t* sel, int Ls,
+                                 const float* lm, const void* crit, const void* num, const void* dir, int B, int Lm,
+                                 float* per_token_loss, float* counts, void* stream) {
+  if (B <= 0 || Lm <= 0 || Ls <= 0 || Ls > Lm || (!sel && Ls != Lm) || !pred || !target || !nll || !lm || !per_token_loss || !counts)
+    return LAP_ERR_ARG;
+  hipLaunchKernelGGL(token_metrics_kernel, dim3(B), dim3(256), 0, S_, pred, target, nll, sel, Ls, lm, (const uint8_t*)crit,
+                     (const uint8_t*)num, (const uint8_t*)dir, Lm, per_token_loss, counts);
   LAP_CHECK_LAUNCH();
   return LAP_OK;
 }

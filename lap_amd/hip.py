@@ -178,6 +178,8 @@ SIGNATURES: dict[str, list] = {
     "lap_panel_gemm": [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _f, _i, _i, _i, _i, _i, _vp, _i, _vp],
     "lap_serve_final_euler": [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp],
     "lap_ce_chunk_update": [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "lap_ce_chunk_update_argmax": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "lap_token_metrics": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp],
     "lap_ce_chunk_grad": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "lap_ce_chunk_grad_hilo": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "lap_adamw_ema_hilo": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _f, _f, _f, _f, _f, _vp],
@@ -727,6 +729,51 @@ def attention_bwd(q, k, v, o, d_o, lse, q_len, k_len, B, NH, NKV, HD, qinfo=None
 def ce_chunk_update(logits, target, m, l, tl, v0):
     rows, vc = logits.shape
     call("lap_ce_chunk_update", _p(logits), logits.stride(0), _p(target), _p(m), _p(l), _p(tl), rows, v0, vc)
+
+
+def ce_chunk_update_argmax(logits, target, m, l, tl, amax, v0):
+    """ce_chunk_update plus the running row argmax into amax (int32 [rows], lowest index among ties): call once per vocab chunk
+    in ascending v0, starting from the same m / l / tl state as ce_chunk_update (m below every logit)."""
+    _req2(logits, torch.float32, "logits")
+    rows, vc = logits.shape
+    for t, dt, nm in ((target, torch.int32, "target"), (m, torch.float32, "m"), (l, torch.float32, "l"), (tl, torch.float32, "tl"),
+                      (amax, torch.int32, "amax")):
+        _req(t, dt, nm)
+        if not t.is_contiguous() or t.numel() != rows:
+            raise ValueError(f"{nm}: expected a contiguous tensor of {rows} elements, got shape {tuple(t.shape)}")
+    call("lap_ce_chunk_update_argmax", _p(logits), logits.stride(0), _p(target), _p(m), _p(l), _p(tl), _p(amax), rows, int(v0), vc)
+
+
+def token_metrics(pred, target, nll, lm, *, sel=None, critical=None, number=None, direction=None):
+    """Verbose token metrics of metrics.py:7-45 in one launch (include/lap_hip.h lap_token_metrics).  pred / target (int32) and
+    nll (f32): [B * Ls] over the computed rows; sel: int32 [B, Ls] positions of those rows (None: all Lm = Lt - 1 rows); lm: f32
+    [B, Lm] loss weights; critical / number / direction: bool [B, Lm] class masks or None.  Returns per_token_loss f32 [B, Lm]
+    and counts f32 [B, 4, 2] = (correct, total) for the loss mask, critical, number and direction tokens."""
+    _req(lm, torch.float32, "lm")
+    if lm.dim() != 2 or not lm.is_contiguous():
+        raise ValueError(f"lm: expected a contiguous [B, Lm] tensor, got shape {tuple(lm.shape)}")
+    B, Lm = lm.shape
+    if sel is not None:
+        _req2(sel, torch.int32, "sel")
+        if sel.shape[0] != B or not sel.is_contiguous() or not 0 < sel.shape[1] <= Lm:
+            raise ValueError(f"sel: expected a contiguous [{B}, <= {Lm}] tensor, got shape {tuple(sel.shape)}")
+        Ls = sel.shape[1]
+    else:
+        Ls = Lm
+    for t, dt, nm in ((pred, torch.int32, "pred"), (target, torch.int32, "target"), (nll, torch.float32, "nll")):
+        _req(t, dt, nm)
+        if not t.is_contiguous() or t.numel() != B * Ls:
+            raise ValueError(f"{nm}: expected a contiguous tensor of B * Ls = {B * Ls} elements, got shape {tuple(t.shape)}")
+    for t, nm in ((critical, "critical"), (number, "number"), (direction, "direction")):
+        if t is not None:
+            _req(t, torch.bool, nm)
+            if tuple(t.shape) != (B, Lm) or not t.is_contiguous():
+                raise ValueError(f"{nm}: expected a contiguous [{B}, {Lm}] bool tensor, got shape {tuple(t.shape)}")
+    ptl = torch.empty((B, Lm), dtype=torch.float32, device=lm.device)
+    counts = torch.empty((B, 4, 2), dtype=torch.float32, device=lm.device)
+    call("lap_token_metrics", _p(pred), _p(target), _p(nll), _p(sel), Ls, _p(lm), _p(critical), _p(number), _p(direction), B, Lm,
+         _p(ptl), _p(counts))
+    return ptl, counts
 
 
 def ce_chunk_grad(logits, target, m, l, w, dlogits, v0, dlogits_lo=None):

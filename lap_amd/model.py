@@ -1085,7 +1085,7 @@ class LAP:
 
     # ================================================================== training forward (+ backward)
     def _loss_impl(self, rng, observation: CoTObservation, actions: torch.Tensor, *, train: bool, noise=None, time=None,
-                   backward: bool, collect: dict | None = None):
+                   backward: bool, collect: dict | None = None, verbose: bool = False):
         cfg = self.config
         # lap.py:426-462,557-596: three branches — both losses (LAP-3B); enable_action_training=False: `llm([prefix])` and the
         # cross entropy only (VLA-0 style configs); enable_langact_training=False: both streams, flow matching only (pi0 style)
@@ -1132,6 +1132,7 @@ class LAP:
         sm = obs.sample_mask if obs.sample_mask is not None else torch.ones(B, dtype=torch.bool, device=dev)
         lang_loss = torch.zeros(B, dtype=torch.float32, device=dev)
         sel = pl = None
+        verbose_metrics = {}
         Dv, V = self.v.width, cfg.vocab_size
         if lang_on:
             # ---- language loss (lap.py:209-289): rows Pn-Lt .. Pn-2 predict tokens 1 .. Lt-1
@@ -1147,10 +1148,26 @@ class LAP:
             # rows of weight 0 — instead of all Lt - 1 (BASELINE shapes: 16 of 47).  A hint smaller than a sample's count would drop
             # tokens silently, so the device-side check turns the loss into NaN instead (no host sync).
             n_sel = observation.loss_rows_max if observation.loss_rows_max is not None else obs.loss_rows_max
+            # verbose (lap.py:240-277): the class masks lie inside the reasoning mask but not inside token_loss_mask (reasoning
+            # dropout), so the rows are chosen by loss mask | class masks and the hint is `metric_rows_max`, counted over that union
+            # (no hint: all Lt - 1 rows).  The loss still weighs the rows by `lm` alone.
+            row_mask = lm_bool
+            if verbose:
+                def prep(mk):       # prepare_mask, lap.py:241-247
+                    if mk is None:
+                        return None
+                    mk = mk[:, 1:].to(dev, torch.bool)
+                    return (mk & obs.sample_mask[:, None] if obs.sample_mask is not None else mk).contiguous()
+
+                cls_masks = [prep(obs.critical_token_mask), prep(obs.number_token_mask), prep(obs.direction_token_mask)]
+                for mk in cls_masks:
+                    if mk is not None:
+                        row_mask = row_mask | mk
+                n_sel = observation.metric_rows_max if observation.metric_rows_max is not None else obs.metric_rows_max
             sel = None
             if n_sel is not None and 0 < n_sel < Lt - 1 and os.environ.get("LAP_LM_ALL_ROWS", "0") != "1":
-                sel = torch.sort((~lm_bool).to(torch.uint8), dim=1, stable=True).indices[:, :n_sel]          # [B, n_sel] in 0 .. Lt-2
-                hint_too_small = (lm.sum(-1) > n_sel).any()
+                sel = torch.sort((~row_mask).to(torch.uint8), dim=1, stable=True).indices[:, :n_sel]          # [B, n_sel] in 0 .. Lt-2
+                hint_too_small = ((row_mask.sum(-1) if verbose else lm.sum(-1)) > n_sel).any()
                 Ls = n_sel
                 rowid = (torch.arange(B, device=dev) * Pn + (Pn - Lt))[:, None] + sel
                 rows = xf0.index_select(0, rowid.view(-1))
@@ -1174,18 +1191,26 @@ class LAP:
             chunks = [(v0, min(vc_max, V - v0)) for v0 in range(0, V, vc_max)]
             m = torch.full((R,), -3.0e38, dtype=torch.float32, device=dev)
             lsum = torch.zeros(R, dtype=torch.float32, device=dev); tl = torch.zeros(R, dtype=torch.float32, device=dev)
+            amax = torch.empty(R, dtype=torch.int32, device=dev) if verbose else None      # predictions from the same pass
             logit_chunks = []
             for v0, vc in chunks:
                 lg = torch.empty((R, vc), dtype=torch.float32, device=dev)
                 hip.gemm(pl, table16[v0:v0 + vc], lg, M=R, N=vc, K=Dv, lda=Dv, ldb=Dv, ldc=vc)
                 if table_lo is not None:
                     hip.gemm(pl, table_lo[v0:v0 + vc], lg, M=R, N=vc, K=Dv, lda=Dv, ldb=Dv, ldc=vc, accum=True)
-                hip.ce_chunk_update(lg, targets, m, lsum, tl, v0)
+                if verbose:
+                    hip.ce_chunk_update_argmax(lg, targets, m, lsum, tl, amax, v0)
+                else:
+                    hip.ce_chunk_update(lg, targets, m, lsum, tl, v0)
                 logit_chunks.append(lg if backward else None)
             nll = (m + torch.log(lsum) - tl).view(B, Ls)
             lang_loss = (nll * lm_s).sum(-1) / cnt
             if sel is not None:
                 lang_loss = torch.where(hint_too_small, torch.full_like(lang_loss, float("nan")), lang_loss)
+            if verbose:
+                verbose_metrics = self._token_metrics(amax, targets, nll, lm, sel, cls_masks, obs.tokenized_prompt[:, 1:])
+                if collect is not None:
+                    collect["predictions"], collect["sel"] = amax.view(B, Ls), sel
 
         # ---- action loss (lap.py:291-301)
         pre1 = v_t = None
@@ -1224,6 +1249,18 @@ class LAP:
                 extra_metrics[pfx + "loss"] = (lang_loss * fb(msk)).sum() / torch.clamp(fb(msk).sum(), min=1.0)
                 extra_metrics[pfx + "num_samples"] = fb(msk).sum()
                 extra_metrics[pfx + "sample_portion"] = fb(msk).sum() / torch.clamp(n_act_loc, min=1.0)
+            if cfg.enable_vqa_training and obs.vqa_dataset_id is not None:
+                # metrics.py:59-73 (lap.py:500-508): loss and sample count per VQA dataset, one [B, K] indicator for all K datasets
+                from lap_amd.config import VQA_DATASET_ID_MAP
+
+                names = list(VQA_DATASET_ID_MAP)
+                idv = torch.tensor([VQA_DATASET_ID_MAP[n] for n in names], dtype=torch.int64, device=dev)
+                ind = fb((obs.vqa_dataset_id.to(dev).to(torch.int64).view(B, 1) == idv.view(1, -1)) & vqa_m.view(B, 1))
+                ns = ind.sum(0)
+                ls = (lang_loss.view(1, B) @ ind).view(-1) / torch.clamp(ns, min=1.0)
+                for k, n in enumerate(names):
+                    extra_metrics[f"vqa_{n}_loss"] = ls[k]
+                    extra_metrics[f"vqa_{n}_num_samples"] = ns[k]
             extra_metrics["active_num_samples"] = n_act_loc
             extra_metrics["active_sample_portion"] = n_act_loc / max(B, 1)
         else:   # (also the langact-off branch: the VQA / prediction masks reach the action loss as they came, lap.py:557-566)
@@ -1249,7 +1286,9 @@ class LAP:
         loss = self.comm.all_reduce_sum((lang_term + action_term).view(1)).view(())
         metrics = {"lang_loss": lang_loss.mean(), "action_loss": (act_loss * fb(act_mask)).sum() / torch.clamp(fb(act_mask).sum(), min=1.0),
                    "langact_loss": (lang_loss * fb(sm)).sum() / torch.clamp(fb(sm).sum(), min=1.0) if not mixing else extra_metrics["langact_loss"],
-                   **{k: v for k, v in extra_metrics.items() if k != "langact_loss"}}
+                   **{k: v for k, v in extra_metrics.items() if k != "langact_loss"}, **verbose_metrics}
+        if verbose:     # lap.py:569-577: weighted language term plus the weighted, masked action term of each sample
+            metrics["per_sample_loss"] = wl * lang_loss + (cfg.action_loss_weight * act_loss * fb(act_mask) if act_on else 0.0)
         if collect is not None:
             collect.update(pl=pl, pre1=pre1, v_t=v_t.view(B, S, ad) if v_t is not None else None, u_t=u_t, per_sample_lang=lang_loss,
                            per_sample_action=act_loss)
@@ -1331,13 +1370,36 @@ class LAP:
 
     def compute_loss(self, rng, observation, actions, *, train: bool = False, stage_config=None, verbose_mode=None,
                      return_augmented_images: bool = False, noise=None, time=None, collect=None):
-        """lap.py:380-602.  rng: int seed or torch.Generator.  `noise` / `time` may be given explicitly (parity tests)."""
-        return self._loss_impl(rng, observation, actions, train=train, noise=noise, time=time, backward=False, collect=collect)
+        """lap.py:380-602.  rng: int seed or torch.Generator.  `noise` / `time` may be given explicitly (parity tests).
+        verbose_mode (None: the config's, lap.py:393-394) adds the token-accuracy metrics and `per_sample_loss` (_token_metrics)."""
+        verbose = bool(self.config.verbose_mode if verbose_mode is None else verbose_mode)
+        return self._loss_impl(rng, observation, actions, train=train, noise=noise, time=time, backward=False, collect=collect,
+                               verbose=verbose)
 
     def loss_and_grad(self, rng, observation, actions, *, train: bool = True, noise=None, time=None, collect=None):
         """Forward + backward; gradients land in self.ps.grad (engine layout; bf16 for the GEMM-weight units, f32 for the embedding table and
-        the small unit: ParamStore.grad_dtype).  The caller zeroes the accumulated (f32) units first."""
-        return self._loss_impl(rng, observation, actions, train=train, noise=noise, time=time, backward=True, collect=collect)
+        the small unit: ParamStore.grad_dtype).  The caller zeroes the accumulated (f32) units first.  Verbose metrics follow the
+        config's `verbose_mode` (the reference's train step runs with the class attribute, scripts/train.py:351)."""
+        return self._loss_impl(rng, observation, actions, train=train, noise=noise, time=time, backward=True, collect=collect,
+                               verbose=bool(self.config.verbose_mode))
+
+    def _token_metrics(self, amax, targets, nll, lm, sel, cls_masks, labels):
+        """compute_token_accuracy_metrics (metrics.py:7-45) from the LM head's argmax: per-token loss and per-sample (correct, total)
+        counts in one kernel (lap_token_metrics); the batch accuracies from the counts' totals, all-reduced in one collective so that
+        under FSDP they are the global values the reference computes."""
+        crit, num, dirn = cls_masks
+        ptl, counts = hip.token_metrics(amax, targets, nll.reshape(-1).contiguous(), lm.contiguous(),
+                                        sel=sel.to(torch.int32).contiguous() if sel is not None else None,
+                                        critical=crit, number=num, direction=dirn)
+        tot = self.comm.all_reduce_sum(counts.sum(0).reshape(8)).view(4, 2)
+        acc = tot[:, 0] / torch.clamp(tot[:, 1], min=1.0)
+        out = {"token_accuracy": acc[0], "per_token_loss": ptl, "labels": labels}
+        for k, (name, mk) in enumerate((("critical", crit), ("number", num), ("direction", dirn)), start=1):
+            if mk is not None:
+                out[f"{name}_token_accuracy"] = acc[k]
+                out[f"per_sample_{name}_correct"] = counts[:, k, 0]
+                out[f"per_sample_{name}_total"] = counts[:, k, 1]
+        return out
 
     # ================================================================== serving
     @torch.no_grad()

@@ -48,6 +48,9 @@ class CoTObservation:
     # rows per sample instead of all L-1 (lap.py:221-260 computes them all and multiplies by the mask); set by `from_dict` and the
     # loaders from the host-side masks.  A bound that is too small poisons the loss with NaN (checked on the device, no sync).
     loss_rows_max: int | None = None
+    # The same kind of hint for verbose mode (lap.py:240-277), a HOST int: the bound over loss mask | critical | number |
+    # direction masks (positions 1..L-1), the rows whose predictions the token-accuracy metrics read.  None: all L-1 rows.
+    metric_rows_max: int | None = None
 
     @classmethod
     def from_dict(cls, data: dict, device=None) -> "CoTObservation":
@@ -64,7 +67,7 @@ class CoTObservation:
         cot = data.get("extras", {}).get("cot", {}) if isinstance(data.get("extras"), dict) else {}
         g = lambda k: data.get(k, cot.get(k))
         b = lambda k: _t(g(k), torch.bool, device)
-        hint = None
+        hint = metric_hint = None
         la, pm, tl = g("tokenized_langact_mask"), data.get("tokenized_prompt_mask"), g("token_loss_mask")
         if la is not None and pm is not None and not (isinstance(la, torch.Tensor) and la.is_cuda):   # host-side masks: count here
             import numpy as np
@@ -73,8 +76,15 @@ class CoTObservation:
             if tl is not None:
                 m = m & np.asarray(tl, dtype=bool)
             hint = int(m[:, 1:].sum(-1).max()) if m.ndim == 2 and m.shape[1] > 1 else None
+            cls_masks = [g(k) for k in ("critical_token_mask", "number_token_mask", "direction_token_mask")]
+            if hint is not None and not any(isinstance(c, torch.Tensor) and c.is_cuda for c in cls_masks):
+                for c in cls_masks:     # an upper bound like `loss_rows_max` (the sample mask is not applied to either)
+                    if c is not None:
+                        m = m | np.asarray(c, dtype=bool)
+                metric_hint = int(m[:, 1:].sum(-1).max())
         return cls(
             loss_rows_max=hint,
+            metric_rows_max=metric_hint,
             images=images,
             image_masks={k: _t(v, torch.bool, device) for k, v in data.get("image_mask", {}).items()},
             state=_t(data.get("state"), torch.float32, device),

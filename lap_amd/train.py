@@ -203,7 +203,8 @@ class ValidationStepRunner:
     def __call__(self, rng, state: TrainState, batch, *, noise=None, time=None) -> dict:
         observation, actions = batch
         seed = (int(rng) * 1_000_003 + state.step) if not isinstance(rng, torch.Generator) else rng
-        val_loss, val_metrics = state.model.compute_loss(seed, observation, actions, train=False, noise=noise, time=time)
+        val_loss, val_metrics = state.model.compute_loss(seed, observation, actions, train=False, noise=noise, time=time,
+                                                         verbose_mode=self.config.model.verbose_mode)
         val_metrics = dict(val_metrics)
         val_metrics["val_loss"] = val_loss
         return val_metrics
@@ -224,7 +225,19 @@ def run_validation(runner: ValidationStepRunner, rng, state: TrainState, val_loa
     if not infos:
         return {}
     keys = [k for k, v in infos[0].items() if torch.is_tensor(v) and v.numel() == 1]
-    return {(k if k.startswith("val_") else "val_" + k): float(torch.stack([i[k].float().reshape(()) for i in infos]).mean()) for k in keys}
+    out = {(k if k.startswith("val_") else "val_" + k): float(torch.stack([i[k].float().reshape(()) for i in infos]).mean()) for k in keys}
+    mx = _max_per_sample_loss(infos)
+    if mx is not None:
+        out["val_max_per_sample_loss"] = mx
+    return out
+
+
+def _max_per_sample_loss(infos: list) -> float | None:
+    """metrics_logging.py:200-207: verbose infos carry `per_sample_loss` [B]; the maximum over the interval's infos is logged as
+    `max_per_sample_loss`.  Other non-scalar metrics (per_token_loss, labels, per-sample counts) are not logged."""
+    if not infos or "per_sample_loss" not in infos[0]:
+        return None
+    return float(torch.stack([i["per_sample_loss"].float().max() for i in infos]).max())
 
 
 # ====================================================================================== training entry point
@@ -351,6 +364,13 @@ def main(config: TrainConfig, *, data_loader=None, val_data_loader=None, device:
                 t = torch.tensor([mean[k] for k in keys], device=device)
                 dist.all_reduce(t)
                 mean = {k: float(v) / world for k, v in zip(keys, t)}
+            mx = _max_per_sample_loss(infos)
+            if mx is not None:
+                if world > 1:
+                    t = torch.tensor([mx], device=device)
+                    dist.all_reduce(t, op=dist.ReduceOp.MAX)
+                    mx = float(t)
+                mean["max_per_sample_loss"] = mx
             mean["param_norm"] = float(runner.param_norm(state))
             dt = _time.perf_counter() - t_last
             if rank == 0:
@@ -360,9 +380,14 @@ def main(config: TrainConfig, *, data_loader=None, val_data_loader=None, device:
         if val_runner is not None and (step + 1) % config.val_interval == 0:          # scripts/train.py:619-660
             vm = run_validation(val_runner, config.seed, state, val_data_loader)
             if world > 1 and vm:
+                mx = vm.pop("val_max_per_sample_loss", None)
                 t = torch.tensor(list(vm.values()), device=device)
                 dist.all_reduce(t)
                 vm = {k: float(v) / world for k, v in zip(vm, t)}
+                if mx is not None:
+                    t = torch.tensor([mx], device=device)
+                    dist.all_reduce(t, op=dist.ReduceOp.MAX)
+                    vm["val_max_per_sample_loss"] = float(t)
             if rank == 0 and vm:
                 log(f"step {step + 1} validation: " + ", ".join(f"{k}={v:.4f}" for k, v in vm.items()))
         if ((step + 1) % config.save_interval == 0 and step + 1 > start) or last:
