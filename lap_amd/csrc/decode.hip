@@ -1,0 +1,614 @@
+// Fused single-token decode of the VLM stream (expert 0) for LAP.sample_tokens (lap.py:678-766, the LAP_AR serving mode) at
+// the Gemma-2B widths: D 2048, 8 query heads / 1 kv head of 256, MLP 16384, B <= 8 rows.
+//
+// Every kernel of a decode step reads where it is from a small device state instead of host arguments, so one captured step
+// replays unchanged for every token (the reference's lax.while_loop body):
+//   state[0] = t       tokens written to out[:, .] so far; a decode step feeds token out[:, t-1] at position plen[b] + t-1,
+//                      appends its K / V at generated-cache row t-1 and attends to t generated keys
+//   state[1] = done    t >= max_steps or every sample has emitted EOS: every kernel returns at once, nothing more is written
+//   state[8 + b]       EOS seen by sample b
+//   state[16 + b]      plen[b] (the prefill length of sample b)
+//
+// Kernels (one launch each; weights [N][K] bf16, streamed once straight into VGPRs with nontemporal loads, f32 accumulation):
+//   embed       x[b] = bf16(table[out[b][t-1]] * sqrt(D))                                   (lap_embed_gather)
+//   qkv         h = RMSNorm(x)(1 + n_attn) -> bf16(h Wqkv^T) -> RoPE, q scale, head split;  (lap_rmsnorm_fwd, linear_fwd,
+//               K / V go to row t-1 of the generated cache, q to a small buffer              lap_rope_split_fwd)
+//   attention   8 query heads against [prefix keys gated by kinfo | t generated keys], keys split over waves of 16, then a
+//               combine pass                                                                 (lap_attention_serve)
+//   proj_res    y = bf16(a W^T + x)  (out projection, down projection)                     (linear_fwd + residual)
+//   gate_up     h = RMSNorm(x)(1 + n_ffw) -> act = bf16(bf16(gelu_tanh(bf16 g)) * bf16 u)  (linear_fwd, lap_geglu_fwd_ld)
+//   lm_head     h = RMSNorm(x)(1 + final_norm) -> logit = f32(hi h) + f32(lo h) per vocabulary row, never stored (except
+//               the debug `logits` output); per block (max, lowest index) partials          (_lm_logits)
+//   finish      one block: argmax over the partials with the lowest index among ties, out[:, t] = token, EOS mask, t += 1,
+//               done                                                                         (lap_argmax_rows_f32)
+// Rounding points are those of the eager step; only the summation order of the dot products differs.
+// Device state is written with plain per-lane stores.
+#include "common.hpp"
+#include "../../include/lap_hip.h"
+
+#define S_ ((hipStream_t)stream)
+
+namespace {
+
+constexpr int DEC_D = 2048, DEC_NH = 8, DEC_NKV = 1, DEC_HD = 256, DEC_H = 16384, DEC_MAXB = 8;
+constexpr int KC = 16;                     // keys per attention wave
+constexpr int LM_BLOCKS = 1024;            // LM-head grid (partials per sample)
+constexpr float NEG_BIG = -1.0e30f;
+constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
+constexpr int QWORD = (1 << 24) | 0xFFFFFF;    // the decode query's info word (class 1, index past every key)
+
+__device__ __forceinline__ bool mask_ok(int qi, int ki) {
+  return (((qi >> 24) & (ki >> 24)) != 0) && ((ki & 0xffffff) <= (qi & 0xffffff));
+}
+
+__device__ __forceinline__ void ld8f(const bf16* p, float (&v)[8]) {
+  const bf16x8 t = *reinterpret_cast<const bf16x8*>(p);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) v[e] = (float)t[e];
+}
+__device__ __forceinline__ bf16x8 ldw(const bf16* p) {      // the weight stream: read once by one wave
+  return __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(p));
+}
+__device__ __forceinline__ float dot8(const bf16x8 w, const float (&x)[8], float acc) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) acc = __builtin_fmaf((float)w[e], x[e], acc);
+  return acc;
+}
+__device__ __forceinline__ bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
+
+// RMSNorm prologue (lap_rmsnorm_fwd's plain form: h = bf16(x r (1 + gamma)), r = 1 / sqrt(mean(x^2) + eps)) of B rows of
+// width D into LDS.  256 threads, D % 8 == 0, D <= 2048.
+template <int B>
+__device__ __forceinline__ void norm_rows_to_lds(const bf16* x, const float* gamma, int D, float eps, bf16* sx, float* red) {
+  for (int b = 0; b < B; ++b) {
+    float ss = 0.f;
+    for (int c = threadIdx.x * 8; c < D; c += 2048) {
+      float v[8];
+      ld8f(x + (long long)b * D + c, v);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) ss += v[e] * v[e];
+    }
+    ss = block_sum<4>(ss, red);
+    const float r = 1.0f / sqrtf(ss / (float)D + eps);
+    for (int c = threadIdx.x * 8; c < D; c += 2048) {
+      float v[8];
+      ld8f(x + (long long)b * D + c, v);
+      bf16x8 o;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = f2bf(v[e] * r * (1.0f + gamma[c + e]));
+      *reinterpret_cast<bf16x8*>(sx + b * D + c) = o;
+    }
+  }
+  __syncthreads();
+}
+
+enum { EPI_QKV = 0, EPI_GEGLU = 1, EPI_RES = 2 };
+
+struct ProjP {
+  const int* state;
+  const bf16* x;          // block input [B][K] (normalised in the prologue when gamma != NULL)
+  const float* gamma;
+  const bf16* w;          // [N][K]
+  int K, units;
+  float eps;
+  bf16* out;              // GEGLU: act [B][H]; RES: y [B][N]
+  const bf16* res;        // RES: residual [B][N]
+  int N, H;               // RES: N; GEGLU: H
+  bf16* q; bf16* ck; bf16* cv;   // QKV: q [B][NH*HD], generated caches [B][cap][HD]
+  int cap, NH, HD;
+  float q_scale;
+};
+
+// One "unit" = the two output features an epilogue needs together: QKV the rotation pair (d, d + HD/2) of one head; GeGLU a
+// gate column and its up column; RES two neighbouring columns.  KW waves of a block split K for one unit (KW = 4) or each
+// wave owns a unit (KW = 1); blocks walk the units with a grid stride.
+template <int EPI>
+__device__ __forceinline__ void unit_features(const ProjP& p, int u, int& f0, int& f1) {
+  if (EPI == EPI_QKV) { const int half = p.HD / 2; f0 = (u / half) * p.HD + u % half; f1 = f0 + half; }
+  else if (EPI == EPI_GEGLU) { f0 = u; f1 = u + p.H; }
+  else { f0 = 2 * u; f1 = 2 * u + 1; }
+}
+
+template <int EPI, int B, bool NORM, int KW>
+__global__ __launch_bounds__(256) void dec_proj_kernel(ProjP p) {
+  __shared__ __attribute__((aligned(16))) bf16 sx[NORM ? B * DEC_D : 8];
+  __shared__ float red[4];
+  __shared__ float sacc[KW > 1 ? 4 * 2 * B : 1];
+  if (p.state[1]) return;
+  const int t = p.state[0];
+  if (EPI == EPI_QKV && (t < 1 || t > p.cap)) return;      // (cache row t - 1)
+  if (NORM) norm_rows_to_lds<B>(p.x, p.gamma, p.K, p.eps, sx, red);
+  const bf16* xs = NORM ? sx : p.x;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  constexpr int NU = 4 / KW;                      // units per block iteration
+  const int wu = w / KW, wk = w % KW;
+  const int Ks = p.K / KW;
+  for (int u0 = blockIdx.x * NU; u0 < p.units; u0 += gridDim.x * NU) {
+    const int u = u0 + wu;
+    const bool valid = u < p.units;
+    int f0 = 0, f1 = 0;
+    unit_features<EPI>(p, valid ? u : 0, f0, f1);
+    float a0[B], a1[B];
+#pragma unroll
+    for (int b = 0; b < B; ++b) { a0[b] = 0.f; a1[b] = 0.f; }
+    if (valid) {
+      const bf16* w0 = p.w + (long long)f0 * p.K;
+      const bf16* w1 = p.w + (long long)f1 * p.K;
+#pragma unroll 4
+      for (int k = wk * Ks + lane * 8; k < (wk + 1) * Ks; k += 512) {
+        const bf16x8 v0 = ldw(w0 + k), v1 = ldw(w1 + k);
+#pragma unroll
+        for (int b = 0; b < B; ++b) {
+          float xv[8];
+          ld8f(xs + (long long)b * p.K + k, xv);
+          a0[b] = dot8(v0, xv, a0[b]);
+          a1[b] = dot8(v1, xv, a1[b]);
+        }
+      }
+    }
+#pragma unroll
+    for (int b = 0; b < B; ++b) { a0[b] = wave_sum(a0[b]); a1[b] = wave_sum(a1[b]); }
+    if (KW > 1) {        // the K slices of the block's waves, summed in wave order
+      if (lane == 0) {
+#pragma unroll
+        for (int b = 0; b < B; ++b) { sacc[(w * 2 + 0) * B + b] = a0[b]; sacc[(w * 2 + 1) * B + b] = a1[b]; }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int b = 0; b < B; ++b) {
+        float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+        for (int i = 0; i < KW; ++i) { s0 += sacc[(i * 2 + 0) * B + b]; s1 += sacc[(i * 2 + 1) * B + b]; }
+        a0[b] = s0; a1[b] = s1;
+      }
+      __syncthreads();
+    }
+    if (!valid || wk != 0 || lane >= B) continue;
+    // epilogue: lane b writes sample b
+    float y0 = 0.f, y1 = 0.f;
+#pragma unroll
+    for (int b = 0; b < B; ++b) if (b == lane) { y0 = a0[b]; y1 = a1[b]; }
+    const int b = lane;
+    if (EPI == EPI_RES) {
+      const bf16* r = p.res + (long long)b * p.N + f0;
+      bf16x2 o;
+      o[0] = f2bf(y0 + (float)r[0]);
+      o[1] = f2bf(y1 + (float)r[1]);
+      *reinterpret_cast<bf16x2*>(p.out + (long long)b * p.N + f0) = o;
+    } else if (EPI == EPI_GEGLU) {
+      const float g = round_bf16(y0), up = round_bf16(y1);
+      p.out[(long long)b * p.H + f0] = f2bf(round_bf16(gelu_tanh_f(g)) * up);
+    } else {
+      const int half = p.HD / 2, head = u / half, i = u % half;
+      const int s = t - 1;
+      float x1 = round_bf16(y0), x2 = round_bf16(y1);
+      if (head <= p.NH) {          // q heads and the k head are rotated
+        float sn, cs, r1, r2;
+        rope_sincos((float)(p.state[16 + b] + s), i, p.HD, sn, cs);
+        rope_rotate(x1, x2, sn, cs, r1, r2);
+        x1 = round_bf16(r1); x2 = round_bf16(r2);
+        if (head < p.NH) { x1 *= p.q_scale; x2 *= p.q_scale; }
+      }
+      bf16* dst;
+      if (head < p.NH) dst = p.q + (long long)b * p.NH * p.HD + head * p.HD;
+      else dst = (head == p.NH ? p.ck : p.cv) + ((long long)b * p.cap + s) * p.HD;
+      dst[i] = f2bf(x1);
+      dst[i + half] = f2bf(x2);
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------- embed
+__global__ __launch_bounds__(256) void dec_embed_kernel(const int* state, const float* table, int row_lo, int row_hi,
+                                                        const int* out, int cap, bf16* x, int D, float scale) {
+  if (state[1]) return;
+  const int b = blockIdx.x, t = state[0];
+  if (t < 1 || t > cap) return;
+  const int tok = out[(long long)b * cap + t - 1];
+  for (int c = threadIdx.x * 8; c < D; c += 2048) {
+    bf16x8 o;
+    if (tok >= row_lo && tok < row_hi) {
+      const float* src = table + (long long)(tok - row_lo) * D + c;
+      const f32x4 a = *reinterpret_cast<const f32x4*>(src), e4 = *reinterpret_cast<const f32x4*>(src + 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { o[e] = f2bf(a[e] * scale); o[4 + e] = f2bf(e4[e] * scale); }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = f2bf(0.f);
+    }
+    *reinterpret_cast<bf16x8*>(x + (long long)b * D + c) = o;
+  }
+}
+
+// --------------------------------------------------------------------------------------------------------- attention
+// grid (ceil(chunks / 4), B), 4 waves; wave c owns keys [16 c, 16 c + 16) of [prefix (Pn) | generated (cap)].  Lane l holds
+// dims 4 l .. 4 l + 3 of the 8 query heads.  Per chunk: scores s (f32), m = max over the chunk's allowed keys, e = exp2(s
+// log2e - m log2e), p = bf16(e) (lap_attention_serve's rounding point), l = sum e, o = sum p v; written as o / l and
+// lse = (m + log2 l) ln 2, or lse = NEG_BIG for a chunk with no allowed key.
+struct AttnDecP {
+  const int* state;
+  const bf16* q;                       // [B][NH * HD]
+  const bf16* pk; const bf16* pv;      // prefix caches [B * Pn][HD]
+  const int* kinfo;                    // [B][Pn]
+  const bf16* gk; const bf16* gv;      // generated caches [B][cap][HD]
+  int Pn, cap, nchunk, npre;
+  float* lpart;                        // [B][nchunk][NH]
+  float* opart;                        // [B][nchunk][NH][HD]
+  bf16* o;                             // [B][NH * HD]
+};
+
+__global__ __launch_bounds__(256) void dec_attn_kernel(AttnDecP p) {
+  constexpr int NH = DEC_NH, HD = DEC_HD;
+  if (p.state[1]) return;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, b = blockIdx.y;
+  const int c = blockIdx.x * 4 + w;
+  if (c >= p.nchunk) return;
+  const int t = min(p.state[0], p.cap);
+  const bf16* kb; const bf16* vb;
+  int nkeys, j0;
+  if (c < p.npre) {
+    j0 = c * KC;
+    nkeys = min(KC, p.Pn - j0);
+    kb = p.pk + ((long long)b * p.Pn + j0) * HD;
+    vb = p.pv + ((long long)b * p.Pn + j0) * HD;
+  } else {
+    j0 = (c - p.npre) * KC;
+    nkeys = max(0, min(KC, t - j0));          // t generated keys (this step's included)
+    kb = p.gk + ((long long)b * p.cap + j0) * HD;
+    vb = p.gv + ((long long)b * p.cap + j0) * HD;
+  }
+  float qf[NH][4];
+#pragma unroll
+  for (int h = 0; h < NH; ++h) {
+    const bf16x4 v = *reinterpret_cast<const bf16x4*>(p.q + (long long)b * NH * HD + h * HD + lane * 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) qf[h][e] = (float)v[e];
+  }
+  // every K / V row and mask word of the chunk is loaded up front (one round trip), then the scores: lane j < KC keeps those of key j
+  bf16x4 kr[KC], vr[KC];
+#pragma unroll
+  for (int j = 0; j < KC; ++j) {
+    kr[j] = bf16x4{};
+    vr[j] = bf16x4{};
+    if (j < nkeys) {
+      kr[j] = *reinterpret_cast<const bf16x4*>(kb + (long long)j * HD + lane * 4);
+      vr[j] = *reinterpret_cast<const bf16x4*>(vb + (long long)j * HD + lane * 4);
+    }
+  }
+  const bool okl = lane < nkeys && (c < p.npre ? mask_ok(QWORD, p.kinfo[(long long)b * p.Pn + j0 + lane]) : true);
+  const unsigned long long okmask = __ballot(okl);
+  float sj[NH];
+  const bool okj = okl;
+#pragma unroll
+  for (int h = 0; h < NH; ++h) sj[h] = NEG_BIG;
+#pragma unroll
+  for (int j = 0; j < KC; ++j) {
+    if (!((okmask >> j) & 1ull)) continue;    // (uniform over the wave)
+    float kf[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) kf[e] = (float)kr[j][e];
+#pragma unroll
+    for (int h = 0; h < NH; ++h) {
+      float s = 0.f;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) s = __builtin_fmaf(qf[h][e], kf[e], s);
+      s = wave_sum(s);
+      if (lane == j) sj[h] = s;
+    }
+  }
+  float m[NH], l[NH], pj[NH];
+#pragma unroll
+  for (int h = 0; h < NH; ++h) {
+    m[h] = wave_max(okj ? sj[h] : NEG_BIG) * LOG2E;
+    const float e = okj ? __builtin_amdgcn_exp2f(sj[h] * LOG2E - m[h]) : 0.f;
+    l[h] = wave_sum(e);
+    pj[h] = round_bf16(e);
+  }
+  float acc[NH][4];
+#pragma unroll
+  for (int h = 0; h < NH; ++h)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[h][e] = 0.f;
+#pragma unroll
+  for (int j = 0; j < KC; ++j) {
+    if (!((okmask >> j) & 1ull)) continue;    // (p = 0 for a masked key)
+    float vf[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) vf[e] = (float)vr[j][e];
+#pragma unroll
+    for (int h = 0; h < NH; ++h) {
+      const float pp = __shfl(pj[h], j, 64);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[h][e] = __builtin_fmaf(pp, vf[e], acc[h][e]);
+    }
+  }
+  const long long pr = (long long)b * p.nchunk + c;
+#pragma unroll
+  for (int h = 0; h < NH; ++h) {
+    const float inv = l[h] > 0.f ? 1.0f / l[h] : 0.f;
+    f32x4 o4;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o4[e] = acc[h][e] * inv;
+    *reinterpret_cast<f32x4*>(p.opart + (pr * NH + h) * HD + lane * 4) = o4;
+    if (lane == 0) p.lpart[pr * NH + h] = l[h] > 0.f ? (m[h] + __builtin_amdgcn_logf(l[h])) * LN2 : NEG_BIG;
+  }
+}
+
+// grid (NH, B), 64 threads: thread = 4 dims of one head.  O = sum_c exp(lse_c - max) o_c / sum_c exp(lse_c - max) (the
+// combine of lap_attention_serve; chunks without an allowed key have weight 0).
+__global__ __launch_bounds__(64) void dec_attn_combine_kernel(AttnDecP p) {
+  constexpr int NH = DEC_NH, HD = DEC_HD;
+  if (p.state[1]) return;
+  const int h = blockIdx.x, b = blockIdx.y, d0 = threadIdx.x * 4;
+  const float* lp = p.lpart + (long long)b * p.nchunk * NH + h;
+  const float* op = p.opart + ((long long)b * p.nchunk * NH + h) * HD + d0;
+  float mx = NEG_BIG;
+#pragma unroll 8
+  for (int c = 0; c < p.nchunk; ++c) mx = fmaxf(mx, lp[(long long)c * NH]);
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  float den = 0.f;
+#pragma unroll 8
+  for (int c = 0; c < p.nchunk; ++c) {
+    const float li = lp[(long long)c * NH];
+    const float wgt = li > NEG_BIG * 0.5f ? __expf(li - mx) : 0.f;
+    den += wgt;
+    acc += *reinterpret_cast<const f32x4*>(op + (long long)c * NH * HD) * wgt;
+  }
+  const float sc = den > 0.f ? 1.0f / den : 0.f;
+  bf16x4 o;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) o[e] = f2bf(acc[e] * sc);
+  *reinterpret_cast<bf16x4*>(p.o + (long long)b * NH * HD + h * HD + d0) = o;
+}
+
+// ------------------------------------------------------------------------------------------------------------ LM head
+struct LmP {
+  const int* state;
+  const bf16* x; const float* gamma; float eps;
+  const bf16* hi; const bf16* lo;      // [V][D] planes (lo may be NULL)
+  int V, D;
+  float* logits;                       // debug: f32 [B][V] or NULL
+  float* pval; int* pidx;              // partials [gridDim.x][B]
+};
+
+template <int B>
+__global__ __launch_bounds__(256) void dec_lm_head_kernel(LmP p) {
+  __shared__ __attribute__((aligned(16))) bf16 sx[B * DEC_D];
+  __shared__ float red[4];
+  __shared__ float sv[4][B];
+  __shared__ int si[4][B];
+  if (p.state[1]) return;
+  norm_rows_to_lds<B>(p.x, p.gamma, p.D, p.eps, sx, red);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  float bv[B];
+  int bi[B];
+#pragma unroll
+  for (int b = 0; b < B; ++b) { bv[b] = -INFINITY; bi[b] = 0x7fffffff; }
+  const int units = (p.V + 1) / 2;
+  for (int u = blockIdx.x * 4 + w; u < units; u += gridDim.x * 4) {
+    const int f0 = 2 * u, f1 = min(2 * u + 1, p.V - 1);
+    float h0[B], h1[B], l0[B], l1[B];
+#pragma unroll
+    for (int b = 0; b < B; ++b) { h0[b] = 0.f; h1[b] = 0.f; l0[b] = 0.f; l1[b] = 0.f; }
+#pragma unroll (B > 4 ? 2 : 4)            // (4 at B = 7 spills)
+    for (int k = lane * 8; k < p.D; k += 512) {
+      const bf16x8 w0 = ldw(p.hi + (long long)f0 * p.D + k), w1 = ldw(p.hi + (long long)f1 * p.D + k);
+      bf16x8 z0 = w0, z1 = w1;
+      if (p.lo) { z0 = ldw(p.lo + (long long)f0 * p.D + k); z1 = ldw(p.lo + (long long)f1 * p.D + k); }
+#pragma unroll
+      for (int b = 0; b < B; ++b) {
+        float xv[8];
+        ld8f(sx + b * p.D + k, xv);
+        h0[b] = dot8(w0, xv, h0[b]);
+        h1[b] = dot8(w1, xv, h1[b]);
+        if (p.lo) { l0[b] = dot8(z0, xv, l0[b]); l1[b] = dot8(z1, xv, l1[b]); }
+      }
+    }
+#pragma unroll
+    for (int b = 0; b < B; ++b) {
+      float v0 = wave_sum(h0[b]), v1 = wave_sum(h1[b]);
+      if (p.lo) { v0 += wave_sum(l0[b]); v1 += wave_sum(l1[b]); }   // the eager path: C = hi.h, then C += lo.h
+      if (p.logits && lane == 0) {
+        p.logits[(long long)b * p.V + f0] = v0;
+        if (f1 != f0) p.logits[(long long)b * p.V + f1] = v1;
+      }
+      if (better(v0, f0, bv[b], bi[b])) { bv[b] = v0; bi[b] = f0; }
+      if (f1 != f0 && better(v1, f1, bv[b], bi[b])) { bv[b] = v1; bi[b] = f1; }
+    }
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int b = 0; b < B; ++b) { sv[w][b] = bv[b]; si[w][b] = bi[b]; }
+  }
+  __syncthreads();
+  if (threadIdx.x < B) {
+    const int b = threadIdx.x;
+    float v = sv[0][b];
+    int i = si[0][b];
+    for (int k = 1; k < 4; ++k)
+      if (better(sv[k][b], si[k][b], v, i)) { v = sv[k][b]; i = si[k][b]; }
+    p.pval[(long long)blockIdx.x * B + b] = v;
+    p.pidx[(long long)blockIdx.x * B + b] = i;
+  }
+}
+
+// one block: per sample, the best of the partials (lowest index among ties); then out[:, t], EOS mask, t + 1, done.
+__global__ __launch_bounds__(256) void dec_finish_kernel(int* state, const float* pval, const int* pidx, int nblk, int* out, int cap,
+                                                         int B, int eos_token) {
+  __shared__ float sv[4];
+  __shared__ int si[4];
+  __shared__ int tok[DEC_MAXB];
+  if (state[1]) return;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  for (int b = 0; b < B; ++b) {
+    float v = -INFINITY;
+    int i = 0x7fffffff;
+    for (int k = threadIdx.x; k < nblk; k += 256) {
+      const float pv = pval[(long long)k * B + b];
+      const int pi = pidx[(long long)k * B + b];
+      if (better(pv, pi, v, i)) { v = pv; i = pi; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(v, o, 64);
+      const int oi = __shfl_xor(i, o, 64);
+      if (better(ov, oi, v, i)) { v = ov; i = oi; }
+    }
+    if (lane == 0) { sv[w] = v; si[w] = i; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      for (int k = 1; k < 4; ++k)
+        if (better(sv[k], si[k], v, i)) { v = sv[k]; i = si[k]; }
+      tok[b] = i;
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const int t = state[0];
+    if (t >= cap) { state[1] = 1; return; }
+    int all = 1;
+    for (int b = 0; b < B; ++b) {
+      out[(long long)b * cap + t] = tok[b];
+      const int e = state[8 + b] | (tok[b] == eos_token ? 1 : 0);
+      state[8 + b] = e;
+      all &= e;
+    }
+    state[0] = t + 1;
+    state[1] = (t + 1 >= cap || all) ? 1 : 0;
+  }
+}
+
+__global__ __launch_bounds__(256) void dec_init_kernel(int* state, const int* plen, int* out, int B, int cap) {
+  for (long long i = threadIdx.x; i < (long long)B * cap; i += 256) out[i] = 0;
+  if (threadIdx.x < 32) {
+    const int i = threadIdx.x;
+    state[i] = (i >= 16 && i < 16 + B) ? plen[i - 16] : 0;
+  }
+}
+
+#define DISPATCH_B(B_, ...)                                                        \
+  switch (B_) {                                                                    \
+    case 1: { constexpr int BB = 1; __VA_ARGS__; } break;                          \
+    case 2: { constexpr int BB = 2; __VA_ARGS__; } break;                          \
+    case 3: { constexpr int BB = 3; __VA_ARGS__; } break;                          \
+    case 4: { constexpr int BB = 4; __VA_ARGS__; } break;                          \
+    case 5: { constexpr int BB = 5; __VA_ARGS__; } break;                          \
+    case 6: { constexpr int BB = 6; __VA_ARGS__; } break;                          \
+    case 7: { constexpr int BB = 7; __VA_ARGS__; } break;                          \
+    case 8: { constexpr int BB = 8; __VA_ARGS__; } break;                          \
+    default: return LAP_ERR_ARG;                                                   \
+  }
+
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+}  // namespace
+
+extern "C" int lap_decode_ok(int B, int D, int NH, int NKV, int HD, int H, int V) {
+  return B >= 1 && B <= DEC_MAXB && D == DEC_D && NH == DEC_NH && NKV == DEC_NKV && HD == DEC_HD && H == DEC_H && V >= 2 ? 1 : 0;
+}
+
+extern "C" int lap_decode_state_words(void) { return 32; }
+
+extern "C" int lap_decode_lm_blocks(void) { return LM_BLOCKS; }
+
+extern "C" int lap_decode_init(int* state, const int* plen, int* out, int B, int cap, void* stream) {
+  if (!state || !plen || !out || B < 1 || B > DEC_MAXB || cap < 1) return LAP_ERR_ARG;
+  hipLaunchKernelGGL(dec_init_kernel, dim3(1), dim3(256), 0, S_, state, plen, out, B, cap);
+  LAP_CHECK_LAUNCH();
+  return LAP_OK;
+}
+
+extern "C" int lap_decode_embed(const int* state, const float* table, int row_lo, int row_hi, const int* out, int cap, void* x,
+                                int B, int D, float scale, void* stream) {
+  if (!state || !table || !out || !x || B < 1 || B > DEC_MAXB || D != DEC_D || cap < 1 || !aligned16(table) || !aligned16(x)) return LAP_ERR_ARG;
+  hipLaunchKernelGGL(dec_embed_kernel, dim3(B), dim3(256), 0, S_, state, table, row_lo, row_hi, out, cap, (bf16*)x, D, scale);
+  LAP_CHECK_LAUNCH();
+  return LAP_OK;
+}
+
+extern "C" int lap_decode_qkv(const int* state, const void* x, const float* gamma, const void* wqkv, void* q, void* cache_k,
+                              void* cache_v, int B, int D, int NH, int HD, int cap, float q_scale, float eps, void* stream) {
+  if (!lap_decode_ok(B, D, NH, 1, HD, DEC_H, 2) || !state || !gamma || !q || !cache_k || !cache_v || cap < 1 ||
+      !aligned16(x) || !aligned16(wqkv)) return LAP_ERR_ARG;
+  ProjP p{};
+  p.state = state; p.x = (const bf16*)x; p.gamma = gamma; p.w = (const bf16*)wqkv; p.K = D; p.units = (NH + 2) * HD / 2;
+  p.eps = eps; p.q = (bf16*)q; p.ck = (bf16*)cache_k; p.cv = (bf16*)cache_v; p.cap = cap; p.NH = NH; p.HD = HD; p.q_scale = q_scale;
+  const dim3 grid((p.units + 3) / 4);
+  DISPATCH_B(B, hipLaunchKernelGGL((dec_proj_kernel<EPI_QKV, BB, true, 1>), grid, dim3(256), 0, S_, p));
+  LAP_CHECK_LAUNCH();
+  return LAP_OK;
+}
+
+extern "C" int lap_decode_gate_up(const int* state, const void* x, const float* gamma, const void* wgu, void* act, int B, int D,
+                                  int H, float eps, void* stream) {
+  if (!lap_decode_ok(B, D, DEC_NH, 1, DEC_HD, H, 2) || !state || !gamma || !act || !aligned16(x) || !aligned16(wgu)) return LAP_ERR_ARG;
+  ProjP p{};
+  p.state = state; p.x = (const bf16*)x; p.gamma = gamma; p.w = (const bf16*)wgu; p.K = D; p.units = H; p.H = H; p.eps = eps;
+  p.out = (bf16*)act;
+  const dim3 grid(min(H / 4, 1024));
+  DISPATCH_B(B, hipLaunchKernelGGL((dec_proj_kernel<EPI_GEGLU, BB, true, 1>), grid, dim3(256), 0, S_, p));
+  LAP_CHECK_LAUNCH();
+  return LAP_OK;
+}
+
+extern "C" int lap_decode_proj_residual(const int* state, const void* a, const void* w, const void* x, void* y, int B, int N, int K,
+                                        int kwaves, void* stream) {
+  if (!state || !a || !w || !x || !y || B < 1 || B > DEC_MAXB || N < 2 || (N & 1) || K < 512 || (K % 2048) ||
+      (kwaves != 1 && kwaves != 4) || !aligned16(a) || !aligned16(w) || ((uintptr_t)y & 3) || ((uintptr_t)x & 3)) return LAP_ERR_ARG;
+  ProjP p{};
+  p.state = state; p.x = (const bf16*)a; p.w = (const bf16*)w; p.K = K; p.units = N / 2; p.N = N; p.res = (const bf16*)x;
+  p.out = (bf16*)y;
+  const int nu = 4 / kwaves;
+  const dim3 grid(min((p.units + nu - 1) / nu, 2048));
+  if (kwaves == 4) { DISPATCH_B(B, hipLaunchKernelGGL((dec_proj_kernel<EPI_RES, BB, false, 4>), grid, dim3(256), 0, S_, p)); }
+  else { DISPATCH_B(B, hipLaunchKernelGGL((dec_proj_kernel<EPI_RES, BB, false, 1>), grid, dim3(256), 0, S_, p)); }
+  LAP_CHECK_LAUNCH();
+  return LAP_OK;
+}
+
+extern "C" int lap_decode_attn_scratch_floats(int B, int Pn, int cap) {
+  if (B < 1 || B > DEC_MAXB || Pn < 1 || cap < 1 || Pn > (1 << 20) || cap > (1 << 20)) return -1;
+  const int nchunk = (Pn + KC - 1) / KC + (cap + KC - 1) / KC;
+  return B * nchunk * DEC_NH * (DEC_HD + 1);
+}
+
+extern "C" int lap_decode_attention(const int* state, const void* q, const void* prefix_k, const void* prefix_v, const int* kinfo,
+                                    int Pn, const void* cache_k, const void* cache_v, int cap, void* o, float* scratch,
+                                    long long scratch_floats, int B, int NH, int NKV, int HD, void* stream) {
+  if (!state || !q || !prefix_k || !prefix_v || !kinfo || !cache_k || !cache_v || !o || !scratch || Pn < 1 || cap < 1 ||
+      !lap_decode_ok(B, DEC_D, NH, NKV, HD, DEC_H, 2) || scratch_floats < lap_decode_attn_scratch_floats(B, Pn, cap) ||
+      !aligned16(scratch)) return LAP_ERR_ARG;
+  AttnDecP p{};
+  p.state = state; p.q = (const bf16*)q; p.pk = (const bf16*)prefix_k; p.pv = (const bf16*)prefix_v; p.kinfo = kinfo;
+  p.gk = (const bf16*)cache_k; p.gv = (const bf16*)cache_v; p.Pn = Pn; p.cap = cap;
+  p.npre = (Pn + KC - 1) / KC;
+  p.nchunk = p.npre + (cap + KC - 1) / KC;
+  p.opart = scratch;
+  p.lpart = scratch + (long long)B * p.nchunk * DEC_NH * DEC_HD;
+  p.o = (bf16*)o;
+  hipLaunchKernelGGL(dec_attn_kernel, dim3((p.nchunk + 3) / 4, B), dim3(256), 0, S_, p);
+  LAP_CHECK_LAUNCH();
+  hipLaunchKernelGGL(dec_attn_combine_kernel, dim3(DEC_NH, B), dim3(64), 0, S_, p);
+  LAP_CHECK_LAUNCH();
+  return LAP_OK;
+}
+
+extern "C" int lap_decode_lm_head(const int* state, const void* x, const float* gamma, const void* hi, const void* lo, int B, int D,
+                                  int V, float eps, float* logits, float* pval, int* pidx, void* stream) {
+  if (!state || !gamma || !hi || !pval || !pidx || B < 1 || B > DEC_MAXB || D != DEC_D || V < 2 || !aligned16(x) || !aligned16(hi) ||
+      (lo && !aligned16(lo))) return LAP_ERR_ARG;
+  LmP p{};
+  p.state = state; p.x = (const bf16*)x; p.gamma = gamma; p.eps = eps; p.hi = (const bf16*)hi; p.lo = (const bf16*)lo;
+  p.V = V; p.D = D; p.logits = logits; p.pval = pval; p.pidx = pidx;
+  DISPATCH_B(B, hipLaunchKernelGGL(dec_lm_head_kernel<BB>, dim3(LM_BLOCKS), dim3(256), 0, S_, p));
+  LAP_CHECK_LAUNCH();
+  return LAP_OK;
+}
+
+extern "C" int lap_decode_finish(int* state, const float* pval, const int* pidx, int* out, int B, int cap, int eos_token,
+                                 void* stream) {
+  if (!state || !pval || !pidx || !out || B < 1 || B > DEC_MAXB || cap < 1) return LAP_ERR_ARG;
+  hipLaunchKernelGGL(dec_finish_kernel, dim3(1), dim3(256), 0, S_, state, pval, pidx, LM_BLOCKS, out, cap, B, eos_token);
+  LAP_CHECK_LAUNCH();
+  return LAP_OK;
+}

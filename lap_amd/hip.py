@@ -198,6 +198,18 @@ SIGNATURES: dict[str, list] = {
     "lap_lora_up_add": [_vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _f, _vp],
     "lap_lora_wgrad": [_vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _ll, _vp],
     "lap_lora_merge": [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _f, _vp],
+    "lap_decode_ok": [_i, _i, _i, _i, _i, _i, _i],
+    "lap_decode_state_words": [],
+    "lap_decode_lm_blocks": [],
+    "lap_decode_attn_scratch_floats": [_i, _i, _i],
+    "lap_decode_init": [_vp, _vp, _vp, _i, _i, _vp],
+    "lap_decode_embed": [_vp, _vp, _i, _i, _vp, _i, _vp, _i, _i, _f, _vp],
+    "lap_decode_qkv": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp],
+    "lap_decode_attention": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _ll, _i, _i, _i, _i, _vp],
+    "lap_decode_proj_residual": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "lap_decode_gate_up": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
+    "lap_decode_lm_head": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
+    "lap_decode_finish": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],
 }
 
 _fn = {}
@@ -1252,3 +1264,96 @@ def lora_merge(w, a, b, out, *, G=1, nsum=1, s=1.0):
     call("lap_lora_merge", _p(w), w.stride(0), _p(a), a.stride(0), _p(b), b.stride(0), nsum, _p(out), out.stride(0), w.shape[1], Ng, G,
          R, float(s))
     return out
+
+
+# ------------------------------------------------------------------ fused single-token decode (csrc/decode.hip)
+DECODE_KWAVES_DOWN = 4      # lap_decode_proj_residual's K split for the down projection (K 16384): tools/bench_ar.py --kwaves
+
+
+def decode_ok(B, D, NH, NKV, HD, H, V) -> bool:
+    """True when lap_decode_* serve these widths (Gemma-2B: D 2048, 8 / 1 heads of 256, MLP 16384; 1 <= B <= 8)."""
+    return bool(_fn["lap_decode_ok"](int(B), int(D), int(NH), int(NKV), int(HD), int(H), int(V)))
+
+
+def decode_state(B, device):
+    """Device state of one decode (include/lap_hip.h lap_decode_*): int32 [lap_decode_state_words()]."""
+    return torch.zeros(_fn["lap_decode_state_words"](), dtype=torch.int32, device=device)
+
+
+def decode_lm_partials(B, device):
+    n = _fn["lap_decode_lm_blocks"]() * B
+    return torch.empty(n, dtype=torch.float32, device=device), torch.empty(n, dtype=torch.int32, device=device)
+
+
+def decode_attn_scratch(B, Pn, cap, device):
+    n = _fn["lap_decode_attn_scratch_floats"](int(B), int(Pn), int(cap))
+    if n <= 0:
+        raise LapHipError("lap_decode_attn_scratch_floats: rejected arguments")
+    return torch.empty(n, dtype=torch.float32, device=device)
+
+
+def _dreq(t, dtype, name):
+    _req(t, dtype, name)
+    if not t.is_contiguous():
+        raise TypeError(f"{name} must be contiguous")
+
+
+def decode_init(state, plen, out):
+    _dreq(state, torch.int32, "state"); _dreq(plen, torch.int32, "plen"); _dreq(out, torch.int32, "out")
+    call("lap_decode_init", _p(state), _p(plen), _p(out), out.shape[0], out.shape[1])
+
+
+def decode_embed(state, table, row_lo, row_hi, out, x, scale):
+    _dreq(x, torch.bfloat16, "x"); _dreq(table, torch.float32, "table")
+    call("lap_decode_embed", _p(state), _p(table), int(row_lo), int(row_hi), _p(out), out.shape[1], _p(x), x.shape[0], x.shape[1],
+         float(scale))
+
+
+def decode_qkv(state, x, gamma, wqkv, q, cache_k, cache_v, NH, HD, q_scale, eps=1e-6):
+    """cache_k / cache_v: bf16 [B, cap, HD]."""
+    for t, n in ((x, "x"), (wqkv, "wqkv"), (q, "q"), (cache_k, "cache_k"), (cache_v, "cache_v")):
+        _dreq(t, torch.bfloat16, n)
+    _dreq(gamma, torch.float32, "gamma")
+    B, D = x.shape
+    call("lap_decode_qkv", _p(state), _p(x), _p(gamma), _p(wqkv), _p(q), _p(cache_k), _p(cache_v), B, D, NH, HD, cache_k.shape[1],
+         float(q_scale), float(eps))
+
+
+def decode_attention(state, q, prefix_k, prefix_v, kinfo, Pn, cache_k, cache_v, o, scratch, NH, NKV, HD):
+    for t, n in ((q, "q"), (prefix_k, "prefix_k"), (prefix_v, "prefix_v"), (cache_k, "cache_k"), (cache_v, "cache_v"), (o, "o")):
+        _dreq(t, torch.bfloat16, n)
+    _dreq(kinfo, torch.int32, "kinfo"); _dreq(scratch, torch.float32, "scratch")
+    B = q.shape[0]
+    call("lap_decode_attention", _p(state), _p(q), _p(prefix_k), _p(prefix_v), _p(kinfo), int(Pn), _p(cache_k), _p(cache_v),
+         cache_k.shape[1], _p(o), _p(scratch), scratch.numel(), B, NH, NKV, HD)
+
+
+def decode_proj_residual(state, a, w, x, y, kwaves=4):
+    for t, n in ((a, "a"), (w, "w"), (x, "x"), (y, "y")):
+        _dreq(t, torch.bfloat16, n)
+    B, K = a.shape
+    call("lap_decode_proj_residual", _p(state), _p(a), _p(w), _p(x), _p(y), B, w.shape[0], K, int(kwaves))
+
+
+def decode_gate_up(state, x, gamma, wgu, act, eps=1e-6):
+    for t, n in ((x, "x"), (wgu, "wgu"), (act, "act")):
+        _dreq(t, torch.bfloat16, n)
+    _dreq(gamma, torch.float32, "gamma")
+    B, D = x.shape
+    call("lap_decode_gate_up", _p(state), _p(x), _p(gamma), _p(wgu), _p(act), B, D, act.shape[1], float(eps))
+
+
+def decode_lm_head(state, x, gamma, hi, lo, pval, pidx, logits=None, eps=1e-6):
+    """logits (debug): f32 [B, V] written when given."""
+    _dreq(x, torch.bfloat16, "x"); _dreq(hi, torch.bfloat16, "hi"); _dreq(gamma, torch.float32, "gamma")
+    if lo is not None:
+        _dreq(lo, torch.bfloat16, "lo")
+    if logits is not None:
+        _dreq(logits, torch.float32, "logits")
+    B, D = x.shape
+    call("lap_decode_lm_head", _p(state), _p(x), _p(gamma), _p(hi), _p(lo), B, D, hi.shape[0], float(eps), _p(logits), _p(pval),
+         _p(pidx))
+
+
+def decode_finish(state, pval, pidx, out, eos_token):
+    call("lap_decode_finish", _p(state), _p(pval), _p(pidx), _p(out), out.shape[0], out.shape[1], int(eos_token))

@@ -1683,7 +1683,8 @@ class LAP:
             hip.gemm(pl, lo, lg, M=rows.shape[0], N=V, K=Dv, lda=Dv, ldb=Dv, ldc=V, accum=True)
         return lg
 
-    def sample_tokens(self, rng, observation, *, max_decoding_steps: int = 390, temperature: float = 0.0, collect=None):
+    def sample_tokens(self, rng, observation, *, max_decoding_steps: int = 390, temperature: float = 0.0, collect=None,
+                      decode: str = "eager"):
         """lap.py:678-766 (LAP_AR serving mode): VLM-only prefill, then single-token decode until every sample has emitted
         EOS or `max_decoding_steps` tokens; returns int32 [B, max_decoding_steps] (zeros after the stop).
 
@@ -1696,12 +1697,25 @@ class LAP:
         fully masked rows (uniform averages, "never consumed" elsewhere); the engine's attention writes zeros for such
         rows, so decode logits differ from the reference in that case only (prefill logits still agree; tested).
         temperature > 0 samples with the Gumbel-max trick from a torch generator seeded by `rng` (the JAX PRNG stream of
-        `jax.random.categorical` cannot be reproduced)."""
+        `jax.random.categorical` cannot be reproduced).
+
+        decode: "eager" (default) runs each decode step as generic launches; "fused" runs it on the single-token kernels of
+        csrc/decode.hip (Gemma-2B widths, 1 <= B <= 8, one replica; anything else raises ValueError) with a fixed-capacity
+        generated K/V cache and the step / EOS / stop state on the device, checked by the host once per 8 steps.  Greedy
+        only: temperature > 0 keeps the eager loop (its torch-generator Gumbel stream cannot run inside a captured graph).
+        The two paths differ in the summation order of their dot products only."""
+        if decode not in ("eager", "fused"):
+            raise ValueError(f"sample_tokens: decode must be 'eager' or 'fused', got {decode!r}")
+        if decode == "fused":
+            self._check_fused_decode(observation.tokenized_prompt.shape[0])
         with self._serving_weights():
+            if decode == "fused" and temperature <= 0.0:
+                return self._sample_tokens_fused(observation, max_decoding_steps=max_decoding_steps, collect=collect)
             return self._sample_tokens(rng, observation, max_decoding_steps=max_decoding_steps, temperature=temperature, collect=collect)
 
-    def _sample_tokens(self, rng, observation, *, max_decoding_steps: int = 390, temperature: float = 0.0, collect=None):
-        """`sample_tokens` with the weights as `_serving_weights` presents them (merged when the model has adapters)."""
+    def _ar_prefill(self, observation):
+        """The VLM-only prefill of sample_tokens (lap.py:693-716): (B, Pn, prefix K/V cache per layer, kinfo_prefix [B, Pn],
+        qinfo of the decode query, plen [B], the last valid residual row of every sample [B, D])."""
         cfg = self.config
         dev = self.device
         if self.comm.world_size != 1:
@@ -1724,7 +1738,13 @@ class LAP:
         else:
             xf0, _, _ = self._llm_fwd(x0, None, None, ppos, qinfo_p, kinfo_p, B, Pn, 0, False, cache_out=cache)
         last = (torch.arange(B, device=dev) * Pn + seqlen - 1)
-        logits = self._lm_logits(xf0.index_select(0, last).contiguous())        # decodes the first token (lap.py:716)
+        return B, Pn, cache, kinfo_prefix, qinfo_d, plen, xf0.index_select(0, last).contiguous()
+
+    def _sample_tokens(self, rng, observation, *, max_decoding_steps: int = 390, temperature: float = 0.0, collect=None):
+        """`sample_tokens` with the weights as `_serving_weights` presents them (merged when the model has adapters)."""
+        dev = self.device
+        B, Pn, cache, kinfo_prefix, qinfo_d, plen, x_last = self._ar_prefill(observation)
+        logits = self._lm_logits(x_last)                                        # decodes the first token (lap.py:716)
         out = torch.zeros((B, max_decoding_steps), dtype=torch.int32, device=dev)
         eos = torch.zeros((B,), dtype=torch.bool, device=dev)
         gen = [(None, None)] * self.v.depth
@@ -1745,3 +1765,105 @@ class LAP:
             pos = (plen + (step - 1)).to(torch.int32).view(B, 1).contiguous()
             logits = self._vlm_decode_step(token, pos, step - 1, cache, gen, qinfo_d, kinfo_prefix, B, Pn)
         return out
+
+    # ---- fused single-token decode (csrc/decode.hip)
+    DECODE_STEPS_PER_CHECK = 8      # fused steps between two host reads of the device stop flag (eager `decode="fused"`)
+
+    def decode_supported(self, B: int) -> bool:
+        """Whether `sample_tokens(decode="fused")` / `GraphedTokenDecoder` serve `B` rows of this model."""
+        v = self.v
+        return self.comm.world_size == 1 and hip.decode_ok(B, v.width, v.num_heads, v.num_kv_heads, v.head_dim, v.mlp_dim,
+                                                            self.config.vocab_size)
+
+    def _check_fused_decode(self, B: int):
+        if self.comm.world_size != 1:
+            raise ValueError("fused decode is a serving path: replicas only (world_size 1)")
+        if not self.decode_supported(B):
+            v = self.v
+            raise ValueError(f"fused decode serves the Gemma-2B widths at 1 <= B <= 8 (D 2048, 8 / 1 heads of 256, MLP 16384); got "
+                             f"B {B}, D {v.width}, heads {v.num_heads} / {v.num_kv_heads} of {v.head_dim}, MLP {v.mlp_dim}")
+
+    def _decode_ctx(self, B: int, Pn: int, cap: int):
+        return _DecodeCtx(self, B, Pn, cap)
+
+    def _fused_first_token(self, ctx, pre, logits=None):
+        """Reset the device state for the prefill `pre` (from `_ar_prefill`) and decode the first token from its last rows."""
+        B, Pn, cache, kinfo_prefix, _, plen, x_last = pre
+        ctx.bind(cache, kinfo_prefix)
+        ctx.plen.copy_(plen)
+        hip.decode_init(ctx.state, ctx.plen, ctx.out)
+        self._fused_token(ctx, x_last, logits)
+
+    def _fused_token(self, ctx, x, logits=None):
+        """final norm + LM head over the hi / lo planes + argmax -> out[:, t], EOS mask, t + 1 (lap.py:716-724)."""
+        hip.decode_lm_head(ctx.state, x, self.F("llm/final_norm"), self.W("llm/embed"), self.ps.w16lo("llm/embed"), ctx.pval, ctx.pidx,
+                           logits)
+        hip.decode_finish(ctx.state, ctx.pval, ctx.pidx, ctx.out, self.EOS_TOKEN)
+
+    def _fused_step(self, ctx, logits=None):
+        """One decode step (lap.py:734-752) + its token, positions and stop condition from the device state: replays unchanged."""
+        v = self.v
+        NH, HD, KV = v.num_heads, v.head_dim, v.num_kv_heads
+        rows, lo, hi = self.ps.embed_rows()
+        hip.decode_embed(ctx.state, rows, lo, hi, ctx.out, ctx.x, math.sqrt(v.width))
+        for l in range(v.depth):
+            p = f"llm/{l}/"
+            gk, gv = ctx.gen[l, 0], ctx.gen[l, 1]
+            hip.decode_qkv(ctx.state, ctx.x, self.F(p + "n_attn"), self.W(p + "wqkv0"), ctx.q, gk, gv, NH, HD, HD ** -0.5)
+            ck, cv = ctx.prefix[l]
+            hip.decode_attention(ctx.state, ctx.q, ck, cv, ctx.kinfo, ctx.Pn, gk, gv, ctx.o, ctx.attn_scratch, NH, KV, HD)
+            hip.decode_proj_residual(ctx.state, ctx.o, self.W(p + "wo0"), ctx.x, ctx.xa)
+            hip.decode_gate_up(ctx.state, ctx.xa, self.F(p + "n_ffw"), self.W(p + "wgu0"), ctx.act)
+            hip.decode_proj_residual(ctx.state, ctx.act, self.W(p + "wd0"), ctx.xa, ctx.x, kwaves=hip.DECODE_KWAVES_DOWN)
+        self._fused_token(ctx, ctx.x, logits)
+
+    def _sample_tokens_fused(self, observation, *, max_decoding_steps: int, collect=None):
+        pre = self._ar_prefill(observation)
+        B, Pn = pre[0], pre[1]
+        ctx = self._decode_ctx(B, Pn, max_decoding_steps)
+        lg = torch.empty((B, self.config.vocab_size), dtype=torch.float32, device=self.device) if collect is not None else None
+        self._fused_first_token(ctx, pre, lg)
+        if collect is not None:     # debug: one host read per token
+            collect["logit/0"] = lg.clone()
+            while not bool(ctx.state[1].item()):
+                self._fused_step(ctx, lg)
+                collect[f"logit/{int(ctx.state[0].item()) - 1}"] = lg.clone()
+            return ctx.out
+        n = self.DECODE_STEPS_PER_CHECK
+        for _ in range((max_decoding_steps - 1 + n - 1) // n):
+            if bool(ctx.state[1].item()):
+                break
+            for _ in range(n):
+                self._fused_step(ctx)
+        return ctx.out
+
+
+class _DecodeCtx:
+    """Buffers of one fused decode (B rows, `Pn` prefix keys, `cap` = max_decoding_steps): the device state, the token output,
+    the fixed-capacity generated K/V cache of every layer ([depth, 2, B, cap, head_dim] bf16, 7.2 MB per sample at 390 steps
+    for LAP-3B) and the step's activations.  The prefix K/V cache and kinfo come from the prefill (`bind`)."""
+
+    def __init__(self, model: LAP, B: int, Pn: int, cap: int):
+        v = model.v
+        dev = model.device
+        bf = torch.bfloat16
+        self.B, self.Pn, self.cap = B, Pn, cap
+        self.state = hip.decode_state(B, dev)
+        self.plen = torch.zeros((B,), dtype=torch.int32, device=dev)
+        self.out = torch.zeros((B, cap), dtype=torch.int32, device=dev)
+        self.gen = torch.zeros((v.depth, 2, B, cap, v.head_dim), dtype=bf, device=dev)
+        self.x = torch.zeros((B, v.width), dtype=bf, device=dev)
+        self.xa = torch.zeros((B, v.width), dtype=bf, device=dev)
+        self.q = torch.zeros((B, v.num_heads * v.head_dim), dtype=bf, device=dev)
+        self.o = torch.zeros((B, v.num_heads * v.head_dim), dtype=bf, device=dev)
+        self.act = torch.zeros((B, v.mlp_dim), dtype=bf, device=dev)
+        self.attn_scratch = hip.decode_attn_scratch(B, Pn, cap, dev)
+        self.pval, self.pidx = hip.decode_lm_partials(B, dev)
+        self.prefix = None
+        self.kinfo = None
+
+    def bind(self, cache, kinfo_prefix):
+        if kinfo_prefix.shape != (self.B, self.Pn):
+            raise ValueError(f"decode context for B {self.B}, {self.Pn} prefix keys; got kinfo {tuple(kinfo_prefix.shape)}")
+        self.prefix = list(cache)
+        self.kinfo = kinfo_prefix

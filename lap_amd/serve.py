@@ -71,6 +71,103 @@ class GraphedSampler:
         return self.out
 
 
+class GraphedTokenDecoder:
+    """hipGraph-replayed greedy `LAP.sample_tokens(decode="fused")` (the LAP_AR serving mode), the sibling of GraphedSampler.
+
+    Two graphs: (1) the VLM prefill + the first token (state reset included) and (2) `steps_per_replay` fused decode steps
+    (csrc/decode.hip), each of which reads its position, cache row and stop flag from the device state, so the same graph
+    replays for every token and turns into no-ops once every sample has emitted EOS or the budget is spent.  The host reads
+    the stop flag once per replay of (2).  Returns int32 [B, max_decoding_steps] like `sample_tokens` (a fresh tensor).
+    The EOS token is the model's `EOS_TOKEN` when the graphs are captured."""
+
+    def __init__(self, model: LAP, batch_size: int = 1, max_decoding_steps: int = 390, prompt_len: int | None = None,
+                 steps_per_replay: int = 8):
+        model._check_fused_decode(batch_size)
+        if max_decoding_steps < 1 or steps_per_replay < 1:
+            raise ValueError("max_decoding_steps and steps_per_replay must be >= 1")
+        self.model, self.B, self.max_steps, self.spr = model, batch_size, max_decoding_steps, steps_per_replay
+        cfg = model.config
+        dev = model.device
+        L = prompt_len or cfg.max_token_len
+        H = cfg.image_size
+        self.obs = CoTObservation(
+            images={k: torch.zeros(batch_size, H, H, 3, device=dev) for k in cfg.image_keys},
+            image_masks={k: torch.ones(batch_size, dtype=torch.bool, device=dev) for k in cfg.image_keys},
+            state=torch.zeros(batch_size, cfg.action_dim, device=dev),
+            tokenized_prompt=torch.zeros(batch_size, L, dtype=torch.int32, device=dev),
+            tokenized_prompt_mask=torch.ones(batch_size, L, dtype=torch.bool, device=dev),
+            tokenized_langact_mask=torch.zeros(batch_size, L, dtype=torch.bool, device=dev))
+        self.ctx = None
+        self.g_prefill = self.g_step = None
+
+    def _load(self, obs: CoTObservation):
+        for k in self.obs.images:
+            self.obs.images[k].copy_(obs.images[k])
+            m = obs.image_masks.get(k) if obs.image_masks else None
+            if m is not None:
+                self.obs.image_masks[k].copy_(m)
+            else:
+                self.obs.image_masks[k].fill_(True)
+        if obs.state is not None:
+            self.obs.state.copy_(obs.state)
+        self.obs.tokenized_prompt.copy_(obs.tokenized_prompt)
+        self.obs.tokenized_prompt_mask.copy_(obs.tokenized_prompt_mask)
+        if obs.tokenized_langact_mask is not None:      # (an all-false mask is the same prefix attention as none)
+            self.obs.tokenized_langact_mask.copy_(obs.tokenized_langact_mask)
+        else:
+            self.obs.tokenized_langact_mask.zero_()
+
+    def _prefill(self):
+        m = self.model
+        pre = m._ar_prefill(self.obs)
+        if self.ctx is None:
+            self.ctx = m._decode_ctx(self.B, pre[1], self.max_steps)
+        m._fused_first_token(self.ctx, pre)
+
+    def _steps(self):
+        for _ in range(self.spr):
+            self.model._fused_step(self.ctx)
+
+    def capture(self):
+        m = self.model
+        m.refresh_serve_caches()
+        with m._serving_weights():
+            side = torch.cuda.Stream(device=m.device)
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):   # warm-up outside capture (kernel attribute setup, allocator pools, serving caches)
+                self._prefill()
+                self._steps()
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            self.g_prefill = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.g_prefill):
+                self._prefill()
+            self.g_step = torch.cuda.CUDAGraph()      # (reads the prefix caches the first graph's pool holds)
+            with torch.cuda.graph(self.g_step):
+                self._steps()
+        torch.cuda.synchronize()
+        return self
+
+    def compatible(self, obs: CoTObservation) -> bool:
+        """The captured graphs are tied to the batch size, image resolution and prompt length."""
+        g = self.obs
+        return (all(k in obs.images and tuple(obs.images[k].shape) == tuple(g.images[k].shape) for k in g.images)
+                and tuple(obs.tokenized_prompt.shape) == tuple(g.tokenized_prompt.shape))
+
+    def __call__(self, obs: CoTObservation) -> torch.Tensor:
+        if self.g_step is None:
+            self.capture()
+        # merged LoRA weights / packed prefill images the graphs hold addresses of follow the parameters in place
+        self.model.refresh_serve_caches()
+        self._load(obs)
+        self.g_prefill.replay()
+        for _ in range((self.max_steps - 1 + self.spr - 1) // self.spr):
+            if bool(self.ctx.state[1].item()):      # one host read per replay
+                break
+            self.g_step.replay()
+        return self.ctx.out.clone()
+
+
 class Policy:
     """openpi's Policy surface: `infer(obs)` -> {"actions", ..., "policy_timing"}.
 
@@ -206,12 +303,17 @@ class ARPolicy:
     ids of `LAP.sample_tokens` (+ the model-level state) instead of an action chunk; decoding them to text / actions is
     the job of the output transforms, which take exactly this dict."""
 
-    def __init__(self, base: Policy, *, sample_kwargs: dict | None = None):
+    def __init__(self, base: Policy, *, sample_kwargs: dict | None = None, use_graph: bool = False):
         if not hasattr(base.model, "sample_tokens"):
             raise AssertionError("Model must have a sample_tokens method")
         self._base = base
         self._sample_kwargs = dict(sample_kwargs or {})
         self._calls = 0
+        # use_graph: greedy requests of the captured shapes replay a GraphedTokenDecoder (B = 1); anything else, and models whose
+        # widths the fused decode kernels do not serve, go through sample_tokens
+        self._decoder = None
+        if use_graph and base.model.decode_supported(1):
+            self._decoder = GraphedTokenDecoder(base.model, 1, self._sample_kwargs.get("max_decoding_steps", 390))
 
     def __getattr__(self, name):
         return getattr(self._base, name)
@@ -227,7 +329,11 @@ class ARPolicy:
             inputs = obs
         o, batched = base._to_observation(inputs)
         self._calls += 1
-        tokens = base.model.sample_tokens(self._calls, o, **self._sample_kwargs)
+        if (self._decoder is not None and self._sample_kwargs.get("temperature", 0.0) <= 0.0
+                and self._sample_kwargs.get("decode", "eager") in ("eager", "fused") and self._decoder.compatible(o)):
+            tokens = self._decoder(o)
+        else:
+            tokens = base.model.sample_tokens(self._calls, o, **self._sample_kwargs)
         out = {"state": batched.get("state"), "tokens": tokens.cpu().numpy(), "raw_state": raw_state}
         model_ms = (time.perf_counter() - t0) * 1e3
         if base._has_transforms:
@@ -242,14 +348,16 @@ class ARPolicy:
         return self.infer_reasoning(obs)
 
 
-def create_trained_policy_ar(*args, sample_kwargs: dict | None = None, language_action_format="verbose_eef_with_rotation", **kwargs) -> ARPolicy:
+def create_trained_policy_ar(*args, sample_kwargs: dict | None = None, language_action_format="verbose_eef_with_rotation",
+                             ar_graph: bool = False, **kwargs) -> ARPolicy:
     """policy_config_adapter.py:157-160 with the AR output stack [DetokenizeReasoning, CoTOutputs(language_action_format)]:
     generated ids -> text -> [dx, dy, dz, droll, dpitch, dyaw, gripper] (the language action describes the whole chunk as
     one delta, output_transforms.py:75-104; `Unnormalize` has no `actions` statistics to apply to such deltas and is left out
-    as in the reference's standard stack it would act on the normalised `state` only)."""
+    as in the reference's standard stack it would act on the normalised `state` only).
+    ar_graph: serve greedy requests through a GraphedTokenDecoder (ARPolicy(use_graph=True)); off by default."""
     from lap_amd import policy_io as pio
 
     base = create_trained_policy(*args, use_graph=False, **kwargs)
     tok = next(t.tokenizer for t in base._transforms if isinstance(t, pio.TokenizePromptAndReasoning))
     base._output_transform = pio.compose([pio.DetokenizeReasoning(tok), pio.CoTOutputs(language_action_format=language_action_format)])
-    return ARPolicy(base, sample_kwargs=sample_kwargs)
+    return ARPolicy(base, sample_kwargs=sample_kwargs, use_graph=ar_graph)

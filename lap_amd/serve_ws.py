@@ -194,11 +194,16 @@ def main(argv=None):
     ap.add_argument("--type", choices=["flow", "ar"], default="flow")
     ap.add_argument("--default-prompt", default=None)
     ap.add_argument("--port", type=int, default=8000)
+    ap.add_argument("--ar-graph", action="store_true",
+                    help="--type ar: decode greedy requests with the hipGraph-replayed fused decoder (GraphedTokenDecoder)")
     a = ap.parse_args(argv)
     cfg = get_config(a.config)
     cfg = dataclasses.replace(cfg, model=dataclasses.replace(cfg.model, stop_action_to_vlm_grad=False))   # serve_policy.py:77-79
+    if a.ar_graph and a.type != "ar":
+        ap.error("--ar-graph needs --type ar")
+    extra = {"ar_graph": True} if a.ar_graph else {}
     make = create_trained_policy_ar if a.type == "ar" else create_trained_policy
-    policy = make(cfg, a.checkpoint_dir, tokenizer_model_path=a.tokenizer_model, default_prompt=a.default_prompt)
+    policy = make(cfg, a.checkpoint_dir, tokenizer_model_path=a.tokenizer_model, default_prompt=a.default_prompt, **extra)
     logging.basicConfig(level=logging.INFO)
     WebsocketPolicyServer(policy, "0.0.0.0", a.port, metadata=policy.metadata).serve_forever()
 

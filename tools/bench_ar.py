@@ -1,0 +1,83 @@
+"""Batch-1 LAP_AR token decoding of LAP-3B on one MI355X: eager, fused (csrc/decode.hip issued from Python) and graph-replayed
+(GraphedTokenDecoder) ms per token, prefill ms, graphed-vs-eager token agreement, algorithmic bytes per token and the achieved
+rate against the 6.29 TB/s measured copy rate.  Random weights, the reference prompt shape, greedy, EOS disabled so that every
+run decodes N tokens.  One JSON line.
+
+    python tools/bench_ar.py [--tokens 64] [--config lap_bench] [--kwaves 4]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+from lap_amd import hip
+from lap_amd.config import get_config
+from lap_amd.model import LAP
+from lap_amd.serve import GraphedTokenDecoder
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--config", default="lap_bench")
+ap.add_argument("--tokens", type=int, default=64)
+ap.add_argument("--kwaves", type=int, default=hip.DECODE_KWAVES_DOWN, help="K split of the down projection (1 or 4)")
+ap.add_argument("--reps", type=int, default=3)
+ap.add_argument("--profile-graphed", action="store_true", help="capture, replay one graphed decode and exit (for rocprofv3)")
+a = ap.parse_args()
+hip.DECODE_KWAVES_DOWN = a.kwaves
+
+cfg = get_config(a.config).model
+dev = "cuda"
+model = LAP(cfg, seed=0, device=dev, with_grads=False)
+model.EOS_TOKEN = -1
+N = a.tokens
+dec = GraphedTokenDecoder(model, 1, N)
+gen = torch.Generator(device="cpu").manual_seed(0)
+for k in dec.obs.images:
+    dec.obs.images[k].copy_(torch.rand(dec.obs.images[k].shape, generator=gen) * 2 - 1)
+dec.obs.tokenized_prompt.copy_(torch.randint(0, cfg.vocab_size, dec.obs.tokenized_prompt.shape, generator=gen, dtype=torch.int32))
+o = dec.obs
+
+
+def timeit(fn, n):
+    fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(n):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / n * 1e3
+
+
+if a.profile_graphed:
+    dec(o)
+    torch.cuda.synchronize()
+    sys.exit(0)
+t_pre = timeit(lambda: model.sample_tokens(0, o, max_decoding_steps=1), a.reps)            # prefill + first token
+t_eager = timeit(lambda: model.sample_tokens(0, o, max_decoding_steps=N), a.reps)
+t_fused = timeit(lambda: model.sample_tokens(0, o, max_decoding_steps=N, decode="fused"), a.reps)
+eager = model.sample_tokens(0, o, max_decoding_steps=N)
+dec.capture()
+t_gpre = timeit(lambda: (dec.g_prefill.replay()), a.reps)
+t_graph = timeit(lambda: dec(o), a.reps)
+got = dec(o)
+agree = int((got == eager).cumprod(1).sum())          # leading tokens that agree
+
+v = model.v
+layer = sum(model.W(f"llm/0/{n}").numel() for n in ("wqkv0", "wo0", "wgu0", "wd0")) * 2
+head = model.W("llm/embed").numel() * 2 * (2 if model.ps.w16lo("llm/embed") is not None else 1)
+bytes_tok = v.depth * layer + head
+per = lambda t, t0: (t - t0) / (N - 1)
+g_ms = per(t_graph, t_gpre)
+print(json.dumps({
+    "metric": "batch-1 LAP_AR decode LAP-3B bf16 (ms per token after the prefill, greedy, EOS disabled)",
+    "tokens": N, "prompt_len": cfg.max_token_len,
+    "eager_ms_per_token": round(per(t_eager, t_pre), 3), "fused_ms_per_token": round(per(t_fused, t_pre), 3),
+    "graphed_ms_per_token": round(g_ms, 3), "prefill_ms": round(t_pre, 3), "graphed_prefill_ms": round(t_gpre, 3),
+    "graphed_total_ms": round(t_graph, 3), "eager_total_ms": round(t_eager, 3),
+    "graphed_vs_eager_leading_tokens_equal": agree, "graphed_equals_eager": bool(torch.equal(got, eager)),
+    "algorithmic_bytes_per_token": bytes_tok, "floor_ms_per_token_at_6.29TBps": round(bytes_tok / 6.29e12 * 1e3, 3),
+    "achieved_GBps_graphed": round(bytes_tok / (g_ms * 1e-3) / 1e9, 1),
+    "share_of_6.29TBps": round(bytes_tok / (g_ms * 1e-3) / 6.29e12, 3), "down_proj_kwaves": a.kwaves}))
