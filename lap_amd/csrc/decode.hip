@@ -19,11 +19,15 @@
 //   gate_up     h = RMSNorm(x)(1 + n_ffw) -> act = bf16(bf16(gelu_tanh(bf16 g)) * bf16 u)  (linear_fwd, lap_geglu_fwd_ld)
 //   lm_head     h = RMSNorm(x)(1 + final_norm) -> logit = f32(hi h) + f32(lo h) per vocabulary row, never stored (except
 //               the debug `logits` output); per block (max, lowest index) partials          (_lm_logits)
+//   lm_head_sample   lm_head whose partials are over score = logit * inv_t + Gumbel noise of (seed, t, b, vocabulary row)
+//               (sampling.hpp) when the sampling words {seed low, seed high, bits of inv_t, 0} hold inv_t != 0, and lm_head's
+//               partials bit for bit when inv_t == 0                                        (lap_gumbel_argmax_rows_f32)
 //   finish      one block: argmax over the partials with the lowest index among ties, out[:, t] = token, EOS mask, t += 1,
 //               done                                                                         (lap_argmax_rows_f32)
 // Rounding points are those of the eager step; only the summation order of the dot products differs.
 // Device state is written with plain per-lane stores.
 #include "common.hpp"
+#include "sampling.hpp"
 #include "../../include/lap_hip.h"
 
 #define S_ ((hipStream_t)stream)
@@ -369,9 +373,14 @@ struct LmP {
   int V, D;
   float* logits;                       // debug: f32 [B][V] or NULL
   float* pval; int* pidx;              // partials [gridDim.x][B]
+  const int* samp;                     // SAMPLE: {seed low, seed high, bits of inv_t (0 = greedy), reserved}
 };
 
-template <int B>
+// SAMPLE: the sampler is the epilogue of a unit.  After the wave_sums the two logits of all B rows are wave-uniform; lane b
+// keeps row b's pair, runs row b's Philox block and its four logarithms (B <= 8 lanes carry data, the instruction count is that
+// of one row) and folds the two scores into ITS running best, so the B-fold compare chain of the greedy form becomes one.
+// The <B, false> instances are the greedy kernel unchanged.
+template <int B, bool SAMPLE>
 __global__ __launch_bounds__(256) void dec_lm_head_kernel(LmP p) {
   __shared__ __attribute__((aligned(16))) bf16 sx[B * DEC_D];
   __shared__ float red[4];
@@ -384,6 +393,14 @@ __global__ __launch_bounds__(256) void dec_lm_head_kernel(LmP p) {
   int bi[B];
 #pragma unroll
   for (int b = 0; b < B; ++b) { bv[b] = -INFINITY; bi[b] = 0x7fffffff; }
+  float lbv = -INFINITY;               // SAMPLE: lane b's running best of row b
+  int lbi = 0x7fffffff;
+  uint32_t seed_lo = 0, seed_hi = 0, step = 0;
+  float inv_t = 0.f;
+  if (SAMPLE) {
+    seed_lo = (uint32_t)p.samp[0]; seed_hi = (uint32_t)p.samp[1]; inv_t = __int_as_float(p.samp[2]);
+    step = (uint32_t)p.state[0];
+  }
   const int units = (p.V + 1) / 2;
   for (int u = blockIdx.x * 4 + w; u < units; u += gridDim.x * 4) {
     const int f0 = 2 * u, f1 = min(2 * u + 1, p.V - 1);
@@ -404,6 +421,7 @@ __global__ __launch_bounds__(256) void dec_lm_head_kernel(LmP p) {
         if (p.lo) { l0[b] = dot8(z0, xv, l0[b]); l1[b] = dot8(z1, xv, l1[b]); }
       }
     }
+    float y0 = 0.f, y1 = 0.f;
 #pragma unroll
     for (int b = 0; b < B; ++b) {
       float v0 = wave_sum(h0[b]), v1 = wave_sum(h1[b]);
@@ -412,11 +430,22 @@ __global__ __launch_bounds__(256) void dec_lm_head_kernel(LmP p) {
         p.logits[(long long)b * p.V + f0] = v0;
         if (f1 != f0) p.logits[(long long)b * p.V + f1] = v1;
       }
-      if (better(v0, f0, bv[b], bi[b])) { bv[b] = v0; bi[b] = f0; }
-      if (f1 != f0 && better(v1, f1, bv[b], bi[b])) { bv[b] = v1; bi[b] = f1; }
+      if (SAMPLE) {
+        if (b == lane) { y0 = v0; y1 = v1; }
+      } else {
+        if (better(v0, f0, bv[b], bi[b])) { bv[b] = v0; bi[b] = f0; }
+        if (f1 != f0 && better(v1, f1, bv[b], bi[b])) { bv[b] = v1; bi[b] = f1; }
+      }
+    }
+    if (SAMPLE) {
+      if (inv_t != 0.f) lap_sampling::gumbel_scores(y0, y1, inv_t, seed_lo, seed_hi, step, (uint32_t)lane, (uint32_t)u, y0, y1);
+      if (better(y0, f0, lbv, lbi)) { lbv = y0; lbi = f0; }
+      if (f1 != f0 && better(y1, f1, lbv, lbi)) { lbv = y1; lbi = f1; }
     }
   }
-  if (lane == 0) {
+  if (SAMPLE) {
+    if (lane < B) { sv[w][lane] = lbv; si[w][lane] = lbi; }
+  } else if (lane == 0) {
 #pragma unroll
     for (int b = 0; b < B; ++b) { sv[w][b] = bv[b]; si[w][b] = bi[b]; }
   }
@@ -600,7 +629,22 @@ extern "C" int lap_decode_lm_head(const int* state, const void* x, const float* 
   LmP p{};
   p.state = state; p.x = (const bf16*)x; p.gamma = gamma; p.eps = eps; p.hi = (const bf16*)hi; p.lo = (const bf16*)lo;
   p.V = V; p.D = D; p.logits = logits; p.pval = pval; p.pidx = pidx;
-  DISPATCH_B(B, hipLaunchKernelGGL(dec_lm_head_kernel<BB>, dim3(LM_BLOCKS), dim3(256), 0, S_, p));
+  DISPATCH_B(B, hipLaunchKernelGGL((dec_lm_head_kernel<BB, false>), dim3(LM_BLOCKS), dim3(256), 0, S_, p));
+  LAP_CHECK_LAUNCH();
+  return LAP_OK;
+}
+
+extern "C" int lap_decode_sampling_words(void) { return 4; }
+
+extern "C" int lap_decode_lm_head_sample(const int* state, const int* sampling, const void* x, const float* gamma, const void* hi,
+                                         const void* lo, int B, int D, int V, float eps, float* logits, float* pval, int* pidx,
+                                         void* stream) {
+  if (!state || !sampling || !gamma || !hi || !pval || !pidx || B < 1 || B > DEC_MAXB || D != DEC_D || V < 2 || !aligned16(x) ||
+      !aligned16(hi) || (lo && !aligned16(lo))) return LAP_ERR_ARG;
+  LmP p{};
+  p.state = state; p.x = (const bf16*)x; p.gamma = gamma; p.eps = eps; p.hi = (const bf16*)hi; p.lo = (const bf16*)lo;
+  p.V = V; p.D = D; p.logits = logits; p.pval = pval; p.pidx = pidx; p.samp = sampling;
+  DISPATCH_B(B, hipLaunchKernelGGL((dec_lm_head_kernel<BB, true>), dim3(LM_BLOCKS), dim3(256), 0, S_, p));
   LAP_CHECK_LAUNCH();
   return LAP_OK;
 }

@@ -4,6 +4,7 @@
 // adamw)), and the global-norm reduction (optax.global_norm).  All HBM-bound.
 #include <cstdlib>
 #include "common.hpp"
+#include "sampling.hpp"
 #include "../../include/lap_hip.h"
 
 namespace {
@@ -175,6 +176,43 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restric
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int k = 1; k < 4; ++k)
+      if (sv[k] > best || (sv[k] == best && si[k] < bi)) { best = sv[k]; bi = si[k]; }
+    out[blockIdx.x] = bi;
+  }
+}
+
+// Sampled token choice (lap.py:719-722 jax.random.categorical(logits / temperature) as Gumbel-max): index of the row maximum of
+// logit * inv_t + noise(seed, step, row, column) (sampling.hpp), lowest index among ties; the plain argmax when inv_t == 0.
+// One block of 1024 threads per row (the row costs ~150 integer and logarithm instructions per pair of columns, not bytes); a
+// thread takes pairs of columns, one Philox block each.  One pass, nothing stored but out[row].
+__global__ __launch_bounds__(1024) void gumbel_argmax_rows_kernel(const float* __restrict__ x, int ld, int n, float inv_t,
+                                                                   uint32_t seed_lo, uint32_t seed_hi, uint32_t step,
+                                                                   int* __restrict__ out) {
+  __shared__ float sv[16];
+  __shared__ int si[16];
+  const float* row = x + (long long)blockIdx.x * ld;
+  float best = -INFINITY;
+  int bi = 0x7fffffff;
+  const int units = (n + 1) / 2;
+  for (int u = threadIdx.x; u < units; u += 1024) {
+    const int c0 = 2 * u, c1 = min(2 * u + 1, n - 1);
+    float s0 = row[c0], s1 = row[c1];
+    if (inv_t != 0.f) lap_sampling::gumbel_scores(s0, s1, inv_t, seed_lo, seed_hi, step, blockIdx.x, (uint32_t)u, s0, s1);
+    if (s0 > best || (s0 == best && c0 < bi)) { best = s0; bi = c0; }
+    if (c1 != c0 && (s1 > best || (s1 == best && c1 < bi))) { best = s1; bi = c1; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+  }
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (lane == 0) { sv[w] = best; si[w] = bi; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 1; k < 16; ++k)
       if (sv[k] > best || (sv[k] == best && si[k] < bi)) { best = sv[k]; bi = si[k]; }
     out[blockIdx.x] = bi;
   }
@@ -432,6 +470,14 @@ extern "C" int lap_ce_chunk_grad_hilo(const float* logits, int ldl, const int32_
 extern "C" int lap_argmax_rows_f32(const float* x, int rows, int n, int ld, int* out, void* stream) {
   if (rows <= 0 || n <= 0 || ld < n || !x || !out) return LAP_ERR_ARG;
   hipLaunchKernelGGL(argmax_rows_kernel, dim3(rows), dim3(256), 0, S_, x, ld, n, out);
+  LAP_CHECK_LAUNCH();
+  return LAP_OK;
+}
+extern "C" int lap_gumbel_argmax_rows_f32(const float* logits, int rows, int n, int ld, float inv_t, unsigned int seed_lo,
+                                          unsigned int seed_hi, int step, int* out, void* stream) {
+  if (rows <= 0 || n <= 0 || ld < n || !logits || !out || step < 0 || !(inv_t >= 0.f) || inv_t > 3.0e38f) return LAP_ERR_ARG;
+  hipLaunchKernelGGL(gumbel_argmax_rows_kernel, dim3(rows), dim3(1024), 0, S_, logits, ld, n, inv_t, (uint32_t)seed_lo,
+                     (uint32_t)seed_hi, (uint32_t)step, out);
   LAP_CHECK_LAUNCH();
   return LAP_OK;
 }

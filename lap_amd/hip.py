@@ -187,6 +187,7 @@ SIGNATURES: dict[str, list] = {
     "lap_sumsq_bf16": [_vp, _ll, _vp, _vp],
     "lap_adamw_ema_g16": [_vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _f, _f, _f, _f, _f, _vp],
     "lap_argmax_rows_f32": [_vp, _i, _i, _i, _vp, _vp],
+    "lap_gumbel_argmax_rows_f32": [_vp, _i, _i, _i, _f, C.c_uint, C.c_uint, _i, _vp, _vp],
     "lap_adamw_ema": [_vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _f, _f, _f, _f, _f, _vp],
     "lap_fm_mix": [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
     "lap_posemb_sincos": [_vp, _vp, _i, _i, _f, _f, _vp],
@@ -210,6 +211,8 @@ SIGNATURES: dict[str, list] = {
     "lap_decode_gate_up": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
     "lap_decode_lm_head": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
     "lap_decode_finish": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "lap_decode_sampling_words": [],
+    "lap_decode_lm_head_sample": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
 }
 
 _fn = {}
@@ -371,6 +374,25 @@ def argmax_rows(x, out=None):
     if out is None:
         out = torch.empty((x.shape[0],), dtype=torch.int32, device=x.device)
     call("lap_argmax_rows_f32", _p(x), x.shape[0], x.shape[1], x.stride(0), _p(out))
+    return out
+
+
+def sampling_words(seed, temperature):
+    """(seed low word, seed high word, inv_t) of a device-sampled draw (lap_amd/sampling.py): `seed` is taken modulo 2^64,
+    inv_t = float32(1 / temperature), 0 (greedy) for temperature <= 0; a temperature whose inverse is not finite raises."""
+    from lap_amd.sampling import inverse_temperature
+
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return seed & 0xFFFFFFFF, seed >> 32, float(inverse_temperature(temperature))
+
+
+def gumbel_argmax_rows(x, temperature, seed, step, out=None):
+    """x f32 [rows, n] -> int32 [rows]: argmax of x / temperature + the Gumbel noise of (seed, step, row, column), one pass."""
+    _req(x, torch.float32, "x")
+    lo, hi, inv_t = sampling_words(seed, temperature)
+    if out is None:
+        out = torch.empty((x.shape[0],), dtype=torch.int32, device=x.device)
+    call("lap_gumbel_argmax_rows_f32", _p(x), x.shape[0], x.shape[1], x.stride(0), inv_t, lo, hi, int(step), _p(out))
     return out
 
 
@@ -1353,6 +1375,37 @@ def decode_lm_head(state, x, gamma, hi, lo, pval, pidx, logits=None, eps=1e-6):
     B, D = x.shape
     call("lap_decode_lm_head", _p(state), _p(x), _p(gamma), _p(hi), _p(lo), B, D, hi.shape[0], float(eps), _p(logits), _p(pval),
          _p(pidx))
+
+
+def decode_sampling(device):
+    """The sampling words of a decode (lap_decode_lm_head_sample): int32 [4] = {seed low, seed high, bits of inv_t, 0}; zeros are
+    a greedy decode.  A captured graph holds its address; `decode_set_sampling` rewrites it between replays."""
+    return torch.zeros(_fn["lap_decode_sampling_words"](), dtype=torch.int32, device=device)
+
+
+def decode_set_sampling(buf, seed, temperature):
+    """Fill the sampling words with a plain host-to-device copy (no kernel).  temperature <= 0 is greedy."""
+    import numpy as np
+
+    _dreq(buf, torch.int32, "sampling")
+    lo, hi, inv_t = sampling_words(seed, temperature)
+    words = np.array([lo, hi, int(np.float32(inv_t).view(np.uint32)), 0], dtype=np.uint32).view(np.int32)
+    buf.copy_(torch.from_numpy(words))
+
+
+def decode_lm_head_sample(state, sampling, x, gamma, hi, lo, pval, pidx, logits=None, eps=1e-6):
+    """`decode_lm_head` with the sampler of `sampling` (see `decode_sampling`) as its epilogue; logits (debug) stay raw."""
+    _dreq(x, torch.bfloat16, "x"); _dreq(hi, torch.bfloat16, "hi"); _dreq(gamma, torch.float32, "gamma")
+    _dreq(sampling, torch.int32, "sampling")
+    if sampling.numel() < _fn["lap_decode_sampling_words"]():
+        raise TypeError("sampling: int32 [lap_decode_sampling_words()]")
+    if lo is not None:
+        _dreq(lo, torch.bfloat16, "lo")
+    if logits is not None:
+        _dreq(logits, torch.float32, "logits")
+    B, D = x.shape
+    call("lap_decode_lm_head_sample", _p(state), _p(sampling), _p(x), _p(gamma), _p(hi), _p(lo), B, D, hi.shape[0], float(eps),
+         _p(logits), _p(pval), _p(pidx))
 
 
 def decode_finish(state, pval, pidx, out, eos_token):

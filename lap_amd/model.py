@@ -1684,7 +1684,7 @@ class LAP:
         return lg
 
     def sample_tokens(self, rng, observation, *, max_decoding_steps: int = 390, temperature: float = 0.0, collect=None,
-                      decode: str = "eager"):
+                      decode: str = "eager", sampler: str = "host"):
         """lap.py:678-766 (LAP_AR serving mode): VLM-only prefill, then single-token decode until every sample has emitted
         EOS or `max_decoding_steps` tokens; returns int32 [B, max_decoding_steps] (zeros after the stop).
 
@@ -1701,17 +1701,34 @@ class LAP:
 
         decode: "eager" (default) runs each decode step as generic launches; "fused" runs it on the single-token kernels of
         csrc/decode.hip (Gemma-2B widths, 1 <= B <= 8, one replica; anything else raises ValueError) with a fixed-capacity
-        generated K/V cache and the step / EOS / stop state on the device, checked by the host once per 8 steps.  Greedy
-        only: temperature > 0 keeps the eager loop (its torch-generator Gumbel stream cannot run inside a captured graph).
-        The two paths differ in the summation order of their dot products only."""
+        generated K/V cache and the step / EOS / stop state on the device, checked by the host once per 8 steps.
+        The two paths differ in the summation order of their dot products only.
+
+        sampler: where the noise of a temperature > 0 draw comes from.  "host" (default) is the torch-generator Gumbel stream
+        above; it cannot run inside a captured graph, so `decode="fused"` with temperature > 0 keeps the eager loop.
+        "device" draws token t of row b as the argmax of logit * float32(1 / temperature) + g, g the counter-based Gumbel noise
+        of (seed = `rng` as a 64-bit integer, t, b, vocabulary index) that lap_amd/sampling.py defines and restates on the host:
+        `decode="eager"` applies it to its stored logits in one pass (lap_gumbel_argmax_rows_f32), `decode="fused"` as the
+        epilogue of the fused LM head (lap_decode_lm_head_sample), where no logit is stored.  The two decode modes then draw
+        from the same noise and differ in summation order only, and `sampling.sample_from_logits(collect["logit/<t>"],
+        temperature, rng, t)` reproduces a draw offline.  temperature <= 0 is greedy under either sampler, bit for bit the same.
+        `collect` keeps the raw logits under sampler="device" (under "host" it holds what the argmax saw, as before)."""
         if decode not in ("eager", "fused"):
             raise ValueError(f"sample_tokens: decode must be 'eager' or 'fused', got {decode!r}")
+        if sampler not in ("host", "device"):
+            raise ValueError(f"sample_tokens: sampler must be 'host' or 'device', got {sampler!r}")
         if decode == "fused":
             self._check_fused_decode(observation.tokenized_prompt.shape[0])
+        if sampler == "device":
+            hip.sampling_words(rng, temperature)        # (rejects a temperature whose inverse is not finite before any work)
         with self._serving_weights():
+            if decode == "fused" and sampler == "device":
+                return self._sample_tokens_fused(observation, max_decoding_steps=max_decoding_steps, collect=collect,
+                                                 sampling=(rng, temperature))
             if decode == "fused" and temperature <= 0.0:
                 return self._sample_tokens_fused(observation, max_decoding_steps=max_decoding_steps, collect=collect)
-            return self._sample_tokens(rng, observation, max_decoding_steps=max_decoding_steps, temperature=temperature, collect=collect)
+            return self._sample_tokens(rng, observation, max_decoding_steps=max_decoding_steps, temperature=temperature, collect=collect,
+                                       device_sampler=sampler == "device")
 
     def _ar_prefill(self, observation):
         """The VLM-only prefill of sample_tokens (lap.py:693-716): (B, Pn, prefix K/V cache per layer, kinfo_prefix [B, Pn],
@@ -1740,7 +1757,8 @@ class LAP:
         last = (torch.arange(B, device=dev) * Pn + seqlen - 1)
         return B, Pn, cache, kinfo_prefix, qinfo_d, plen, xf0.index_select(0, last).contiguous()
 
-    def _sample_tokens(self, rng, observation, *, max_decoding_steps: int = 390, temperature: float = 0.0, collect=None):
+    def _sample_tokens(self, rng, observation, *, max_decoding_steps: int = 390, temperature: float = 0.0, collect=None,
+                       device_sampler: bool = False):
         """`sample_tokens` with the weights as `_serving_weights` presents them (merged when the model has adapters)."""
         dev = self.device
         B, Pn, cache, kinfo_prefix, qinfo_d, plen, x_last = self._ar_prefill(observation)
@@ -1748,13 +1766,16 @@ class LAP:
         out = torch.zeros((B, max_decoding_steps), dtype=torch.int32, device=dev)
         eos = torch.zeros((B,), dtype=torch.bool, device=dev)
         gen = [(None, None)] * self.v.depth
-        g = _gen(rng, dev) if temperature > 0.0 else None
+        g = _gen(rng, dev) if temperature > 0.0 and not device_sampler else None
         step = 0
         while step < max_decoding_steps:
-            if temperature > 0.0:
-                u = torch.rand(logits.shape, generator=g, device=dev, dtype=torch.float32).clamp_(1e-20, 1.0)
-                logits = logits / temperature - torch.log(-torch.log(u))
-            token = hip.argmax_rows(logits)
+            if device_sampler and temperature > 0.0:      # one pass over the raw logits, no [B, V] temporaries
+                token = hip.gumbel_argmax_rows(logits, temperature, rng, step)
+            else:
+                if temperature > 0.0:
+                    u = torch.rand(logits.shape, generator=g, device=dev, dtype=torch.float32).clamp_(1e-20, 1.0)
+                    logits = logits / temperature - torch.log(-torch.log(u))
+                token = hip.argmax_rows(logits)
             if collect is not None:
                 collect[f"logit/{step}"] = logits.clone()
             out[:, step] = token
@@ -1783,8 +1804,8 @@ class LAP:
             raise ValueError(f"fused decode serves the Gemma-2B widths at 1 <= B <= 8 (D 2048, 8 / 1 heads of 256, MLP 16384); got "
                              f"B {B}, D {v.width}, heads {v.num_heads} / {v.num_kv_heads} of {v.head_dim}, MLP {v.mlp_dim}")
 
-    def _decode_ctx(self, B: int, Pn: int, cap: int):
-        return _DecodeCtx(self, B, Pn, cap)
+    def _decode_ctx(self, B: int, Pn: int, cap: int, sampling: bool = False):
+        return _DecodeCtx(self, B, Pn, cap, sampling)
 
     def _fused_first_token(self, ctx, pre, logits=None):
         """Reset the device state for the prefill `pre` (from `_ar_prefill`) and decode the first token from its last rows."""
@@ -1795,9 +1816,14 @@ class LAP:
         self._fused_token(ctx, x_last, logits)
 
     def _fused_token(self, ctx, x, logits=None):
-        """final norm + LM head over the hi / lo planes + argmax -> out[:, t], EOS mask, t + 1 (lap.py:716-724)."""
-        hip.decode_lm_head(ctx.state, x, self.F("llm/final_norm"), self.W("llm/embed"), self.ps.w16lo("llm/embed"), ctx.pval, ctx.pidx,
-                           logits)
+        """final norm + LM head over the hi / lo planes + argmax -> out[:, t], EOS mask, t + 1 (lap.py:716-724).  A context
+        with sampling words runs the sampling LM head, which is the greedy one while the words hold inv_t = 0."""
+        if ctx.sampling is not None:
+            hip.decode_lm_head_sample(ctx.state, ctx.sampling, x, self.F("llm/final_norm"), self.W("llm/embed"),
+                                      self.ps.w16lo("llm/embed"), ctx.pval, ctx.pidx, logits)
+        else:
+            hip.decode_lm_head(ctx.state, x, self.F("llm/final_norm"), self.W("llm/embed"), self.ps.w16lo("llm/embed"), ctx.pval,
+                               ctx.pidx, logits)
         hip.decode_finish(ctx.state, ctx.pval, ctx.pidx, ctx.out, self.EOS_TOKEN)
 
     def _fused_step(self, ctx, logits=None):
@@ -1817,10 +1843,13 @@ class LAP:
             hip.decode_proj_residual(ctx.state, ctx.act, self.W(p + "wd0"), ctx.xa, ctx.x, kwaves=hip.DECODE_KWAVES_DOWN)
         self._fused_token(ctx, ctx.x, logits)
 
-    def _sample_tokens_fused(self, observation, *, max_decoding_steps: int, collect=None):
+    def _sample_tokens_fused(self, observation, *, max_decoding_steps: int, collect=None, sampling=None):
+        """sampling: None (the greedy LM head) or (seed, temperature) for the sampling LM head."""
         pre = self._ar_prefill(observation)
         B, Pn = pre[0], pre[1]
-        ctx = self._decode_ctx(B, Pn, max_decoding_steps)
+        ctx = self._decode_ctx(B, Pn, max_decoding_steps, sampling is not None)
+        if sampling is not None:
+            ctx.set_sampling(*sampling)
         lg = torch.empty((B, self.config.vocab_size), dtype=torch.float32, device=self.device) if collect is not None else None
         self._fused_first_token(ctx, pre, lg)
         if collect is not None:     # debug: one host read per token
@@ -1843,7 +1872,7 @@ class _DecodeCtx:
     the fixed-capacity generated K/V cache of every layer ([depth, 2, B, cap, head_dim] bf16, 7.2 MB per sample at 390 steps
     for LAP-3B) and the step's activations.  The prefix K/V cache and kinfo come from the prefill (`bind`)."""
 
-    def __init__(self, model: LAP, B: int, Pn: int, cap: int):
+    def __init__(self, model: LAP, B: int, Pn: int, cap: int, sampling: bool = False):
         v = model.v
         dev = model.device
         bf = torch.bfloat16
@@ -1859,8 +1888,17 @@ class _DecodeCtx:
         self.act = torch.zeros((B, v.mlp_dim), dtype=bf, device=dev)
         self.attn_scratch = hip.decode_attn_scratch(B, Pn, cap, dev)
         self.pval, self.pidx = hip.decode_lm_partials(B, dev)
+        # the sampling words {seed low, seed high, bits of 1 / temperature, 0} of the sampling LM head (zeros: greedy); None:
+        # the context decodes on the greedy LM head
+        self.sampling = hip.decode_sampling(dev) if sampling else None
         self.prefix = None
         self.kinfo = None
+
+    def set_sampling(self, seed: int, temperature: float):
+        """Seed and temperature of the next decode (a host-to-device copy; captured graphs keep the buffer's address)."""
+        if self.sampling is None:
+            raise ValueError("this decode context was built without sampling")
+        hip.decode_set_sampling(self.sampling, seed, temperature)
 
     def bind(self, cache, kinfo_prefix):
         if kinfo_prefix.shape != (self.B, self.Pn):

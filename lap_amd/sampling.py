@@ -1,0 +1,109 @@
+"""The noise of a device-sampled LAP_AR token draw, restated on the host (numpy only; no GPU, no torch).
+
+`LAP.sample_tokens(..., sampler="device")` draws token `t` of row `b` as the argmax over the vocabulary of
+
+    score[j] = float32(logit[j] * inv_t) + g(seed, t, b, j)          inv_t = float32(1 / temperature)
+
+(lowest index among ties), the Gumbel-max form of the reference's `jax.random.categorical(logits / temperature)`
+(lap.py:719-724).  The noise is a pure function of (seed: uint64, step t, row b, vocabulary index j):
+
+* Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11; multipliers 0xD2511F53 /
+  0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85) with key = (low, high word of the seed) and counter = (j >> 1, b, t, 0);
+  index j takes output word j & 1 (words 2 and 3 are unused).
+* u = ((word >> 9) + 0.5) * 2^-23: the top 23 bits, so that n + 0.5 (2 n + 1 < 2^24) and u are exact in float32 and u lies
+  strictly inside (0, 1): 2^-24 <= u <= 1 - 2^-24.  (With 24 bits, n + 0.5 needs 25 significant bits once n >= 2^23; it
+  rounds, and the all-ones word gives u = 1 and infinite noise.)
+* g = -log(-log(u)) with the accurate float32 logarithm, so -2.81 < g < 16.64.
+
+The kernels (csrc/sampling.hpp, used by lap_decode_lm_head_sample and lap_gumbel_argmax_rows_f32) compute the same thing; they
+agree with this file up to the last bits of the two logarithms.  A served draw is reproduced offline from the raw logits with
+`sample_from_logits(logits, temperature, seed, step)`.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+PHILOX_M0, PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+PHILOX_W0, PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+_MASK = np.uint64(0xFFFFFFFF)
+_S32 = np.uint64(32)
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32 with 10 rounds.  counter: uint32 [..., 4], key: uint32 [..., 2] (broadcast against each other over the leading
+    dimensions); returns uint32 [..., 4]."""
+    c = np.asarray(counter, dtype=np.uint64) & _MASK
+    k = np.asarray(key, dtype=np.uint64) & _MASK
+    if c.shape[-1] != 4 or k.shape[-1] != 2:
+        raise ValueError("philox4x32_10: counter has 4 words, key has 2")
+    lead = np.broadcast_shapes(c.shape[:-1], k.shape[:-1])
+    c0, c1, c2, c3 = (np.broadcast_to(c[..., i], lead) for i in range(4))
+    k0, k1 = (np.broadcast_to(k[..., i], lead) for i in range(2))
+    m0, m1 = np.uint64(PHILOX_M0), np.uint64(PHILOX_M1)
+    for r in range(10):
+        if r:
+            k0 = (k0 + np.uint64(PHILOX_W0)) & _MASK
+            k1 = (k1 + np.uint64(PHILOX_W1)) & _MASK
+        p0, p1 = m0 * c0, m1 * c2              # 32 x 32 -> 64 bits
+        c0, c1, c2, c3 = (p1 >> _S32) ^ c1 ^ k0, p1 & _MASK, (p0 >> _S32) ^ c3 ^ k1, p0 & _MASK
+    return np.stack([c0, c1, c2, c3], -1).astype(np.uint32)
+
+
+def _seed_words(seed: int):
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return seed & 0xFFFFFFFF, seed >> 32
+
+
+def uniform_from_word(word):
+    """uint32 word -> float32 u strictly inside (0, 1), exact: ((word >> 9) + 0.5) * 2^-23."""
+    n = (np.asarray(word, dtype=np.uint32) >> np.uint32(9)).astype(np.float32)
+    return (n + np.float32(0.5)) * np.float32(2.0 ** -23)
+
+
+def gumbel_from_word(word):
+    """uint32 word -> float32 Gumbel noise -log(-log(u))."""
+    u = uniform_from_word(word)
+    return -np.log(-np.log(u, dtype=np.float32), dtype=np.float32)
+
+
+def gumbel_noise(seed: int, step: int, rows: int, vocab_size: int) -> np.ndarray:
+    """float32 [rows, vocab_size]: the noise of decode step `step` under `seed` (a 64-bit integer)."""
+    lo, hi = _seed_words(seed)
+    units = (vocab_size + 1) // 2
+    ctr = np.zeros((rows, units, 4), dtype=np.uint32)
+    ctr[..., 0] = np.arange(units, dtype=np.uint32)[None, :]
+    ctr[..., 1] = np.arange(rows, dtype=np.uint32)[:, None]
+    ctr[..., 2] = np.uint32(int(step) & 0xFFFFFFFF)
+    words = philox4x32_10(ctr, np.array([lo, hi], dtype=np.uint32))[..., :2].reshape(rows, 2 * units)[:, :vocab_size]
+    return gumbel_from_word(words)
+
+
+def inverse_temperature(temperature: float) -> np.float32:
+    """float32(1 / temperature); 0 (greedy) for temperature <= 0, as under the reference's `temperature > 0.0` test."""
+    temperature = float(temperature)
+    if temperature != temperature:
+        raise ValueError("temperature is NaN")
+    if temperature <= 0.0:
+        return np.float32(0.0)
+    with np.errstate(over="ignore"):
+        inv_t = np.float32(1.0 / temperature)
+    if not np.isfinite(inv_t):
+        raise ValueError(f"temperature {temperature!r}: 1 / temperature is not finite in float32")
+    return inv_t
+
+
+def scores_from_logits(logits, temperature: float, seed: int, step: int) -> np.ndarray:
+    """float32 [rows, V]: logit * inv_t + noise (two float32 roundings: the product, then the sum); the raw logits when greedy."""
+    lg = np.ascontiguousarray(np.asarray(logits, dtype=np.float32))
+    if lg.ndim != 2:
+        raise ValueError("logits: [rows, vocab_size]")
+    inv_t = inverse_temperature(temperature)
+    if inv_t == 0.0:
+        return lg
+    return lg * inv_t + gumbel_noise(seed, step, lg.shape[0], lg.shape[1])
+
+
+def sample_from_logits(logits, temperature: float, seed: int, step: int) -> np.ndarray:
+    """int32 [rows]: the token every row of float32 `logits` [rows, V] draws at decode step `step` under `seed`; the argmax
+    (lowest index among ties) when temperature <= 0."""
+    return np.argmax(scores_from_logits(logits, temperature, seed, step), axis=-1).astype(np.int32)

@@ -78,14 +78,20 @@ class GraphedTokenDecoder:
     (csrc/decode.hip), each of which reads its position, cache row and stop flag from the device state, so the same graph
     replays for every token and turns into no-ops once every sample has emitted EOS or the budget is spent.  The host reads
     the stop flag once per replay of (2).  Returns int32 [B, max_decoding_steps] like `sample_tokens` (a fresh tensor).
-    The EOS token is the model's `EOS_TOKEN` when the graphs are captured."""
+    The EOS token is the model's `EOS_TOKEN` when the graphs are captured.
+
+    sampling=True captures both graphs on the sampling LM head (`sample_tokens(decode="fused", sampler="device")`): the seed and
+    the temperature of a call are four device words that `__call__(obs, temperature=, seed=)` rewrites before the first replay,
+    so one capture serves greedy and sampled requests of any seed and temperature, with no further host read.  A greedy call
+    returns what the sampling=False decoder returns, bit for bit."""
 
     def __init__(self, model: LAP, batch_size: int = 1, max_decoding_steps: int = 390, prompt_len: int | None = None,
-                 steps_per_replay: int = 8):
+                 steps_per_replay: int = 8, sampling: bool = False):
         model._check_fused_decode(batch_size)
         if max_decoding_steps < 1 or steps_per_replay < 1:
             raise ValueError("max_decoding_steps and steps_per_replay must be >= 1")
         self.model, self.B, self.max_steps, self.spr = model, batch_size, max_decoding_steps, steps_per_replay
+        self.sampling = bool(sampling)
         cfg = model.config
         dev = model.device
         L = prompt_len or cfg.max_token_len
@@ -121,7 +127,7 @@ class GraphedTokenDecoder:
         m = self.model
         pre = m._ar_prefill(self.obs)
         if self.ctx is None:
-            self.ctx = m._decode_ctx(self.B, pre[1], self.max_steps)
+            self.ctx = m._decode_ctx(self.B, pre[1], self.max_steps, self.sampling)
         m._fused_first_token(self.ctx, pre)
 
     def _steps(self):
@@ -154,12 +160,16 @@ class GraphedTokenDecoder:
         return (all(k in obs.images and tuple(obs.images[k].shape) == tuple(g.images[k].shape) for k in g.images)
                 and tuple(obs.tokenized_prompt.shape) == tuple(g.tokenized_prompt.shape))
 
-    def __call__(self, obs: CoTObservation) -> torch.Tensor:
+    def __call__(self, obs: CoTObservation, *, temperature: float = 0.0, seed: int = 0) -> torch.Tensor:
+        if temperature > 0.0 and not self.sampling:
+            raise ValueError("GraphedTokenDecoder: temperature > 0 needs a decoder built with sampling=True")
         if self.g_step is None:
             self.capture()
         # merged LoRA weights / packed prefill images the graphs hold addresses of follow the parameters in place
         self.model.refresh_serve_caches()
         self._load(obs)
+        if self.sampling:
+            self.ctx.set_sampling(seed, temperature)
         self.g_prefill.replay()
         for _ in range((self.max_steps - 1 + self.spr - 1) // self.spr):
             if bool(self.ctx.state[1].item()):      # one host read per replay
@@ -310,10 +320,16 @@ class ARPolicy:
         self._sample_kwargs = dict(sample_kwargs or {})
         self._calls = 0
         # use_graph: greedy requests of the captured shapes replay a GraphedTokenDecoder (B = 1); anything else, and models whose
-        # widths the fused decode kernels do not serve, go through sample_tokens
+        # widths the fused decode kernels do not serve, go through sample_tokens.  With sample_kwargs["sampler"] == "device" the
+        # decoder is captured on the sampling LM head and serves requests of any temperature; the seed of a request is the call
+        # counter that sample_tokens gets as `rng`, so both routes (and a restarted server) draw the same tokens.
         self._decoder = None
+        if self._sample_kwargs.get("sampler", "host") not in ("host", "device"):
+            raise ValueError(f"ARPolicy: sampler must be 'host' or 'device', got {self._sample_kwargs['sampler']!r}")
+        self._device_sampler = self._sample_kwargs.get("sampler", "host") == "device"
         if use_graph and base.model.decode_supported(1):
-            self._decoder = GraphedTokenDecoder(base.model, 1, self._sample_kwargs.get("max_decoding_steps", 390))
+            self._decoder = GraphedTokenDecoder(base.model, 1, self._sample_kwargs.get("max_decoding_steps", 390),
+                                                sampling=self._device_sampler)
 
     def __getattr__(self, name):
         return getattr(self._base, name)
@@ -329,9 +345,10 @@ class ARPolicy:
             inputs = obs
         o, batched = base._to_observation(inputs)
         self._calls += 1
-        if (self._decoder is not None and self._sample_kwargs.get("temperature", 0.0) <= 0.0
+        temperature = self._sample_kwargs.get("temperature", 0.0)
+        if (self._decoder is not None and (temperature <= 0.0 or self._device_sampler)
                 and self._sample_kwargs.get("decode", "eager") in ("eager", "fused") and self._decoder.compatible(o)):
-            tokens = self._decoder(o)
+            tokens = self._decoder(o, temperature=temperature, seed=self._calls) if self._device_sampler else self._decoder(o)
         else:
             tokens = base.model.sample_tokens(self._calls, o, **self._sample_kwargs)
         out = {"state": batched.get("state"), "tokens": tokens.cpu().numpy(), "raw_state": raw_state}
@@ -354,7 +371,8 @@ def create_trained_policy_ar(*args, sample_kwargs: dict | None = None, language_
     generated ids -> text -> [dx, dy, dz, droll, dpitch, dyaw, gripper] (the language action describes the whole chunk as
     one delta, output_transforms.py:75-104; `Unnormalize` has no `actions` statistics to apply to such deltas and is left out
     as in the reference's standard stack it would act on the normalised `state` only).
-    ar_graph: serve greedy requests through a GraphedTokenDecoder (ARPolicy(use_graph=True)); off by default."""
+    ar_graph: serve greedy requests through a GraphedTokenDecoder (ARPolicy(use_graph=True)); off by default.  With
+    sample_kwargs={"temperature": T, "sampler": "device"} the same graphs serve sampled requests too."""
     from lap_amd import policy_io as pio
 
     base = create_trained_policy(*args, use_graph=False, **kwargs)

@@ -178,6 +178,16 @@ class WebsocketPolicyServer:
             writer.close()
 
 
+def _ar_sample_kwargs(temperature: float, sampler: str) -> dict:
+    """The `sample_kwargs` the --ar-temperature / --ar-sampler flags stand for; nothing at their defaults (today's server)."""
+    kw = {}
+    if temperature != 0.0:
+        kw["temperature"] = temperature
+    if sampler != "host":
+        kw["sampler"] = sampler
+    return {"sample_kwargs": kw} if kw else {}
+
+
 def main(argv=None):
     """python -m lap_amd.serve_ws --config lap_libero --checkpoint-dir DIR --tokenizer-model paligemma_tokenizer.model
     (scripts/serve_policy.py: env / policy selection reduced to an explicit config + checkpoint; `--type ar` for LAP_AR)."""
@@ -196,12 +206,20 @@ def main(argv=None):
     ap.add_argument("--port", type=int, default=8000)
     ap.add_argument("--ar-graph", action="store_true",
                     help="--type ar: decode greedy requests with the hipGraph-replayed fused decoder (GraphedTokenDecoder)")
+    ap.add_argument("--ar-temperature", type=float, default=0.0,
+                    help="--type ar: sampling temperature of every request (0: greedy)")
+    ap.add_argument("--ar-sampler", choices=["host", "device"], default="host",
+                    help="--type ar: 'device' draws with the counter-based noise of lap_amd/sampling.py; with --ar-graph the "
+                         "captured decoder then serves sampled requests too ('host': the torch-generator stream, eager decode)")
     a = ap.parse_args(argv)
     cfg = get_config(a.config)
     cfg = dataclasses.replace(cfg, model=dataclasses.replace(cfg.model, stop_action_to_vlm_grad=False))   # serve_policy.py:77-79
     if a.ar_graph and a.type != "ar":
         ap.error("--ar-graph needs --type ar")
+    if (a.ar_temperature != 0.0 or a.ar_sampler != "host") and a.type != "ar":
+        ap.error("--ar-temperature / --ar-sampler need --type ar")
     extra = {"ar_graph": True} if a.ar_graph else {}
+    extra.update(_ar_sample_kwargs(a.ar_temperature, a.ar_sampler))
     make = create_trained_policy_ar if a.type == "ar" else create_trained_policy
     policy = make(cfg, a.checkpoint_dir, tokenizer_model_path=a.tokenizer_model, default_prompt=a.default_prompt, **extra)
     logging.basicConfig(level=logging.INFO)

@@ -3,7 +3,11 @@
 rate against the 6.29 TB/s measured copy rate.  Random weights, the reference prompt shape, greedy, EOS disabled so that every
 run decodes N tokens.  One JSON line.
 
-    python tools/bench_ar.py [--tokens 64] [--config lap_bench] [--kwaves 4]
+    python tools/bench_ar.py [--tokens 64] [--config lap_bench] [--kwaves 4] [--temperature T]
+
+--temperature T > 0 adds the sampled figures: the eager loop with the torch-generator noise (sampler="host"), the eager loop and
+the fused steps with the device noise (sampler="device"), and a GraphedTokenDecoder(sampling=True) called sampled and greedy.
+--profile-graphed --temperature T replays one sampled decode on the sampling graphs instead of the greedy one.
 """
 import argparse
 import json
@@ -25,6 +29,7 @@ ap.add_argument("--tokens", type=int, default=64)
 ap.add_argument("--kwaves", type=int, default=hip.DECODE_KWAVES_DOWN, help="K split of the down projection (1 or 4)")
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--profile-graphed", action="store_true", help="capture, replay one graphed decode and exit (for rocprofv3)")
+ap.add_argument("--temperature", type=float, default=0.0, help="> 0: also measure sampled decoding at this temperature")
 a = ap.parse_args()
 hip.DECODE_KWAVES_DOWN = a.kwaves
 
@@ -51,8 +56,13 @@ def timeit(fn, n):
     return (time.perf_counter() - t0) / n * 1e3
 
 
+T = a.temperature
 if a.profile_graphed:
-    dec(o)
+    if T > 0.0:
+        sdec = GraphedTokenDecoder(model, 1, N, sampling=True)
+        sdec(o, temperature=T, seed=1)
+    else:
+        dec(o)
     torch.cuda.synchronize()
     sys.exit(0)
 t_pre = timeit(lambda: model.sample_tokens(0, o, max_decoding_steps=1), a.reps)            # prefill + first token
@@ -71,6 +81,26 @@ head = model.W("llm/embed").numel() * 2 * (2 if model.ps.w16lo("llm/embed") is n
 bytes_tok = v.depth * layer + head
 per = lambda t, t0: (t - t0) / (N - 1)
 g_ms = per(t_graph, t_gpre)
+sampled = {}
+if T > 0.0:
+    st = lambda **kw: (lambda: model.sample_tokens(1, o, max_decoding_steps=N, temperature=T, **kw))
+    t_host = timeit(st(), a.reps)
+    t_edev = timeit(st(sampler="device"), a.reps)
+    t_fdev = timeit(st(sampler="device", decode="fused"), a.reps)
+    sdec = GraphedTokenDecoder(model, 1, N, sampling=True).capture()
+    t_spre = timeit(lambda: (sdec.g_prefill.replay()), a.reps)
+    t_sgraph = timeit(lambda: sdec(o, temperature=T, seed=1), a.reps)
+    t_sgreedy = timeit(lambda: sdec(o), a.reps)
+    sgot = sdec(o, temperature=T, seed=1)
+    sampled = {
+        "temperature": T,
+        "eager_host_sampled_ms_per_token": round(per(t_host, t_pre), 3),
+        "eager_device_sampled_ms_per_token": round(per(t_edev, t_pre), 3),
+        "fused_sampled_ms_per_token": round(per(t_fdev, t_pre), 3),
+        "graphed_sampled_ms_per_token": round(per(t_sgraph, t_spre), 3),
+        "graphed_greedy_on_sampling_graph_ms_per_token": round(per(t_sgreedy, t_spre), 3),
+        "graphed_sampled_equals_fused_sampled": bool(torch.equal(sgot, st(sampler="device", decode="fused")())),
+        "greedy_on_sampling_graph_equals_graphed": bool(torch.equal(sdec(o), got))}
 print(json.dumps({
     "metric": "batch-1 LAP_AR decode LAP-3B bf16 (ms per token after the prefill, greedy, EOS disabled)",
     "tokens": N, "prompt_len": cfg.max_token_len,
@@ -80,4 +110,4 @@ print(json.dumps({
     "graphed_vs_eager_leading_tokens_equal": agree, "graphed_equals_eager": bool(torch.equal(got, eager)),
     "algorithmic_bytes_per_token": bytes_tok, "floor_ms_per_token_at_6.29TBps": round(bytes_tok / 6.29e12 * 1e3, 3),
     "achieved_GBps_graphed": round(bytes_tok / (g_ms * 1e-3) / 1e9, 1),
-    "share_of_6.29TBps": round(bytes_tok / (g_ms * 1e-3) / 6.29e12, 3), "down_proj_kwaves": a.kwaves}))
+    "share_of_6.29TBps": round(bytes_tok / (g_ms * 1e-3) / 6.29e12, 3), "down_proj_kwaves": a.kwaves} | sampled))
