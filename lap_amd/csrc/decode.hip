@@ -26,9 +26,18 @@
 //               done                                                                         (lap_argmax_rows_f32)
 // Rounding points are those of the eager step; only the summation order of the dot products differs.
 // Device state is written with plain per-lane stores.
+//
+// fp8 weight-only decoding (the *_fp8 entry points; format: lap_amd/fp8.py): the weight stream is OCP e4m3 codes [N][K], one
+// byte per weight, with one power-of-two scale 2^e per output row n, e the largest integer with amax_n 2^e <= 448.  The same
+// kernels stream the codes (8 per lane per load: lane l owns the k it owns in the bf16 stream), widen them with
+// v_cvt_pk_f32_fp8, accumulate the CODES in f32 and multiply the finished row sum by 2^-e once, ahead of the epilogue's first
+// rounding point.  A power-of-two scale commutes with f32 accumulation and every code 2^-e is a bf16 number, so with the same
+// k-to-lane map and the same order of additions this computes, bit for bit, what the bf16 kernel computes on the dequantised
+// weights (LAP_DEC_F8_LANE = 16 is the 1 KiB-per-wave-instruction variant, equal up to the summation order only).  lap_quantize_fp8_rows makes codes and scales from bf16 or f32 rows into caller-owned buffers.
 #include "common.hpp"
 #include "sampling.hpp"
 #include "../../include/lap_hip.h"
+#include <type_traits>
 
 #define S_ ((hipStream_t)stream)
 
@@ -56,6 +65,36 @@ __device__ __forceinline__ bf16x8 ldw(const bf16* p) {      // the weight stream
 __device__ __forceinline__ float dot8(const bf16x8 w, const float (&x)[8], float acc) {
 #pragma unroll
   for (int e = 0; e < 8; ++e) acc = __builtin_fmaf((float)w[e], x[e], acc);
+  return acc;
+}
+// ---- the e4m3 weight stream
+#ifndef LAP_DEC_F8_LANE
+#define LAP_DEC_F8_LANE 8                  // codes per lane per load: 8 (the bf16 stream's k-to-lane map: bit-equal results) or 16 (1 KiB per wave instruction)
+#endif
+constexpr int F8L = LAP_DEC_F8_LANE;
+static_assert(F8L == 8 || F8L == 16, "LAP_DEC_F8_LANE: 8 or 16");
+typedef __attribute__((ext_vector_type(F8L / 4))) unsigned f8w;
+__device__ __forceinline__ f8w ldw8(const uint8_t* p) {     // read once by one wave, like ldw
+  return __builtin_nontemporal_load(reinterpret_cast<const f8w*>(p));
+}
+__device__ __forceinline__ void widen8(const f8w w, float (&c)[F8L]) {
+#pragma unroll
+  for (int i = 0; i < F8L / 4; ++i) {
+    const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], true);
+    c[4 * i] = lo[0]; c[4 * i + 1] = lo[1]; c[4 * i + 2] = hi[0]; c[4 * i + 3] = hi[1];
+  }
+}
+__device__ __forceinline__ void ldxf(const bf16* p, float (&v)[F8L]) {
+#pragma unroll
+  for (int c = 0; c < F8L / 8; ++c) {
+    const bf16x8 t = *reinterpret_cast<const bf16x8*>(p + 8 * c);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[8 * c + e] = (float)t[e];
+  }
+}
+__device__ __forceinline__ float dotf8(const float (&c)[F8L], const float (&x)[F8L], float acc) {
+#pragma unroll
+  for (int e = 0; e < F8L; ++e) acc = __builtin_fmaf(c[e], x[e], acc);
   return acc;
 }
 __device__ __forceinline__ bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
@@ -103,6 +142,10 @@ struct ProjP {
   float q_scale;
 };
 
+struct ProjP8 : ProjP {     // w: e4m3 codes [N][K]
+  const float* wscale;      // [N] 2^e per output row
+};
+
 // One "unit" = the two output features an epilogue needs together: QKV the rotation pair (d, d + HD/2) of one head; GeGLU a
 // gate column and its up column; RES two neighbouring columns.  KW waves of a block split K for one unit (KW = 4) or each
 // wave owns a unit (KW = 1); blocks walk the units with a grid stride.
@@ -113,8 +156,10 @@ __device__ __forceinline__ void unit_features(const ProjP& p, int u, int& f0, in
   else { f0 = 2 * u; f1 = 2 * u + 1; }
 }
 
-template <int EPI, int B, bool NORM, int KW>
-__global__ __launch_bounds__(256) void dec_proj_kernel(ProjP p) {
+// P = ProjP8: the fp8 weight stream (the ProjP instances are the bf16 kernels unchanged).
+template <int EPI, int B, bool NORM, int KW, class P = ProjP>
+__global__ __launch_bounds__(256) void dec_proj_kernel(P p) {
+  constexpr bool F8 = std::is_same<P, ProjP8>::value;
   __shared__ __attribute__((aligned(16))) bf16 sx[NORM ? B * DEC_D : 8];
   __shared__ float red[4];
   __shared__ float sacc[KW > 1 ? 4 * 2 * B : 1];
@@ -135,7 +180,26 @@ __global__ __launch_bounds__(256) void dec_proj_kernel(ProjP p) {
     float a0[B], a1[B];
 #pragma unroll
     for (int b = 0; b < B; ++b) { a0[b] = 0.f; a1[b] = 0.f; }
-    if (valid) {
+    if constexpr (F8) {
+      if (valid) {
+        const uint8_t* w0 = reinterpret_cast<const uint8_t*>(p.w) + (long long)f0 * p.K;
+        const uint8_t* w1 = reinterpret_cast<const uint8_t*>(p.w) + (long long)f1 * p.K;
+#pragma unroll 4
+        for (int k = wk * Ks + lane * F8L; k < (wk + 1) * Ks; k += 64 * F8L) {
+          const f8w v0 = ldw8(w0 + k), v1 = ldw8(w1 + k);
+          float c0[F8L], c1[F8L];
+          widen8(v0, c0);
+          widen8(v1, c1);
+#pragma unroll
+          for (int b = 0; b < B; ++b) {
+            float xv[F8L];
+            ldxf(xs + (long long)b * p.K + k, xv);
+            a0[b] = dotf8(c0, xv, a0[b]);
+            a1[b] = dotf8(c1, xv, a1[b]);
+          }
+        }
+      }
+    } else if (valid) {
       const bf16* w0 = p.w + (long long)f0 * p.K;
       const bf16* w1 = p.w + (long long)f1 * p.K;
 #pragma unroll 4
@@ -173,6 +237,7 @@ __global__ __launch_bounds__(256) void dec_proj_kernel(ProjP p) {
 #pragma unroll
     for (int b = 0; b < B; ++b) if (b == lane) { y0 = a0[b]; y1 = a1[b]; }
     const int b = lane;
+    if constexpr (F8) { y0 *= 1.0f / p.wscale[f0]; y1 *= 1.0f / p.wscale[f1]; }     // 2^-e: exact
     if (EPI == EPI_RES) {
       const bf16* r = p.res + (long long)b * p.N + f0;
       bf16x2 o;
@@ -380,8 +445,15 @@ struct LmP {
 // keeps row b's pair, runs row b's Philox block and its four logarithms (B <= 8 lanes carry data, the instruction count is that
 // of one row) and folds the two scores into ITS running best, so the B-fold compare chain of the greedy form becomes one.
 // The <B, false> instances are the greedy kernel unchanged.
-template <int B, bool SAMPLE>
-__global__ __launch_bounds__(256) void dec_lm_head_kernel(LmP p) {
+// P = LmP8: `hi` is ONE plane of e4m3 codes with a scale per vocabulary row instead of the hi / lo bf16 planes; partials,
+// sampling epilogue and the debug logits are those of the LmP instances, which are the bf16 kernels unchanged.
+struct LmP8 : LmP {
+  const float* wscale;                 // [V] 2^e per vocabulary row
+};
+
+template <int B, bool SAMPLE, class P = LmP>
+__global__ __launch_bounds__(256) void dec_lm_head_kernel(P p) {
+  constexpr bool F8 = std::is_same<P, LmP8>::value;
   __shared__ __attribute__((aligned(16))) bf16 sx[B * DEC_D];
   __shared__ float red[4];
   __shared__ float sv[4][B];
@@ -407,25 +479,47 @@ __global__ __launch_bounds__(256) void dec_lm_head_kernel(LmP p) {
     float h0[B], h1[B], l0[B], l1[B];
 #pragma unroll
     for (int b = 0; b < B; ++b) { h0[b] = 0.f; h1[b] = 0.f; l0[b] = 0.f; l1[b] = 0.f; }
-#pragma unroll (B > 4 ? 2 : 4)            // (4 at B = 7 spills)
-    for (int k = lane * 8; k < p.D; k += 512) {
-      const bf16x8 w0 = ldw(p.hi + (long long)f0 * p.D + k), w1 = ldw(p.hi + (long long)f1 * p.D + k);
-      bf16x8 z0 = w0, z1 = w1;
-      if (p.lo) { z0 = ldw(p.lo + (long long)f0 * p.D + k); z1 = ldw(p.lo + (long long)f1 * p.D + k); }
+    if constexpr (F8) {
+      const uint8_t* c0p = reinterpret_cast<const uint8_t*>(p.hi) + (long long)f0 * p.D;
+      const uint8_t* c1p = reinterpret_cast<const uint8_t*>(p.hi) + (long long)f1 * p.D;
+#pragma unroll 2
+      for (int k = lane * F8L; k < p.D; k += 64 * F8L) {
+        const f8w w0 = ldw8(c0p + k), w1 = ldw8(c1p + k);
+        float c0[F8L], c1[F8L];
+        widen8(w0, c0);
+        widen8(w1, c1);
 #pragma unroll
-      for (int b = 0; b < B; ++b) {
-        float xv[8];
-        ld8f(sx + b * p.D + k, xv);
-        h0[b] = dot8(w0, xv, h0[b]);
-        h1[b] = dot8(w1, xv, h1[b]);
-        if (p.lo) { l0[b] = dot8(z0, xv, l0[b]); l1[b] = dot8(z1, xv, l1[b]); }
+        for (int b = 0; b < B; ++b) {
+          float xv[F8L];
+          ldxf(sx + b * p.D + k, xv);
+          h0[b] = dotf8(c0, xv, h0[b]);
+          h1[b] = dotf8(c1, xv, h1[b]);
+        }
+      }
+    } else {
+#pragma unroll (B > 4 ? 2 : 4)            // (4 at B = 7 spills)
+      for (int k = lane * 8; k < p.D; k += 512) {
+        const bf16x8 w0 = ldw(p.hi + (long long)f0 * p.D + k), w1 = ldw(p.hi + (long long)f1 * p.D + k);
+        bf16x8 z0 = w0, z1 = w1;
+        if (p.lo) { z0 = ldw(p.lo + (long long)f0 * p.D + k); z1 = ldw(p.lo + (long long)f1 * p.D + k); }
+#pragma unroll
+        for (int b = 0; b < B; ++b) {
+          float xv[8];
+          ld8f(sx + b * p.D + k, xv);
+          h0[b] = dot8(w0, xv, h0[b]);
+          h1[b] = dot8(w1, xv, h1[b]);
+          if (p.lo) { l0[b] = dot8(z0, xv, l0[b]); l1[b] = dot8(z1, xv, l1[b]); }
+        }
       }
     }
     float y0 = 0.f, y1 = 0.f;
+    float r0 = 1.f, r1 = 1.f;
+    if constexpr (F8) { r0 = 1.0f / p.wscale[f0]; r1 = 1.0f / p.wscale[f1]; }     // 2^-e: exact
 #pragma unroll
     for (int b = 0; b < B; ++b) {
       float v0 = wave_sum(h0[b]), v1 = wave_sum(h1[b]);
-      if (p.lo) { v0 += wave_sum(l0[b]); v1 += wave_sum(l1[b]); }   // the eager path: C = hi.h, then C += lo.h
+      if constexpr (F8) { v0 *= r0; v1 *= r1; }
+      else if (p.lo) { v0 += wave_sum(l0[b]); v1 += wave_sum(l1[b]); }   // the eager path: C = hi.h, then C += lo.h
       if (p.logits && lane == 0) {
         p.logits[(long long)b * p.V + f0] = v0;
         if (f1 != f0) p.logits[(long long)b * p.V + f1] = v1;
@@ -530,6 +624,118 @@ __global__ __launch_bounds__(256) void dec_init_kernel(int* state, const int* pl
 
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
+// ------------------------------------------------------------------------------------------------- e4m3 row quantiser
+// One block per row (grid stride): amax, e = the largest integer with amax 2^e <= 448 (0 for an all-zero row; kept inside
+// [-126, 126] so that 2^e and 2^-e are normal f32 numbers), scale[n] = 2^e, codes = e4m3(w 2^e) to nearest even.  w 2^e is
+// exact and never above 448, so the conversion needs no clamp.  Runs once per parameter version.
+template <class T>
+__global__ __launch_bounds__(256) void quant_fp8_rows_kernel(const T* src, uint8_t* codes, float* scales, long long N, int K) {
+  __shared__ float red[4];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  for (long long n = blockIdx.x; n < N; n += gridDim.x) {
+    const T* s = src + n * K;
+    float am = 0.f;
+    for (int c = threadIdx.x * 4; c < K; c += 1024) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) am = fmaxf(am, fabsf((float)s[c + e]));
+    }
+    am = wave_max(am);
+    __syncthreads();
+    if (lane == 0) red[w] = am;
+    __syncthreads();
+    am = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    int e = 0;
+    if (am > 0.f) {
+      int x;
+      const float m = frexpf(am, &x);                 // am = m 2^x, 0.5 <= m < 1; 448 = 0.875 2^9
+      e = min(max((m <= 0.875f ? 9 : 8) - x, -126), 126);
+    }
+    const float sc = ldexpf(1.0f, e);
+    if (threadIdx.x == 0) scales[n] = sc;
+    for (int c = threadIdx.x * 4; c < K; c += 1024) {
+      int q = 0;
+      q = __builtin_amdgcn_cvt_pk_fp8_f32((float)s[c] * sc, (float)s[c + 1] * sc, q, false);
+      q = __builtin_amdgcn_cvt_pk_fp8_f32((float)s[c + 2] * sc, (float)s[c + 3] * sc, q, true);
+      *reinterpret_cast<int*>(codes + n * K + c) = q;
+    }
+  }
+}
+
+// a wave's K slice is whole lane loads of the code stream (a slice of 512 codes keeps half the lanes of a 16-byte load busy)
+inline bool f8_k_ok(int K, int kwaves) { return K % 16 == 0 && K % kwaves == 0 && (K / kwaves) % F8L == 0; }
+
+int qkv_impl(const int* state, const void* x, const float* gamma, const void* wqkv, const float* wscale, bool f8, void* q,
+             void* cache_k, void* cache_v, int B, int D, int NH, int HD, int cap, float q_scale, float eps, void* stream) {
+  if (!lap_decode_ok(B, D, NH, 1, HD, DEC_H, 2) || !state || !gamma || !q || !cache_k || !cache_v || cap < 1 ||
+      !aligned16(x) || !aligned16(wqkv) || (f8 && (!wscale || !f8_k_ok(D, 1)))) return LAP_ERR_ARG;
+  ProjP8 p{};
+  p.state = state; p.x = (const bf16*)x; p.gamma = gamma; p.w = (const bf16*)wqkv; p.K = D; p.units = (NH + 2) * HD / 2;
+  p.eps = eps; p.q = (bf16*)q; p.ck = (bf16*)cache_k; p.cv = (bf16*)cache_v; p.cap = cap; p.NH = NH; p.HD = HD; p.q_scale = q_scale;
+  p.wscale = wscale;
+  const ProjP& pb = p;
+  const dim3 grid((p.units + 3) / 4);
+  if (f8) { DISPATCH_B(B, hipLaunchKernelGGL((dec_proj_kernel<EPI_QKV, BB, true, 1, ProjP8>), grid, dim3(256), 0, S_, p)); }
+  else { DISPATCH_B(B, hipLaunchKernelGGL((dec_proj_kernel<EPI_QKV, BB, true, 1>), grid, dim3(256), 0, S_, pb)); }
+  LAP_CHECK_LAUNCH();
+  return LAP_OK;
+}
+
+int gate_up_impl(const int* state, const void* x, const float* gamma, const void* wgu, const float* wscale, bool f8, void* act,
+                 int B, int D, int H, float eps, void* stream) {
+  if (!lap_decode_ok(B, D, DEC_NH, 1, DEC_HD, H, 2) || !state || !gamma || !act || !aligned16(x) || !aligned16(wgu) ||
+      (f8 && (!wscale || !f8_k_ok(D, 1)))) return LAP_ERR_ARG;
+  ProjP8 p{};
+  p.state = state; p.x = (const bf16*)x; p.gamma = gamma; p.w = (const bf16*)wgu; p.K = D; p.units = H; p.H = H; p.eps = eps;
+  p.out = (bf16*)act;
+  p.wscale = wscale;
+  const ProjP& pb = p;
+  const dim3 grid(min(H / 4, 1024));
+  if (f8) { DISPATCH_B(B, hipLaunchKernelGGL((dec_proj_kernel<EPI_GEGLU, BB, true, 1, ProjP8>), grid, dim3(256), 0, S_, p)); }
+  else { DISPATCH_B(B, hipLaunchKernelGGL((dec_proj_kernel<EPI_GEGLU, BB, true, 1>), grid, dim3(256), 0, S_, pb)); }
+  LAP_CHECK_LAUNCH();
+  return LAP_OK;
+}
+
+int proj_residual_impl(const int* state, const void* a, const void* w, const float* wscale, bool f8, const void* x, void* y, int B,
+                       int N, int K, int kwaves, void* stream) {
+  if (!state || !a || !w || !x || !y || B < 1 || B > DEC_MAXB || N < 2 || (N & 1) || K < 512 || (K % 2048) ||
+      (kwaves != 1 && kwaves != 4) || !aligned16(a) || !aligned16(w) || ((uintptr_t)y & 3) || ((uintptr_t)x & 3) ||
+      (f8 && (!wscale || !f8_k_ok(K, kwaves)))) return LAP_ERR_ARG;
+  ProjP8 p{};
+  p.state = state; p.x = (const bf16*)a; p.w = (const bf16*)w; p.K = K; p.units = N / 2; p.N = N; p.res = (const bf16*)x;
+  p.out = (bf16*)y;
+  p.wscale = wscale;
+  const ProjP& pb = p;
+  const int nu = 4 / kwaves;
+  const dim3 grid(min((p.units + nu - 1) / nu, 2048));
+  if (f8) {
+    if (kwaves == 4) { DISPATCH_B(B, hipLaunchKernelGGL((dec_proj_kernel<EPI_RES, BB, false, 4, ProjP8>), grid, dim3(256), 0, S_, p)); }
+    else { DISPATCH_B(B, hipLaunchKernelGGL((dec_proj_kernel<EPI_RES, BB, false, 1, ProjP8>), grid, dim3(256), 0, S_, p)); }
+  } else if (kwaves == 4) { DISPATCH_B(B, hipLaunchKernelGGL((dec_proj_kernel<EPI_RES, BB, false, 4>), grid, dim3(256), 0, S_, pb)); }
+  else { DISPATCH_B(B, hipLaunchKernelGGL((dec_proj_kernel<EPI_RES, BB, false, 1>), grid, dim3(256), 0, S_, pb)); }
+  LAP_CHECK_LAUNCH();
+  return LAP_OK;
+}
+
+// sampling == NULL: the greedy head.  f8: `hi` holds the code plane, `lo` is not used.
+int lm_head_impl(const int* state, const int* sampling, bool sample, const void* x, const float* gamma, const void* hi, const void* lo,
+                 const float* wscale, bool f8, int B, int D, int V, float eps, float* logits, float* pval, int* pidx, void* stream) {
+  if (!state || (sample && !sampling) || !gamma || !hi || !pval || !pidx || B < 1 || B > DEC_MAXB || D != DEC_D || V < 2 ||
+      !aligned16(x) || !aligned16(hi) || (lo && !aligned16(lo)) || (f8 && (!wscale || !f8_k_ok(D, 1)))) return LAP_ERR_ARG;
+  LmP8 p{};
+  p.state = state; p.x = (const bf16*)x; p.gamma = gamma; p.eps = eps; p.hi = (const bf16*)hi; p.lo = f8 ? nullptr : (const bf16*)lo;
+  p.V = V; p.D = D; p.logits = logits; p.pval = pval; p.pidx = pidx; p.samp = sampling;
+  p.wscale = wscale;
+  const LmP& pb = p;
+  if (f8) {
+    if (sample) { DISPATCH_B(B, hipLaunchKernelGGL((dec_lm_head_kernel<BB, true, LmP8>), dim3(LM_BLOCKS), dim3(256), 0, S_, p)); }
+    else { DISPATCH_B(B, hipLaunchKernelGGL((dec_lm_head_kernel<BB, false, LmP8>), dim3(LM_BLOCKS), dim3(256), 0, S_, p)); }
+  } else if (sample) { DISPATCH_B(B, hipLaunchKernelGGL((dec_lm_head_kernel<BB, true>), dim3(LM_BLOCKS), dim3(256), 0, S_, pb)); }
+  else { DISPATCH_B(B, hipLaunchKernelGGL((dec_lm_head_kernel<BB, false>), dim3(LM_BLOCKS), dim3(256), 0, S_, pb)); }
+  LAP_CHECK_LAUNCH();
+  return LAP_OK;
+}
+
 }  // namespace
 
 extern "C" int lap_decode_ok(int B, int D, int NH, int NKV, int HD, int H, int V) {
@@ -557,42 +763,17 @@ extern "C" int lap_decode_embed(const int* state, const float* table, int row_lo
 
 extern "C" int lap_decode_qkv(const int* state, const void* x, const float* gamma, const void* wqkv, void* q, void* cache_k,
                               void* cache_v, int B, int D, int NH, int HD, int cap, float q_scale, float eps, void* stream) {
-  if (!lap_decode_ok(B, D, NH, 1, HD, DEC_H, 2) || !state || !gamma || !q || !cache_k || !cache_v || cap < 1 ||
-      !aligned16(x) || !aligned16(wqkv)) return LAP_ERR_ARG;
-  ProjP p{};
-  p.state = state; p.x = (const bf16*)x; p.gamma = gamma; p.w = (const bf16*)wqkv; p.K = D; p.units = (NH + 2) * HD / 2;
-  p.eps = eps; p.q = (bf16*)q; p.ck = (bf16*)cache_k; p.cv = (bf16*)cache_v; p.cap = cap; p.NH = NH; p.HD = HD; p.q_scale = q_scale;
-  const dim3 grid((p.units + 3) / 4);
-  DISPATCH_B(B, hipLaunchKernelGGL((dec_proj_kernel<EPI_QKV, BB, true, 1>), grid, dim3(256), 0, S_, p));
-  LAP_CHECK_LAUNCH();
-  return LAP_OK;
+  return qkv_impl(state, x, gamma, wqkv, nullptr, false, q, cache_k, cache_v, B, D, NH, HD, cap, q_scale, eps, stream);
 }
 
 extern "C" int lap_decode_gate_up(const int* state, const void* x, const float* gamma, const void* wgu, void* act, int B, int D,
                                   int H, float eps, void* stream) {
-  if (!lap_decode_ok(B, D, DEC_NH, 1, DEC_HD, H, 2) || !state || !gamma || !act || !aligned16(x) || !aligned16(wgu)) return LAP_ERR_ARG;
-  ProjP p{};
-  p.state = state; p.x = (const bf16*)x; p.gamma = gamma; p.w = (const bf16*)wgu; p.K = D; p.units = H; p.H = H; p.eps = eps;
-  p.out = (bf16*)act;
-  const dim3 grid(min(H / 4, 1024));
-  DISPATCH_B(B, hipLaunchKernelGGL((dec_proj_kernel<EPI_GEGLU, BB, true, 1>), grid, dim3(256), 0, S_, p));
-  LAP_CHECK_LAUNCH();
-  return LAP_OK;
+  return gate_up_impl(state, x, gamma, wgu, nullptr, false, act, B, D, H, eps, stream);
 }
 
 extern "C" int lap_decode_proj_residual(const int* state, const void* a, const void* w, const void* x, void* y, int B, int N, int K,
                                         int kwaves, void* stream) {
-  if (!state || !a || !w || !x || !y || B < 1 || B > DEC_MAXB || N < 2 || (N & 1) || K < 512 || (K % 2048) ||
-      (kwaves != 1 && kwaves != 4) || !aligned16(a) || !aligned16(w) || ((uintptr_t)y & 3) || ((uintptr_t)x & 3)) return LAP_ERR_ARG;
-  ProjP p{};
-  p.state = state; p.x = (const bf16*)a; p.w = (const bf16*)w; p.K = K; p.units = N / 2; p.N = N; p.res = (const bf16*)x;
-  p.out = (bf16*)y;
-  const int nu = 4 / kwaves;
-  const dim3 grid(min((p.units + nu - 1) / nu, 2048));
-  if (kwaves == 4) { DISPATCH_B(B, hipLaunchKernelGGL((dec_proj_kernel<EPI_RES, BB, false, 4>), grid, dim3(256), 0, S_, p)); }
-  else { DISPATCH_B(B, hipLaunchKernelGGL((dec_proj_kernel<EPI_RES, BB, false, 1>), grid, dim3(256), 0, S_, p)); }
-  LAP_CHECK_LAUNCH();
-  return LAP_OK;
+  return proj_residual_impl(state, a, w, nullptr, false, x, y, B, N, K, kwaves, stream);
 }
 
 extern "C" int lap_decode_attn_scratch_floats(int B, int Pn, int cap) {
@@ -624,14 +805,7 @@ extern "C" int lap_decode_attention(const int* state, const void* q, const void*
 
 extern "C" int lap_decode_lm_head(const int* state, const void* x, const float* gamma, const void* hi, const void* lo, int B, int D,
                                   int V, float eps, float* logits, float* pval, int* pidx, void* stream) {
-  if (!state || !gamma || !hi || !pval || !pidx || B < 1 || B > DEC_MAXB || D != DEC_D || V < 2 || !aligned16(x) || !aligned16(hi) ||
-      (lo && !aligned16(lo))) return LAP_ERR_ARG;
-  LmP p{};
-  p.state = state; p.x = (const bf16*)x; p.gamma = gamma; p.eps = eps; p.hi = (const bf16*)hi; p.lo = (const bf16*)lo;
-  p.V = V; p.D = D; p.logits = logits; p.pval = pval; p.pidx = pidx;
-  DISPATCH_B(B, hipLaunchKernelGGL((dec_lm_head_kernel<BB, false>), dim3(LM_BLOCKS), dim3(256), 0, S_, p));
-  LAP_CHECK_LAUNCH();
-  return LAP_OK;
+  return lm_head_impl(state, nullptr, false, x, gamma, hi, lo, nullptr, false, B, D, V, eps, logits, pval, pidx, stream);
 }
 
 extern "C" int lap_decode_sampling_words(void) { return 4; }
@@ -639,14 +813,7 @@ extern "C" int lap_decode_sampling_words(void) { return 4; }
 extern "C" int lap_decode_lm_head_sample(const int* state, const int* sampling, const void* x, const float* gamma, const void* hi,
                                          const void* lo, int B, int D, int V, float eps, float* logits, float* pval, int* pidx,
                                          void* stream) {
-  if (!state || !sampling || !gamma || !hi || !pval || !pidx || B < 1 || B > DEC_MAXB || D != DEC_D || V < 2 || !aligned16(x) ||
-      !aligned16(hi) || (lo && !aligned16(lo))) return LAP_ERR_ARG;
-  LmP p{};
-  p.state = state; p.x = (const bf16*)x; p.gamma = gamma; p.eps = eps; p.hi = (const bf16*)hi; p.lo = (const bf16*)lo;
-  p.V = V; p.D = D; p.logits = logits; p.pval = pval; p.pidx = pidx; p.samp = sampling;
-  DISPATCH_B(B, hipLaunchKernelGGL((dec_lm_head_kernel<BB, true>), dim3(LM_BLOCKS), dim3(256), 0, S_, p));
-  LAP_CHECK_LAUNCH();
-  return LAP_OK;
+  return lm_head_impl(state, sampling, true, x, gamma, hi, lo, nullptr, false, B, D, V, eps, logits, pval, pidx, stream);
 }
 
 extern "C" int lap_decode_finish(int* state, const float* pval, const int* pidx, int* out, int B, int cap, int eos_token,
@@ -655,4 +822,41 @@ extern "C" int lap_decode_finish(int* state, const float* pval, const int* pidx,
   hipLaunchKernelGGL(dec_finish_kernel, dim3(1), dim3(256), 0, S_, state, pval, pidx, LM_BLOCKS, out, cap, B, eos_token);
   LAP_CHECK_LAUNCH();
   return LAP_OK;
+}
+
+// ---- fp8 weight-only decoding: the entry points above on e4m3 codes [N][K] + f32 row scales [N] (2^e)
+extern "C" int lap_quantize_fp8_rows(const void* src, int src_f32, void* codes, float* scales, long long N, int K, void* stream) {
+  if (!src || !codes || !scales || N < 1 || N > 0x7fffffffLL || K < 4 || (K & 3) || ((uintptr_t)codes & 3)) return LAP_ERR_ARG;
+  const dim3 grid((unsigned)min(N, 1LL << 20));
+  if (src_f32) hipLaunchKernelGGL(quant_fp8_rows_kernel<float>, grid, dim3(256), 0, S_, (const float*)src, (uint8_t*)codes, scales, N, K);
+  else hipLaunchKernelGGL(quant_fp8_rows_kernel<bf16>, grid, dim3(256), 0, S_, (const bf16*)src, (uint8_t*)codes, scales, N, K);
+  LAP_CHECK_LAUNCH();
+  return LAP_OK;
+}
+
+extern "C" int lap_decode_qkv_fp8(const int* state, const void* x, const float* gamma, const void* wqkv8, const float* wscale, void* q,
+                                  void* cache_k, void* cache_v, int B, int D, int NH, int HD, int cap, float q_scale, float eps,
+                                  void* stream) {
+  return qkv_impl(state, x, gamma, wqkv8, wscale, true, q, cache_k, cache_v, B, D, NH, HD, cap, q_scale, eps, stream);
+}
+
+extern "C" int lap_decode_gate_up_fp8(const int* state, const void* x, const float* gamma, const void* wgu8, const float* wscale,
+                                      void* act, int B, int D, int H, float eps, void* stream) {
+  return gate_up_impl(state, x, gamma, wgu8, wscale, true, act, B, D, H, eps, stream);
+}
+
+extern "C" int lap_decode_proj_residual_fp8(const int* state, const void* a, const void* w8, const float* wscale, const void* x, void* y,
+                                            int B, int N, int K, int kwaves, void* stream) {
+  return proj_residual_impl(state, a, w8, wscale, true, x, y, B, N, K, kwaves, stream);
+}
+
+extern "C" int lap_decode_lm_head_fp8(const int* state, const void* x, const float* gamma, const void* w8, const float* wscale, int B,
+                                      int D, int V, float eps, float* logits, float* pval, int* pidx, void* stream) {
+  return lm_head_impl(state, nullptr, false, x, gamma, w8, nullptr, wscale, true, B, D, V, eps, logits, pval, pidx, stream);
+}
+
+extern "C" int lap_decode_lm_head_sample_fp8(const int* state, const int* sampling, const void* x, const float* gamma, const void* w8,
+                                             const float* wscale, int B, int D, int V, float eps, float* logits, float* pval, int* pidx,
+                                             void* stream) {
+  return lm_head_impl(state, sampling, true, x, gamma, w8, nullptr, wscale, true, B, D, V, eps, logits, pval, pidx, stream);
 }

@@ -213,6 +213,12 @@ SIGNATURES: dict[str, list] = {
     "lap_decode_finish": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "lap_decode_sampling_words": [],
     "lap_decode_lm_head_sample": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
+    "lap_quantize_fp8_rows": [_vp, _i, _vp, _vp, _ll, _i, _vp],
+    "lap_decode_qkv_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp],
+    "lap_decode_gate_up_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
+    "lap_decode_proj_residual_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "lap_decode_lm_head_fp8": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
+    "lap_decode_lm_head_sample_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
 }
 
 _fn = {}
@@ -1331,12 +1337,45 @@ def decode_embed(state, table, row_lo, row_hi, out, x, scale):
          float(scale))
 
 
-def decode_qkv(state, x, gamma, wqkv, q, cache_k, cache_v, NH, HD, q_scale, eps=1e-6):
-    """cache_k / cache_v: bf16 [B, cap, HD]."""
-    for t, n in ((x, "x"), (wqkv, "wqkv"), (q, "q"), (cache_k, "cache_k"), (cache_v, "cache_v")):
+def _f8req(w, wscale, name):
+    """An fp8 weight of the fused decode: e4m3 codes [N, K] (torch.float8_e4m3fn or its bytes as uint8) + f32 scales [N]."""
+    if w.dtype not in (torch.uint8, torch.float8_e4m3fn) or not w.is_cuda or not w.is_contiguous() or w.dim() != 2:
+        raise TypeError(f"{name}: expected contiguous cuda e4m3 codes [N, K] (float8_e4m3fn / uint8), got {w.device} {w.dtype}")
+    _dreq(wscale, torch.float32, name + " scales")
+    if wscale.numel() != w.shape[0]:
+        raise TypeError(f"{name}: {w.shape[0]} rows but {wscale.numel()} scales")
+
+
+def quantize_fp8_rows(w, codes=None, scales=None):
+    """w bf16 or f32 [N, K] -> (codes float8_e4m3fn [N, K], scales f32 [N] = 2^e) in the row format of lap_amd/fp8.py; `codes` /
+    `scales` given: written in place (the buffers a captured decode graph holds)."""
+    if w.dtype not in (torch.bfloat16, torch.float32) or not w.is_cuda or not w.is_contiguous() or w.dim() != 2:
+        raise TypeError(f"quantize_fp8_rows: expected a contiguous cuda bf16 / f32 matrix, got {w.device} {w.dtype} {tuple(w.shape)}")
+    N, K = w.shape
+    if codes is None:
+        codes = torch.empty((N, K), dtype=torch.float8_e4m3fn, device=w.device)
+    if scales is None:
+        scales = torch.empty((N,), dtype=torch.float32, device=w.device)
+    _f8req(codes, scales, "codes")
+    if tuple(codes.shape) != (N, K):
+        raise TypeError(f"quantize_fp8_rows: codes {tuple(codes.shape)} for a weight {(N, K)}")
+    call("lap_quantize_fp8_rows", _p(w), 1 if w.dtype == torch.float32 else 0, _p(codes), _p(scales), N, K)
+    return codes, scales
+
+
+def decode_qkv(state, x, gamma, wqkv, q, cache_k, cache_v, NH, HD, q_scale, eps=1e-6, wscale=None):
+    """cache_k / cache_v: bf16 [B, cap, HD].  wscale given: wqkv is e4m3 codes with these row scales (lap_decode_qkv_fp8); the
+    other decode_* projections and LM heads take an fp8 weight the same way."""
+    for t, n in ((x, "x"), (q, "q"), (cache_k, "cache_k"), (cache_v, "cache_v")):
         _dreq(t, torch.bfloat16, n)
     _dreq(gamma, torch.float32, "gamma")
     B, D = x.shape
+    if wscale is not None:
+        _f8req(wqkv, wscale, "wqkv")
+        call("lap_decode_qkv_fp8", _p(state), _p(x), _p(gamma), _p(wqkv), _p(wscale), _p(q), _p(cache_k), _p(cache_v), B, D, NH, HD,
+             cache_k.shape[1], float(q_scale), float(eps))
+        return
+    _dreq(wqkv, torch.bfloat16, "wqkv")
     call("lap_decode_qkv", _p(state), _p(x), _p(gamma), _p(wqkv), _p(q), _p(cache_k), _p(cache_v), B, D, NH, HD, cache_k.shape[1],
          float(q_scale), float(eps))
 
@@ -1350,29 +1389,47 @@ def decode_attention(state, q, prefix_k, prefix_v, kinfo, Pn, cache_k, cache_v, 
          cache_k.shape[1], _p(o), _p(scratch), scratch.numel(), B, NH, NKV, HD)
 
 
-def decode_proj_residual(state, a, w, x, y, kwaves=4):
-    for t, n in ((a, "a"), (w, "w"), (x, "x"), (y, "y")):
+def decode_proj_residual(state, a, w, x, y, kwaves=4, wscale=None):
+    for t, n in ((a, "a"), (x, "x"), (y, "y")):
         _dreq(t, torch.bfloat16, n)
     B, K = a.shape
+    if wscale is not None:
+        _f8req(w, wscale, "w")
+        call("lap_decode_proj_residual_fp8", _p(state), _p(a), _p(w), _p(wscale), _p(x), _p(y), B, w.shape[0], K, int(kwaves))
+        return
+    _dreq(w, torch.bfloat16, "w")
     call("lap_decode_proj_residual", _p(state), _p(a), _p(w), _p(x), _p(y), B, w.shape[0], K, int(kwaves))
 
 
-def decode_gate_up(state, x, gamma, wgu, act, eps=1e-6):
-    for t, n in ((x, "x"), (wgu, "wgu"), (act, "act")):
+def decode_gate_up(state, x, gamma, wgu, act, eps=1e-6, wscale=None):
+    for t, n in ((x, "x"), (act, "act")):
         _dreq(t, torch.bfloat16, n)
     _dreq(gamma, torch.float32, "gamma")
     B, D = x.shape
+    if wscale is not None:
+        _f8req(wgu, wscale, "wgu")
+        call("lap_decode_gate_up_fp8", _p(state), _p(x), _p(gamma), _p(wgu), _p(wscale), _p(act), B, D, act.shape[1], float(eps))
+        return
+    _dreq(wgu, torch.bfloat16, "wgu")
     call("lap_decode_gate_up", _p(state), _p(x), _p(gamma), _p(wgu), _p(act), B, D, act.shape[1], float(eps))
 
 
-def decode_lm_head(state, x, gamma, hi, lo, pval, pidx, logits=None, eps=1e-6):
-    """logits (debug): f32 [B, V] written when given."""
-    _dreq(x, torch.bfloat16, "x"); _dreq(hi, torch.bfloat16, "hi"); _dreq(gamma, torch.float32, "gamma")
-    if lo is not None:
-        _dreq(lo, torch.bfloat16, "lo")
+def decode_lm_head(state, x, gamma, hi, lo, pval, pidx, logits=None, eps=1e-6, wscale=None):
+    """logits (debug): f32 [B, V] written when given.  wscale given: `hi` is the one e4m3 code plane of the table, lo is None."""
+    _dreq(x, torch.bfloat16, "x"); _dreq(gamma, torch.float32, "gamma")
     if logits is not None:
         _dreq(logits, torch.float32, "logits")
     B, D = x.shape
+    if wscale is not None:
+        _f8req(hi, wscale, "hi")
+        if lo is not None:
+            raise TypeError("decode_lm_head: the fp8 table is one plane (lo must be None)")
+        call("lap_decode_lm_head_fp8", _p(state), _p(x), _p(gamma), _p(hi), _p(wscale), B, D, hi.shape[0], float(eps), _p(logits),
+             _p(pval), _p(pidx))
+        return
+    _dreq(hi, torch.bfloat16, "hi")
+    if lo is not None:
+        _dreq(lo, torch.bfloat16, "lo")
     call("lap_decode_lm_head", _p(state), _p(x), _p(gamma), _p(hi), _p(lo), B, D, hi.shape[0], float(eps), _p(logits), _p(pval),
          _p(pidx))
 
@@ -1393,17 +1450,25 @@ def decode_set_sampling(buf, seed, temperature):
     buf.copy_(torch.from_numpy(words))
 
 
-def decode_lm_head_sample(state, sampling, x, gamma, hi, lo, pval, pidx, logits=None, eps=1e-6):
+def decode_lm_head_sample(state, sampling, x, gamma, hi, lo, pval, pidx, logits=None, eps=1e-6, wscale=None):
     """`decode_lm_head` with the sampler of `sampling` (see `decode_sampling`) as its epilogue; logits (debug) stay raw."""
-    _dreq(x, torch.bfloat16, "x"); _dreq(hi, torch.bfloat16, "hi"); _dreq(gamma, torch.float32, "gamma")
+    _dreq(x, torch.bfloat16, "x"); _dreq(gamma, torch.float32, "gamma")
     _dreq(sampling, torch.int32, "sampling")
     if sampling.numel() < _fn["lap_decode_sampling_words"]():
         raise TypeError("sampling: int32 [lap_decode_sampling_words()]")
-    if lo is not None:
-        _dreq(lo, torch.bfloat16, "lo")
     if logits is not None:
         _dreq(logits, torch.float32, "logits")
     B, D = x.shape
+    if wscale is not None:
+        _f8req(hi, wscale, "hi")
+        if lo is not None:
+            raise TypeError("decode_lm_head_sample: the fp8 table is one plane (lo must be None)")
+        call("lap_decode_lm_head_sample_fp8", _p(state), _p(sampling), _p(x), _p(gamma), _p(hi), _p(wscale), B, D, hi.shape[0],
+             float(eps), _p(logits), _p(pval), _p(pidx))
+        return
+    _dreq(hi, torch.bfloat16, "hi")
+    if lo is not None:
+        _dreq(lo, torch.bfloat16, "lo")
     call("lap_decode_lm_head_sample", _p(state), _p(sampling), _p(x), _p(gamma), _p(hi), _p(lo), B, D, hi.shape[0], float(eps),
          _p(logits), _p(pval), _p(pidx))
 

@@ -108,6 +108,7 @@ class LAP:
         # unsplit tiles they replace.  LAP_SERVE_PANEL=0: the LDS-tiled kernels (A/B runs, tests)
         self.serve_panel = os.environ.get("LAP_SERVE_PANEL", "1") != "0"
         self._prefill_pw: dict = {}     # name -> [version, packed image]
+        self._dec_w8: dict = {}         # name -> [version, e4m3 codes, row scales]: the fused decoder's fp8 weights (`_dec_fp8`)
         # the prefill's fused GELU / GeGLU epilogues (SigLIP fc1 on the panel kernel, Gemma's gate|up tile) through v_exp / v_rcp, the training
         # kernels' arithmetic; "bf16": tanhf (A/B)
         self._panel_gelu = os.environ.get("LAP_SERVE_PANEL_GELU", "exp2")
@@ -1611,6 +1612,21 @@ class LAP:
             self._prefill_pw[name] = rec = [self.ps.version, img]
         return rec[1]
 
+    def _dec_fp8(self, name):
+        """(e4m3 codes [N, K], f32 row scales [N]) of a weight of the fused decoder in the format of lap_amd/fp8.py: persistent
+        like `_serve_packed_weights`, built on first use and re-quantised IN PLACE per parameter version (a captured decoder
+        holds both addresses).  The layer projections are quantised from the bf16 weight `W(name)` the bf16 decoder reads (the
+        merged one under `_serving_weights`), the LM head from the f32 embedding table.  +1 byte per weight on top of the bf16
+        copies the prefill keeps: 2.0 GB for LAP-3B's 18 layers, 0.53 GB for the table."""
+        rec = self._dec_w8.get(name)
+        if rec is None or rec[0] != self.ps.version:
+            if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("serving caches are stale inside a stream capture: call refresh_serve_caches() first")
+            src = self.F(name) if name == "llm/embed" else self.W(name)
+            codes, scales = hip.quantize_fp8_rows(src, *(() if rec is None else rec[1:]))
+            self._dec_w8[name] = rec = [self.ps.version, codes, scales]
+        return rec[1], rec[2]
+
     def _time_grid(self, num_steps: int):
         dt = -1.0 / num_steps
         n, t = 0, 1.0
@@ -1620,8 +1636,8 @@ class LAP:
         return n, dt
 
     def refresh_serve_caches(self, num_steps: int = 10):
-        """Bring the sampler's parameter-derived caches (merged LoRA weights, adaRMS modulations, packed expert weights) up to the
-        current parameter version, in place.  Eager `sample_actions` does this itself; a captured graph cannot — call it before a replay."""
+        """Bring the sampler's parameter-derived caches (merged LoRA weights, the fused decoder's fp8 weights, adaRMS modulations,
+        packed expert weights) up to the current parameter version, in place.  Eager `sample_actions` does this itself; a captured graph cannot — call it before a replay."""
         with self._serving_weights():
             self._refresh_serve_caches(num_steps)
 
@@ -1629,6 +1645,9 @@ class LAP:
         for name in list(self._merged_w):      # (first: the packed images below are made from them)
             self.comm.wait_unit("llm" + name.split("/")[1])
             self._merged(name)
+        for name in list(self._dec_w8):        # (after the merged weights they are quantised from)
+            self.comm.wait_unit("embed" if name == "llm/embed" else "llm" + name.split("/")[1])
+            self._dec_fp8(name)
         n, dt = self._time_grid(num_steps)
         for name in list(self._prefill_pw):
             kind, l = name.split("/")[:2]
@@ -1684,7 +1703,7 @@ class LAP:
         return lg
 
     def sample_tokens(self, rng, observation, *, max_decoding_steps: int = 390, temperature: float = 0.0, collect=None,
-                      decode: str = "eager", sampler: str = "host"):
+                      decode: str = "eager", sampler: str = "host", decode_weights: str = "bf16"):
         """lap.py:678-766 (LAP_AR serving mode): VLM-only prefill, then single-token decode until every sample has emitted
         EOS or `max_decoding_steps` tokens; returns int32 [B, max_decoding_steps] (zeros after the stop).
 
@@ -1712,9 +1731,19 @@ class LAP:
         epilogue of the fused LM head (lap_decode_lm_head_sample), where no logit is stored.  The two decode modes then draw
         from the same noise and differ in summation order only, and `sampling.sample_from_logits(collect["logit/<t>"],
         temperature, rng, t)` reproduces a draw offline.  temperature <= 0 is greedy under either sampler, bit for bit the same.
-        `collect` keeps the raw logits under sampler="device" (under "host" it holds what the argmax saw, as before)."""
+        `collect` keeps the raw logits under sampler="device" (under "host" it holds what the argmax saw, as before).
+
+        decode_weights: what the fused decode steps stream.  "bf16" (default): the bf16 weights, as before.  "fp8": e4m3 codes
+        with one power-of-two scale per output feature (lap_amd/fp8.py) for the four projections of every layer and for the LM
+        head, half and a quarter of the bytes; "fp8_layers": the projections only, the LM head stays on the hi / lo bf16 planes
+        of the f32 table (its precision decides greedy near-ties).  The kernels compute what the bf16 ones compute on the
+        dequantised weights; the prefill and the embedding gather are unchanged.  The fp8 copies are cached on the model and
+        follow the parameters (`refresh_serve_caches`).  Needs decode="fused"."""
         if decode not in ("eager", "fused"):
             raise ValueError(f"sample_tokens: decode must be 'eager' or 'fused', got {decode!r}")
+        self._check_decode_weights(decode_weights)
+        if decode_weights != "bf16" and decode != "fused":
+            raise ValueError(f"sample_tokens: decode_weights={decode_weights!r} runs on the fused decode kernels only: pass decode=\"fused\"")
         if sampler not in ("host", "device"):
             raise ValueError(f"sample_tokens: sampler must be 'host' or 'device', got {sampler!r}")
         if decode == "fused":
@@ -1724,9 +1753,13 @@ class LAP:
         with self._serving_weights():
             if decode == "fused" and sampler == "device":
                 return self._sample_tokens_fused(observation, max_decoding_steps=max_decoding_steps, collect=collect,
-                                                 sampling=(rng, temperature))
+                                                 sampling=(rng, temperature), weights=decode_weights)
             if decode == "fused" and temperature <= 0.0:
-                return self._sample_tokens_fused(observation, max_decoding_steps=max_decoding_steps, collect=collect)
+                return self._sample_tokens_fused(observation, max_decoding_steps=max_decoding_steps, collect=collect,
+                                                 weights=decode_weights)
+            if decode_weights != "bf16":
+                raise ValueError("sample_tokens: decode_weights other than 'bf16' with temperature > 0 needs sampler='device' (the "
+                                 "host sampler keeps the eager loop)")
             return self._sample_tokens(rng, observation, max_decoding_steps=max_decoding_steps, temperature=temperature, collect=collect,
                                        device_sampler=sampler == "device")
 
@@ -1804,8 +1837,23 @@ class LAP:
             raise ValueError(f"fused decode serves the Gemma-2B widths at 1 <= B <= 8 (D 2048, 8 / 1 heads of 256, MLP 16384); got "
                              f"B {B}, D {v.width}, heads {v.num_heads} / {v.num_kv_heads} of {v.head_dim}, MLP {v.mlp_dim}")
 
-    def _decode_ctx(self, B: int, Pn: int, cap: int, sampling: bool = False):
-        return _DecodeCtx(self, B, Pn, cap, sampling)
+    DECODE_WEIGHTS = ("bf16", "fp8", "fp8_layers")
+
+    @classmethod
+    def _check_decode_weights(cls, weights):
+        if weights not in cls.DECODE_WEIGHTS:
+            raise ValueError(f"decode_weights must be one of {cls.DECODE_WEIGHTS}, got {weights!r}")
+
+    def _decode_ctx(self, B: int, Pn: int, cap: int, sampling: bool = False, weights: str = "bf16"):
+        self._check_decode_weights(weights)
+        return _DecodeCtx(self, B, Pn, cap, sampling, weights)
+
+    def _dec_w(self, ctx, name):
+        """A layer projection as the fused step of `ctx` streams it: (weight, {}) or (e4m3 codes, {"wscale": row scales})."""
+        if ctx.weights == "bf16":
+            return self.W(name), {}
+        codes, scales = self._dec_fp8(name)
+        return codes, {"wscale": scales}
 
     def _fused_first_token(self, ctx, pre, logits=None):
         """Reset the device state for the prefill `pre` (from `_ar_prefill`) and decode the first token from its last rows."""
@@ -1818,12 +1866,15 @@ class LAP:
     def _fused_token(self, ctx, x, logits=None):
         """final norm + LM head over the hi / lo planes + argmax -> out[:, t], EOS mask, t + 1 (lap.py:716-724).  A context
         with sampling words runs the sampling LM head, which is the greedy one while the words hold inv_t = 0."""
-        if ctx.sampling is not None:
-            hip.decode_lm_head_sample(ctx.state, ctx.sampling, x, self.F("llm/final_norm"), self.W("llm/embed"),
-                                      self.ps.w16lo("llm/embed"), ctx.pval, ctx.pidx, logits)
+        if ctx.weights == "fp8":         # one e4m3 plane of the f32 table
+            hi, scales = self._dec_fp8("llm/embed")
+            lo, kw = None, {"wscale": scales}
         else:
-            hip.decode_lm_head(ctx.state, x, self.F("llm/final_norm"), self.W("llm/embed"), self.ps.w16lo("llm/embed"), ctx.pval,
-                               ctx.pidx, logits)
+            hi, lo, kw = self.W("llm/embed"), self.ps.w16lo("llm/embed"), {}
+        if ctx.sampling is not None:
+            hip.decode_lm_head_sample(ctx.state, ctx.sampling, x, self.F("llm/final_norm"), hi, lo, ctx.pval, ctx.pidx, logits, **kw)
+        else:
+            hip.decode_lm_head(ctx.state, x, self.F("llm/final_norm"), hi, lo, ctx.pval, ctx.pidx, logits, **kw)
         hip.decode_finish(ctx.state, ctx.pval, ctx.pidx, ctx.out, self.EOS_TOKEN)
 
     def _fused_step(self, ctx, logits=None):
@@ -1835,19 +1886,23 @@ class LAP:
         for l in range(v.depth):
             p = f"llm/{l}/"
             gk, gv = ctx.gen[l, 0], ctx.gen[l, 1]
-            hip.decode_qkv(ctx.state, ctx.x, self.F(p + "n_attn"), self.W(p + "wqkv0"), ctx.q, gk, gv, NH, HD, HD ** -0.5)
+            w, kw = self._dec_w(ctx, p + "wqkv0")
+            hip.decode_qkv(ctx.state, ctx.x, self.F(p + "n_attn"), w, ctx.q, gk, gv, NH, HD, HD ** -0.5, **kw)
             ck, cv = ctx.prefix[l]
             hip.decode_attention(ctx.state, ctx.q, ck, cv, ctx.kinfo, ctx.Pn, gk, gv, ctx.o, ctx.attn_scratch, NH, KV, HD)
-            hip.decode_proj_residual(ctx.state, ctx.o, self.W(p + "wo0"), ctx.x, ctx.xa)
-            hip.decode_gate_up(ctx.state, ctx.xa, self.F(p + "n_ffw"), self.W(p + "wgu0"), ctx.act)
-            hip.decode_proj_residual(ctx.state, ctx.act, self.W(p + "wd0"), ctx.xa, ctx.x, kwaves=hip.DECODE_KWAVES_DOWN)
+            w, kw = self._dec_w(ctx, p + "wo0")
+            hip.decode_proj_residual(ctx.state, ctx.o, w, ctx.x, ctx.xa, **kw)
+            w, kw = self._dec_w(ctx, p + "wgu0")
+            hip.decode_gate_up(ctx.state, ctx.xa, self.F(p + "n_ffw"), w, ctx.act, **kw)
+            w, kw = self._dec_w(ctx, p + "wd0")
+            hip.decode_proj_residual(ctx.state, ctx.act, w, ctx.xa, ctx.x, kwaves=hip.DECODE_KWAVES_DOWN, **kw)
         self._fused_token(ctx, ctx.x, logits)
 
-    def _sample_tokens_fused(self, observation, *, max_decoding_steps: int, collect=None, sampling=None):
-        """sampling: None (the greedy LM head) or (seed, temperature) for the sampling LM head."""
+    def _sample_tokens_fused(self, observation, *, max_decoding_steps: int, collect=None, sampling=None, weights: str = "bf16"):
+        """sampling: None (the greedy LM head) or (seed, temperature) for the sampling LM head.  weights: `decode_weights`."""
         pre = self._ar_prefill(observation)
         B, Pn = pre[0], pre[1]
-        ctx = self._decode_ctx(B, Pn, max_decoding_steps, sampling is not None)
+        ctx = self._decode_ctx(B, Pn, max_decoding_steps, sampling is not None, weights)
         if sampling is not None:
             ctx.set_sampling(*sampling)
         lg = torch.empty((B, self.config.vocab_size), dtype=torch.float32, device=self.device) if collect is not None else None
@@ -1872,8 +1927,9 @@ class _DecodeCtx:
     the fixed-capacity generated K/V cache of every layer ([depth, 2, B, cap, head_dim] bf16, 7.2 MB per sample at 390 steps
     for LAP-3B) and the step's activations.  The prefix K/V cache and kinfo come from the prefill (`bind`)."""
 
-    def __init__(self, model: LAP, B: int, Pn: int, cap: int, sampling: bool = False):
+    def __init__(self, model: LAP, B: int, Pn: int, cap: int, sampling: bool = False, weights: str = "bf16"):
         v = model.v
+        self.weights = weights          # what the steps stream: "bf16", "fp8" (projections + LM head) or "fp8_layers"
         dev = model.device
         bf = torch.bfloat16
         self.B, self.Pn, self.cap = B, Pn, cap

@@ -83,11 +83,17 @@ class GraphedTokenDecoder:
     sampling=True captures both graphs on the sampling LM head (`sample_tokens(decode="fused", sampler="device")`): the seed and
     the temperature of a call are four device words that `__call__(obs, temperature=, seed=)` rewrites before the first replay,
     so one capture serves greedy and sampled requests of any seed and temperature, with no further host read.  A greedy call
-    returns what the sampling=False decoder returns, bit for bit."""
+    returns what the sampling=False decoder returns, bit for bit.
+
+    weights: `sample_tokens`' `decode_weights` ("bf16", "fp8", "fp8_layers"): the step graph is captured on the fp8 kernels and
+    holds the addresses of the model's fp8 weight cache, which `refresh_serve_caches` re-quantises in place before a replay
+    when the parameters have changed.  Composes with sampling=True."""
 
     def __init__(self, model: LAP, batch_size: int = 1, max_decoding_steps: int = 390, prompt_len: int | None = None,
-                 steps_per_replay: int = 8, sampling: bool = False):
+                 steps_per_replay: int = 8, sampling: bool = False, weights: str = "bf16"):
         model._check_fused_decode(batch_size)
+        model._check_decode_weights(weights)
+        self.weights = weights
         if max_decoding_steps < 1 or steps_per_replay < 1:
             raise ValueError("max_decoding_steps and steps_per_replay must be >= 1")
         self.model, self.B, self.max_steps, self.spr = model, batch_size, max_decoding_steps, steps_per_replay
@@ -127,7 +133,7 @@ class GraphedTokenDecoder:
         m = self.model
         pre = m._ar_prefill(self.obs)
         if self.ctx is None:
-            self.ctx = m._decode_ctx(self.B, pre[1], self.max_steps, self.sampling)
+            self.ctx = m._decode_ctx(self.B, pre[1], self.max_steps, self.sampling, self.weights)
         m._fused_first_token(self.ctx, pre)
 
     def _steps(self):
@@ -165,7 +171,7 @@ class GraphedTokenDecoder:
             raise ValueError("GraphedTokenDecoder: temperature > 0 needs a decoder built with sampling=True")
         if self.g_step is None:
             self.capture()
-        # merged LoRA weights / packed prefill images the graphs hold addresses of follow the parameters in place
+        # merged LoRA weights / fp8 decode weights / packed prefill images the graphs hold addresses of follow the parameters in place
         self.model.refresh_serve_caches()
         self._load(obs)
         if self.sampling:
@@ -327,9 +333,16 @@ class ARPolicy:
         if self._sample_kwargs.get("sampler", "host") not in ("host", "device"):
             raise ValueError(f"ARPolicy: sampler must be 'host' or 'device', got {self._sample_kwargs['sampler']!r}")
         self._device_sampler = self._sample_kwargs.get("sampler", "host") == "device"
+        # sample_kwargs["decode_weights"] ("fp8" / "fp8_layers") reaches both routes: the decoder is captured on those weights,
+        # and sample_tokens gets decode="fused" with it (the fp8 kernels are fused decode kernels), so both decode on the same weights
+        weights = self._sample_kwargs.get("decode_weights", "bf16")
+        base.model._check_decode_weights(weights)
+        if weights != "bf16":
+            if self._sample_kwargs.setdefault("decode", "fused") != "fused":
+                raise ValueError(f"ARPolicy: decode_weights={weights!r} needs decode=\"fused\", got {self._sample_kwargs['decode']!r}")
         if use_graph and base.model.decode_supported(1):
             self._decoder = GraphedTokenDecoder(base.model, 1, self._sample_kwargs.get("max_decoding_steps", 390),
-                                                sampling=self._device_sampler)
+                                                sampling=self._device_sampler, weights=weights)
 
     def __getattr__(self, name):
         return getattr(self._base, name)
@@ -372,7 +385,8 @@ def create_trained_policy_ar(*args, sample_kwargs: dict | None = None, language_
     one delta, output_transforms.py:75-104; `Unnormalize` has no `actions` statistics to apply to such deltas and is left out
     as in the reference's standard stack it would act on the normalised `state` only).
     ar_graph: serve greedy requests through a GraphedTokenDecoder (ARPolicy(use_graph=True)); off by default.  With
-    sample_kwargs={"temperature": T, "sampler": "device"} the same graphs serve sampled requests too."""
+    sample_kwargs={"temperature": T, "sampler": "device"} the same graphs serve sampled requests too;
+    sample_kwargs={"decode_weights": "fp8" | "fp8_layers"} decodes on fp8 weights (implies decode="fused") on either route."""
     from lap_amd import policy_io as pio
 
     base = create_trained_policy(*args, use_graph=False, **kwargs)

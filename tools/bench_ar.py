@@ -3,11 +3,15 @@
 rate against the 6.29 TB/s measured copy rate.  Random weights, the reference prompt shape, greedy, EOS disabled so that every
 run decodes N tokens.  One JSON line.
 
-    python tools/bench_ar.py [--tokens 64] [--config lap_bench] [--kwaves 4] [--temperature T]
+    python tools/bench_ar.py [--tokens 64] [--config lap_bench] [--kwaves 4] [--temperature T] [--weights bf16 fp8 fp8_layers]
 
 --temperature T > 0 adds the sampled figures: the eager loop with the torch-generator noise (sampler="host"), the eager loop and
 the fused steps with the device noise (sampler="device"), and a GraphedTokenDecoder(sampling=True) called sampled and greedy.
 --profile-graphed --temperature T replays one sampled decode on the sampling graphs instead of the greedy one.
+--weights: the bf16 figures are always measured; every other value named (fp8, fp8_layers: `sample_tokens(decode_weights=)`) adds,
+side by side and in the same process, its fused and graphed ms per token, its bytes per token and achieved rate, how many of the
+graphed tokens agree with the bf16 graph's, and the relative error of its first and second tokens' logits against bf16's.
+--profile-graphed replays the graph of the LAST value named.
 """
 import argparse
 import json
@@ -30,6 +34,8 @@ ap.add_argument("--kwaves", type=int, default=hip.DECODE_KWAVES_DOWN, help="K sp
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--profile-graphed", action="store_true", help="capture, replay one graphed decode and exit (for rocprofv3)")
 ap.add_argument("--temperature", type=float, default=0.0, help="> 0: also measure sampled decoding at this temperature")
+ap.add_argument("--weights", nargs="+", default=["bf16"], choices=list(LAP.DECODE_WEIGHTS),
+                help="decode weights to measure next to bf16 (fp8, fp8_layers)")
 a = ap.parse_args()
 hip.DECODE_KWAVES_DOWN = a.kwaves
 
@@ -59,8 +65,10 @@ def timeit(fn, n):
 T = a.temperature
 if a.profile_graphed:
     if T > 0.0:
-        sdec = GraphedTokenDecoder(model, 1, N, sampling=True)
+        sdec = GraphedTokenDecoder(model, 1, N, sampling=True, weights=a.weights[-1])
         sdec(o, temperature=T, seed=1)
+    elif a.weights[-1] != "bf16":
+        GraphedTokenDecoder(model, 1, N, weights=a.weights[-1])(o)
     else:
         dec(o)
     torch.cuda.synchronize()
@@ -81,6 +89,25 @@ head = model.W("llm/embed").numel() * 2 * (2 if model.ps.w16lo("llm/embed") is n
 bytes_tok = v.depth * layer + head
 per = lambda t, t0: (t - t0) / (N - 1)
 g_ms = per(t_graph, t_gpre)
+quant = {}
+for wname in dict.fromkeys(w for w in a.weights if w != "bf16"):
+    qdec = GraphedTokenDecoder(model, 1, N, weights=wname).capture()
+    t_qpre = timeit(lambda: (qdec.g_prefill.replay()), a.reps)
+    t_qgraph = timeit(lambda: qdec(o), a.reps)
+    t_qfused = timeit(lambda: model.sample_tokens(0, o, max_decoding_steps=N, decode="fused", decode_weights=wname), a.reps)
+    qgot = qdec(o)
+    c16, c8 = {}, {}
+    model.sample_tokens(0, o, max_decoding_steps=2, decode="fused", collect=c16)
+    model.sample_tokens(0, o, max_decoding_steps=2, decode="fused", decode_weights=wname, collect=c8)
+    q_bytes = v.depth * layer // 2 + (head // 4 if wname == "fp8" else head)
+    q_ms = per(t_qgraph, t_qpre)
+    quant[wname] = {
+        "fused_ms_per_token": round(per(t_qfused, t_pre), 3), "graphed_ms_per_token": round(q_ms, 3),
+        "graphed_speedup_vs_bf16": round(g_ms / q_ms, 3), "algorithmic_bytes_per_token": q_bytes,
+        "achieved_GBps_graphed": round(q_bytes / (q_ms * 1e-3) / 1e9, 1), "share_of_6.29TBps": round(q_bytes / (q_ms * 1e-3) / 6.29e12, 3),
+        "tokens_equal_to_bf16_graph": int((qgot == got).sum()), "leading_tokens_equal_to_bf16_graph": int((qgot == got).cumprod(1).sum()),
+        "first_token_logit_rel_err_vs_bf16": round(float((c8["logit/0"] - c16["logit/0"]).norm() / c16["logit/0"].norm()), 5),
+        "second_token_logit_rel_err_vs_bf16": round(float((c8["logit/1"] - c16["logit/1"]).norm() / c16["logit/1"].norm()), 5)}
 sampled = {}
 if T > 0.0:
     st = lambda **kw: (lambda: model.sample_tokens(1, o, max_decoding_steps=N, temperature=T, **kw))
@@ -110,4 +137,4 @@ print(json.dumps({
     "graphed_vs_eager_leading_tokens_equal": agree, "graphed_equals_eager": bool(torch.equal(got, eager)),
     "algorithmic_bytes_per_token": bytes_tok, "floor_ms_per_token_at_6.29TBps": round(bytes_tok / 6.29e12 * 1e3, 3),
     "achieved_GBps_graphed": round(bytes_tok / (g_ms * 1e-3) / 1e9, 1),
-    "share_of_6.29TBps": round(bytes_tok / (g_ms * 1e-3) / 6.29e12, 3), "down_proj_kwaves": a.kwaves} | sampled))
+    "share_of_6.29TBps": round(bytes_tok / (g_ms * 1e-3) / 6.29e12, 3), "down_proj_kwaves": a.kwaves} | sampled | ({"weights": quant} if quant else {})))
