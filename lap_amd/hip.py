@@ -670,9 +670,10 @@ def attention_set_variant(variant: int):
 
 
 def attention_fwd(q, k, v, q_len, k_len, B, NH, NKV, HD, qinfo=None, kinfo=None, need_lse=True, scale=1.0,
-                  q_rs=(0, 0), kv_rs=(0, 0), nsplit_hint=None):
+                  q_rs=(0, 0), kv_rs=(0, 0), nsplit_hint=None, o_out=None, lse_out=None):
     """q/k/v: lists of up to two segment tensors (None for an empty segment).  q_rs / kv_rs: row strides in
-    elements when q / k / v are column slices of a wider (fused qkv) buffer; outputs are packed [B*len, NH*HD]."""
+    elements when q / k / v are column slices of a wider (fused qkv) buffer; outputs are packed [B*len, NH*HD].
+    o_out (a list of packed bf16 [B*len, NH*HD] per segment) / lse_out (f32 [B, NH, Tq]): write into the caller's buffers."""
     a = AttnFwdArgs()
     outs = []
     for s in range(2):
@@ -681,7 +682,10 @@ def attention_fwd(q, k, v, q_len, k_len, B, NH, NKV, HD, qinfo=None, kinfo=None,
         a.q_rs[s], a.kv_rs[s], a.o_rs[s] = q_rs[s], kv_rs[s], 0
         o = None
         if qs is not None:
-            o = torch.empty((B * q_len[s], NH * HD), dtype=torch.bfloat16, device=qs.device)
+            o = torch.empty((B * q_len[s], NH * HD), dtype=torch.bfloat16, device=qs.device) if o_out is None else \
+                (o_out[s] if s < len(o_out) else None)
+            if o is None or o.shape != (B * q_len[s], NH * HD) or o.dtype != torch.bfloat16 or not o.is_contiguous():
+                raise TypeError("o_out must hold packed bf16 [B*len, NH*HD] tensors")
         outs.append(o)
         a.o[s] = _p(o)
         a.k[s] = _p(k[s]) if s < len(k) and k[s] is not None else None
@@ -693,7 +697,11 @@ def attention_fwd(q, k, v, q_len, k_len, B, NH, NKV, HD, qinfo=None, kinfo=None,
             raise TypeError(f"{nm} must be a contiguous int32 tensor, got {inf.dtype}")
     Tq = a.q_len[0] + a.q_len[1]
     dev = next(t for t in q if t is not None).device
-    lse = torch.empty((B, NH, Tq), dtype=torch.float32, device=dev) if need_lse else None
+    lse = None
+    if need_lse:
+        lse = lse_out if lse_out is not None else torch.empty((B, NH, Tq), dtype=torch.float32, device=dev)
+        if lse.shape != (B, NH, Tq) or lse.dtype != torch.float32 or not lse.is_contiguous():
+            raise TypeError("lse_out must be a contiguous f32 [B, NH, Tq] tensor")
     a.qinfo, a.kinfo, a.lse = _p(qinfo), _p(kinfo), _p(lse)
     a.scale = float(scale)
     a.B, a.NH, a.NKV, a.HD = B, NH, NKV, HD
