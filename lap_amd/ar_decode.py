@@ -1,0 +1,285 @@
+"""LAP_AR token decoding (lap.py:678-766) behind `LAP.sample_tokens`: the VLM-only prefill, the eager decode step on generic
+launches, the fused step on the single-token kernels of csrc/decode.hip with its device-side state (`DecodeCtx`), and the routing
+between them.  `serve.GraphedTokenDecoder` captures `prefill` + `DecodeCtx.first_token` and `DecodeCtx.step` into two graphs.
+The weights are read through the model (`W`, `F`, `_dec_fp8`), as `LAP._serving_weights` presents them.
+"""
+from __future__ import annotations
+
+import math
+from typing import NamedTuple
+
+import torch
+
+from lap_amd import hip
+from lap_amd.model import LAP, _gen
+from lap_amd.observation import preprocess_observation
+
+DECODE_STEPS_PER_CHECK = 8      # fused steps between two host reads of the device stop flag (eager `decode="fused"`)
+
+
+def check_fused_decode(model: LAP, B: int):
+    if model.comm.world_size != 1:
+        raise ValueError("fused decode is a serving path: replicas only (world_size 1)")
+    if not model.decode_supported(B):
+        v = model.v
+        raise ValueError(f"fused decode serves the Gemma-2B widths at 1 <= B <= 8 (D 2048, 8 / 1 heads of 256, MLP 16384); got "
+                         f"B {B}, D {v.width}, heads {v.num_heads} / {v.num_kv_heads} of {v.head_dim}, MLP {v.mlp_dim}")
+
+
+def check_decode_weights(weights):
+    if weights not in LAP.DECODE_WEIGHTS:
+        raise ValueError(f"decode_weights must be one of {LAP.DECODE_WEIGHTS}, got {weights!r}")
+
+
+def sample_tokens(model: LAP, rng, observation, *, max_decoding_steps: int = 390, temperature: float = 0.0, collect=None,
+                  decode: str = "eager", sampler: str = "host", decode_weights: str = "bf16"):
+    """`LAP.sample_tokens` (documented there): every argument is checked before any device work."""
+    if decode not in ("eager", "fused"):
+        raise ValueError(f"sample_tokens: decode must be 'eager' or 'fused', got {decode!r}")
+    check_decode_weights(decode_weights)
+    if decode_weights != "bf16" and decode != "fused":
+        raise ValueError(f"sample_tokens: decode_weights={decode_weights!r} runs on the fused decode kernels only: pass decode=\"fused\"")
+    if sampler not in ("host", "device"):
+        raise ValueError(f"sample_tokens: sampler must be 'host' or 'device', got {sampler!r}")
+    if decode == "fused":
+        check_fused_decode(model, observation.tokenized_prompt.shape[0])
+    if sampler == "device":
+        hip.sampling_words(rng, temperature)        # (rejects a temperature whose inverse is not finite before any work)
+    with model._serving_weights():
+        if decode == "fused" and (sampler == "device" or temperature <= 0.0):   # (the host sampler's noise cannot run on the device state)
+            return _sample_fused(model, observation, max_decoding_steps=max_decoding_steps, collect=collect,
+                                 sampling=(rng, temperature) if sampler == "device" else None, weights=decode_weights)
+        if decode_weights != "bf16":
+            raise ValueError("sample_tokens: decode_weights other than 'bf16' with temperature > 0 needs sampler='device' (the "
+                             "host sampler keeps the eager loop)")
+        return _sample_eager(model, rng, observation, max_decoding_steps=max_decoding_steps, temperature=temperature, collect=collect,
+                             device_sampler=sampler == "device")
+
+
+class Prefill(NamedTuple):
+    """What the VLM-only prefill leaves for the decode steps."""
+    B: int
+    Pn: int
+    cache: list                     # prefix K/V per layer
+    kinfo_prefix: torch.Tensor      # [B, Pn]
+    qinfo_d: torch.Tensor           # qinfo of the decode query
+    plen: torch.Tensor              # [B] prefill_len
+    x_last: torch.Tensor            # [B, D] the last valid residual row of every sample
+
+
+def prefill(model: LAP, observation) -> Prefill:
+    """The VLM-only prefill of sample_tokens (lap.py:693-716)."""
+    cfg = model.config
+    dev = model.device
+    if model.comm.world_size != 1:
+        raise NotImplementedError("sample_tokens is a serving path: replicas only (SURVEY.md §8e)")
+    model.comm.wait_unit("small")
+    obs = preprocess_observation(observation, train=False, image_keys=cfg.image_keys, image_resolution=cfg.image_resolution)
+    B = obs.tokenized_prompt.shape[0]
+    x0, Pn, _ = model._embed_prefix(obs, False, serve=True)
+    qinfo_p, kinfo_p, ppos = model._serve_infos(obs, 1)[:3]
+    prefix_mask, _ = model._prefix_masks(obs)
+    ar = torch.arange(Pn, device=dev)
+    seqlen = (prefix_mask.to(torch.int64) * ar).max(-1).values + 1          # left_to_right_align's roll amount
+    plen = prefix_mask.sum(-1)                                               # prefill_len
+    in_range = (ar[None] >= (seqlen - plen)[:, None]) & (ar[None] < seqlen[:, None])
+    kinfo_prefix = (in_range.to(torch.int32) << 24).contiguous()
+    qinfo_d = torch.full((B, 1), (1 << 24) | 0xFFFFFF, dtype=torch.int32, device=dev)
+    cache = []
+    if model.serve_fusions and model.gemm_dtype == "bf16":
+        xf0 = model._llm_prefill(x0, ppos, qinfo_p, kinfo_p, B, Pn, cache)
+    else:
+        xf0, _, _ = model._llm_fwd(x0, None, None, ppos, qinfo_p, kinfo_p, B, Pn, 0, False, cache_out=cache)
+    last = (torch.arange(B, device=dev) * Pn + seqlen - 1)
+    return Prefill(B, Pn, cache, kinfo_prefix, qinfo_d, plen, xf0.index_select(0, last).contiguous())
+
+
+# ---- the eager step: generic launches
+def _vlm_decode_step(model: LAP, token, pos, step, cache, gen, qinfo_d, kinfo_prefix, B, Pn):
+    """One expert-0 decode step (lap.py:734-752): embed the sampled token, run the 18 VLM layers on that single row
+    per sample with keys = [prefilled prefix cache | generated tokens incl. this one], return f32 logits [B, V].
+    The reference appends into a fixed-size cache by index (gemma.py:597-605); here the generated keys are a second
+    key segment that grows by one row per step."""
+    v = model.v
+    NH, HD, KV, Dv = v.num_heads, v.head_dim, v.num_kv_heads, v.width
+    dev = model.device
+    x = torch.empty((B, Dv), dtype=torch.bfloat16, device=dev)
+    rows, lo, hi = model.ps.embed_rows()
+    hip.embed_gather(rows, token.view(B, 1).contiguous(), x, B, 1, Dv, 1, 0, math.sqrt(Dv), lo, hi)
+    kinfo = torch.cat([kinfo_prefix, torch.full((B, step + 1), 1 << 24, dtype=torch.int32, device=dev)], 1).contiguous()
+    for l in range(v.depth):
+        p = f"llm/{l}/"
+        h, _ = hip.rmsnorm_fwd(x, scale=model.F(p + "n_attn"), save_rstd=False)
+        qkv = hip.linear_fwd(h, model.W(p + "wqkv0"))
+        q, k, vv = hip.rope_split_fwd(qkv, pos, B, 1, 1, 0, NH, HD, HD ** -0.5)
+        gk, gv = gen[l]
+        gk = k.view(B, 1, -1) if gk is None else torch.cat([gk, k.view(B, 1, -1)], 1)
+        gv = vv.view(B, 1, -1) if gv is None else torch.cat([gv, vv.view(B, 1, -1)], 1)
+        gen[l] = (gk, gv)
+        ck, cv = cache[l]
+        o, _ = hip.attention_fwd([None, q], [ck, gk.view(B * (step + 1), -1)], [cv, gv.view(B * (step + 1), -1)], [0, 1],
+                                 [Pn, step + 1], B, NH, KV, HD, qinfo_d, kinfo, need_lse=False)
+        xa = hip.linear_fwd(o[1], model.W(p + "wo0"), residual=x)
+        hf, _ = hip.rmsnorm_fwd(xa, scale=model.F(p + "n_ffw"), save_rstd=False)
+        act = hip.geglu_fwd(hip.linear_fwd(hf, model.W(p + "wgu0")))
+        x = hip.linear_fwd(act, model.W(p + "wd0"), residual=xa)
+    return _lm_logits(model, x)
+
+
+def _lm_logits(model: LAP, rows):
+    """final norm + Embedder.decode (gemma.py:153-154, 525-527): f32 logits [R, V]."""
+    pl, _ = hip.rmsnorm_fwd(rows, scale=model.F("llm/final_norm"), save_rstd=False)
+    V, Dv = model.config.vocab_size, model.v.width
+    lg = torch.empty((rows.shape[0], V), dtype=torch.float32, device=model.device)
+    hip.gemm(pl, model.W("llm/embed"), lg, M=rows.shape[0], N=V, K=Dv, lda=Dv, ldb=Dv, ldc=V)
+    lo = model.ps.w16lo("llm/embed")      # the f32 table as hi + lo (see _loss_impl)
+    if lo is not None:
+        hip.gemm(pl, lo, lg, M=rows.shape[0], N=V, K=Dv, lda=Dv, ldb=Dv, ldc=V, accum=True)
+    return lg
+
+
+def _sample_eager(model: LAP, rng, observation, *, max_decoding_steps: int, temperature: float, collect, device_sampler: bool):
+    dev = model.device
+    B, Pn, cache, kinfo_prefix, qinfo_d, plen, x_last = prefill(model, observation)
+    logits = _lm_logits(model, x_last)                                      # decodes the first token (lap.py:716)
+    out = torch.zeros((B, max_decoding_steps), dtype=torch.int32, device=dev)
+    eos = torch.zeros((B,), dtype=torch.bool, device=dev)
+    gen = [(None, None)] * model.v.depth
+    g = _gen(rng, dev) if temperature > 0.0 and not device_sampler else None
+    step = 0
+    while step < max_decoding_steps:
+        if device_sampler and temperature > 0.0:      # one pass over the raw logits, no [B, V] temporaries
+            token = hip.gumbel_argmax_rows(logits, temperature, rng, step)
+        else:
+            if temperature > 0.0:
+                u = torch.rand(logits.shape, generator=g, device=dev, dtype=torch.float32).clamp_(1e-20, 1.0)
+                logits = logits / temperature - torch.log(-torch.log(u))
+            token = hip.argmax_rows(logits)
+        if collect is not None:
+            collect[f"logit/{step}"] = logits.clone()
+        out[:, step] = token
+        eos |= token == model.EOS_TOKEN
+        step += 1
+        if step >= max_decoding_steps or bool(eos.all()):   # lap.py:754-756 loop condition (the unused last decode is skipped)
+            break
+        pos = (plen + (step - 1)).to(torch.int32).view(B, 1).contiguous()
+        logits = _vlm_decode_step(model, token, pos, step - 1, cache, gen, qinfo_d, kinfo_prefix, B, Pn)
+    return out
+
+
+# ---- the fused step: single-token kernels, state on the device (csrc/decode.hip)
+def _sample_fused(model: LAP, observation, *, max_decoding_steps: int, collect=None, sampling=None, weights: str = "bf16"):
+    """sampling: None (the greedy LM head) or (seed, temperature) for the sampling LM head.  weights: `decode_weights`."""
+    pre = prefill(model, observation)
+    ctx = DecodeCtx(model, pre.B, pre.Pn, max_decoding_steps, sampling is not None, weights)
+    if sampling is not None:
+        ctx.set_sampling(*sampling)
+    lg = torch.empty((pre.B, model.config.vocab_size), dtype=torch.float32, device=model.device) if collect is not None else None
+    ctx.first_token(pre, lg)
+    if collect is not None:     # debug: one host read per token
+        collect["logit/0"] = lg.clone()
+        while not bool(ctx.state[1].item()):
+            ctx.step(lg)
+            collect[f"logit/{int(ctx.state[0].item()) - 1}"] = lg.clone()
+        return ctx.out
+    n = DECODE_STEPS_PER_CHECK
+    for _ in range((max_decoding_steps - 1 + n - 1) // n):
+        if bool(ctx.state[1].item()):
+            break
+        for _ in range(n):
+            ctx.step()
+    return ctx.out
+
+
+class DecodeCtx:
+    """One fused decode of `model` (B rows, `Pn` prefix keys, `cap` = max_decoding_steps): the device state, the token output,
+    the fixed-capacity generated K/V cache of every layer ([depth, 2, B, cap, head_dim] bf16, 7.2 MB per sample at 390 steps
+    for LAP-3B) and the step's activations.  The prefix K/V cache and kinfo come from the prefill (`first_token` -> `bind`)."""
+
+    def __init__(self, model: LAP, B: int, Pn: int, cap: int, sampling: bool = False, weights: str = "bf16"):
+        check_decode_weights(weights)
+        v = model.v
+        self.model = model
+        self.weights = weights          # what the steps stream: "bf16", "fp8" (projections + LM head) or "fp8_layers"
+        dev = model.device
+        bf = torch.bfloat16
+        self.B, self.Pn, self.cap = B, Pn, cap
+        self.state = hip.decode_state(B, dev)
+        self.plen = torch.zeros((B,), dtype=torch.int32, device=dev)
+        self.out = torch.zeros((B, cap), dtype=torch.int32, device=dev)
+        self.gen = torch.zeros((v.depth, 2, B, cap, v.head_dim), dtype=bf, device=dev)
+        self.x = torch.zeros((B, v.width), dtype=bf, device=dev)
+        self.xa = torch.zeros((B, v.width), dtype=bf, device=dev)
+        self.q = torch.zeros((B, v.num_heads * v.head_dim), dtype=bf, device=dev)
+        self.o = torch.zeros((B, v.num_heads * v.head_dim), dtype=bf, device=dev)
+        self.act = torch.zeros((B, v.mlp_dim), dtype=bf, device=dev)
+        self.attn_scratch = hip.decode_attn_scratch(B, Pn, cap, dev)
+        self.pval, self.pidx = hip.decode_lm_partials(B, dev)
+        # the sampling words {seed low, seed high, bits of 1 / temperature, 0} of the sampling LM head (zeros: greedy); None:
+        # the context decodes on the greedy LM head
+        self.sampling = hip.decode_sampling(dev) if sampling else None
+        self.prefix = None
+        self.kinfo = None
+
+    def set_sampling(self, seed: int, temperature: float):
+        """Seed and temperature of the next decode (a host-to-device copy; captured graphs keep the buffer's address)."""
+        if self.sampling is None:
+            raise ValueError("this decode context was built without sampling")
+        hip.decode_set_sampling(self.sampling, seed, temperature)
+
+    def bind(self, cache, kinfo_prefix):
+        if kinfo_prefix.shape != (self.B, self.Pn):
+            raise ValueError(f"decode context for B {self.B}, {self.Pn} prefix keys; got kinfo {tuple(kinfo_prefix.shape)}")
+        self.prefix = list(cache)
+        self.kinfo = kinfo_prefix
+
+    def first_token(self, pre: Prefill, logits=None):
+        """Reset the device state for the prefill `pre` and decode the first token from its last rows."""
+        self.bind(pre.cache, pre.kinfo_prefix)
+        self.plen.copy_(pre.plen)
+        hip.decode_init(self.state, self.plen, self.out)
+        self._token(pre.x_last, logits)
+
+    def _w(self, name):
+        """A layer projection as the fused step streams it: (weight, {}) or (e4m3 codes, {"wscale": row scales})."""
+        if self.weights == "bf16":
+            return self.model.W(name), {}
+        codes, scales = self.model._dec_fp8(name)
+        return codes, {"wscale": scales}
+
+    def _token(self, x, logits=None):
+        """final norm + LM head over the hi / lo planes + argmax -> out[:, t], EOS mask, t + 1 (lap.py:716-724).  A context
+        with sampling words runs the sampling LM head, which is the greedy one while the words hold inv_t = 0."""
+        m = self.model
+        if self.weights == "fp8":         # one e4m3 plane of the f32 table
+            hi, scales = m._dec_fp8("llm/embed")
+            lo, kw = None, {"wscale": scales}
+        else:
+            hi, lo, kw = m.W("llm/embed"), m.ps.w16lo("llm/embed"), {}
+        if self.sampling is not None:
+            hip.decode_lm_head_sample(self.state, self.sampling, x, m.F("llm/final_norm"), hi, lo, self.pval, self.pidx, logits, **kw)
+        else:
+            hip.decode_lm_head(self.state, x, m.F("llm/final_norm"), hi, lo, self.pval, self.pidx, logits, **kw)
+        hip.decode_finish(self.state, self.pval, self.pidx, self.out, m.EOS_TOKEN)
+
+    def step(self, logits=None):
+        """One decode step (lap.py:734-752) + its token, positions and stop condition from the device state: replays unchanged."""
+        m = self.model
+        v = m.v
+        NH, HD, KV = v.num_heads, v.head_dim, v.num_kv_heads
+        rows, lo, hi = m.ps.embed_rows()
+        hip.decode_embed(self.state, rows, lo, hi, self.out, self.x, math.sqrt(v.width))
+        for l in range(v.depth):
+            p = f"llm/{l}/"
+            gk, gv = self.gen[l, 0], self.gen[l, 1]
+            w, kw = self._w(p + "wqkv0")
+            hip.decode_qkv(self.state, self.x, m.F(p + "n_attn"), w, self.q, gk, gv, NH, HD, HD ** -0.5, **kw)
+            ck, cv = self.prefix[l]
+            hip.decode_attention(self.state, self.q, ck, cv, self.kinfo, self.Pn, gk, gv, self.o, self.attn_scratch, NH, KV, HD)
+            w, kw = self._w(p + "wo0")
+            hip.decode_proj_residual(self.state, self.o, w, self.x, self.xa, **kw)
+            w, kw = self._w(p + "wgu0")
+            hip.decode_gate_up(self.state, self.xa, m.F(p + "n_ffw"), w, self.act, **kw)
+            w, kw = self._w(p + "wd0")
+            hip.decode_proj_residual(self.state, self.act, w, self.xa, self.x, kwaves=hip.DECODE_KWAVES_DOWN, **kw)
+        self._token(self.x, logits)

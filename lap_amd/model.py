@@ -31,6 +31,7 @@ from lap_amd import hip
 from lap_amd.config import LAPConfig, get_gemma_config, get_siglip_config
 from lap_amd.observation import CoTObservation, preprocess_observation
 from lap_amd.params import LORA_PROJ, ParamStore, lora_geometry
+from lap_amd.serve_cache import ServeCache
 
 SUFFIX_IDX_BASE = 0x800000  # suffix ar-indices live above every prefix index (see _train_infos)
 
@@ -55,7 +56,7 @@ def _gen(rng, device):
 
 
 class LAP:
-    EOS_TOKEN = 1
+    EOS_TOKEN = 1   # PaliGemma <eos> (lap.py: self.EOS_TOKEN)
 
     def __init__(self, config: LAPConfig, seed: int = 0, params: dict | None = None, device="cuda", store: ParamStore | None = None,
                  comm=None, with_optimizer: bool = False, with_ema: bool = False, with_grads: bool = True, gemm_dtype: str = "bf16"):
@@ -107,8 +108,6 @@ class LAP:
         # against packed weight images kept per parameter version (+1.0 GB for LAP-3B).  qkv / out / fc1 are bitwise equal to the
         # unsplit tiles they replace.  LAP_SERVE_PANEL=0: the LDS-tiled kernels (A/B runs, tests)
         self.serve_panel = os.environ.get("LAP_SERVE_PANEL", "1") != "0"
-        self._prefill_pw: dict = {}     # name -> [version, packed image]
-        self._dec_w8: dict = {}         # name -> [version, e4m3 codes, row scales]: the fused decoder's fp8 weights (`_dec_fp8`)
         # the prefill's fused GELU / GeGLU epilogues (SigLIP fc1 on the panel kernel, Gemma's gate|up tile) through v_exp / v_rcp, the training
         # kernels' arithmetic; "bf16": tanhf (A/B)
         self._panel_gelu = os.environ.get("LAP_SERVE_PANEL_GELU", "exp2")
@@ -122,7 +121,6 @@ class LAP:
         self.serve_prefetch = os.environ.get("LAP_SERVE_PREFETCH", "1") != "0"
         self._chain_ctr = None
         self._chain_scratch = None
-        self._packed_w = None       # [version, per layer (wqkv, wo, wgu, wd) packed images]
         self._den = None
         # K splits of the prefill's qkv / out / down projections, down's tile.  Round 5 sweep incl. the consumer (tools/probes/
         # prefill_down_sweep.py, us per GEMM + reduce / residual / norm): 256 x 256 x 8 65.0 | 320 x 128 (tile 19) x 8 60.8 | 320 x 256 x 16 64.5
@@ -148,7 +146,8 @@ class LAP:
                 if geo is not None:
                     self._lora_geo[f"{proj}{i}"] = (geo[0], geo[2], geo[3])
         self._merge_depth = 0
-        self._merged_w: dict = {}   # "llm/{l}/<proj><i>" -> [store version, merged bf16 weight]
+        # every parameter-derived tensor of the serving paths (`_merged`, `_dec_fp8`, `_pw`, `_serve_packed_weights`, `_serve_mods`)
+        self.serving_cache = ServeCache(self.ps, self.device, lambda unit: self.comm.wait_unit(unit))
         if self._lora_geo and gemm_dtype == "fp8":
             raise ValueError("gemm_dtype='fp8' has no LoRA route: use gemm_dtype='bf16' with the LoRA Gemma variants")
         if gemm_dtype == "fp8":
@@ -324,16 +323,13 @@ class LAP:
     def _merged(self, name):
         """bf16(W + s B^T A) of a LoRA'd projection from the f32 masters, rounded once (csrc/lora.hip lap_lora_merge): persistent
         like `_serve_mods` and recomputed in place per parameter version."""
-        rec = self._merged_w.get(name)
-        if rec is None or rec[0] != self.ps.version:
-            if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("serving caches are stale inside a stream capture: call refresh_serve_caches() first")
+        def build(old):
             _, l, key = name.split("/")
+            self.comm.wait_unit(f"llm{l}")
             G, nsum, s = self._lora_geo[key]
-            out = rec[1] if rec is not None else torch.empty(self.ps.tensor_spec[name].shape, dtype=torch.bfloat16, device=self.device)
-            hip.lora_merge(self.F(name), self.F(f"llm/{l}/lora_a_{key}"), self.F(f"llm/{l}/lora_b_{key}"), out, G=G, nsum=nsum, s=s)
-            self._merged_w[name] = rec = [self.ps.version, out]
-        return rec[1]
+            out = old if old is not None else torch.empty(self.ps.tensor_spec[name].shape, dtype=torch.bfloat16, device=self.device)
+            return hip.lora_merge(self.F(name), self.F(f"llm/{l}/lora_a_{key}"), self.F(f"llm/{l}/lora_b_{key}"), out, G=G, nsum=nsum, s=s)
+        return self.serving_cache.get(("merged", name), None, build)
 
     @contextlib.contextmanager
     def _serving_weights(self):
@@ -1567,50 +1563,33 @@ class LAP:
         per (nsteps, dt), refreshed IN PLACE when the parameters change: a captured sampler holds its address (ADVICE r3 — a
         cache that dropped the tensor on a version change left a replayed graph reading freed memory and stale modulations).
         `GraphedSampler.__call__` calls `refresh_serve_caches` before every replay; never refreshed during stream capture."""
-        key = (nsteps, float(dt))
-        ent = self.__dict__.setdefault("_mods_cache", {})
-        rec = ent.get(key)
-        if rec is None or rec[0] != self.ps.version:
-            if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("serving caches are stale inside a stream capture: call refresh_serve_caches() first")
+        def build(old):
             tvec = 1.0 + dt * torch.arange(nsteps, dtype=torch.float32, device=self.device)
-            self.comm.wait_unit("ada")
             new = self._time_mod(tvec, False)[0]
-            if rec is None:
-                ent[key] = rec = [self.ps.version, new]
-            else:
-                rec[1].copy_(new)
-                rec[0] = self.ps.version
-        return rec[1]
+            return new if old is None else old.copy_(new)
+        return self.serving_cache.get(("mods", nsteps, float(dt)), "ada", build)
 
     def _serve_packed_weights(self):
         """Fragment-packed images of the action expert's projections for the packed chain (csrc/serve_skinny_body.hpp PK),
         persistent like `_serve_mods` and re-packed in place per parameter version (+0.62 GB for LAP-3B)."""
-        rec = self._packed_w
-        if rec is not None and rec[0] == self.ps.version:
-            return rec[1]
-        if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("serving caches are stale inside a stream capture: call refresh_serve_caches() first")
-        kinds = (("wqkv1", hip.PACK_QKV), ("wo1", hip.PACK_PLAIN), ("wgu1", hip.PACK_GATE_UP), ("wd1", hip.PACK_PLAIN))
-        old = rec[1] if rec is not None else None
-        out = []
-        for l in range(self.v.depth):
-            self.comm.wait_unit(f"llm{l}")
-            out.append(tuple(hip.serve_pack_weight(self.W(f"llm/{l}/{n}"), kind, self.v.head_dim, out=None if old is None else old[l][j])
-                             for j, (n, kind) in enumerate(kinds)))
-        self._packed_w = [self.ps.version, out]
-        return out
+        def build(old):
+            kinds = (("wqkv1", hip.PACK_QKV), ("wo1", hip.PACK_PLAIN), ("wgu1", hip.PACK_GATE_UP), ("wd1", hip.PACK_PLAIN))
+            out = []
+            for l in range(self.v.depth):
+                self.comm.wait_unit(f"llm{l}")
+                out.append(tuple(hip.serve_pack_weight(self.W(f"llm/{l}/{n}"), kind, self.v.head_dim, out=None if old is None else old[l][j])
+                                 for j, (n, kind) in enumerate(kinds)))
+            return out
+        return self.serving_cache.get(("chain",), None, build)
 
     def _pw(self, name):
         """Fragment-packed image (lap_serve_pack_weight kind 3) of a prefill projection for the row-panel kernel, persistent like
         `_serve_packed_weights` and re-packed in place per parameter version."""
-        rec = self._prefill_pw.get(name)
-        if rec is None or rec[0] != self.ps.version:
-            if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("serving caches are stale inside a stream capture: call refresh_serve_caches() first")
-            img = hip.serve_pack_weight(self.W(name), hip.PACK_PLAIN, out=None if rec is None else rec[1])
-            self._prefill_pw[name] = rec = [self.ps.version, img]
-        return rec[1]
+        def build(old):
+            kind, l = name.split("/")[:2]
+            self.comm.wait_unit(f"{kind}{l}")
+            return hip.serve_pack_weight(self.W(name), hip.PACK_PLAIN, out=old)
+        return self.serving_cache.get(("panel", name), None, build)
 
     def _dec_fp8(self, name):
         """(e4m3 codes [N, K], f32 row scales [N]) of a weight of the fused decoder in the format of lap_amd/fp8.py: persistent
@@ -1618,89 +1597,18 @@ class LAP:
         holds both addresses).  The layer projections are quantised from the bf16 weight `W(name)` the bf16 decoder reads (the
         merged one under `_serving_weights`), the LM head from the f32 embedding table.  +1 byte per weight on top of the bf16
         copies the prefill keeps: 2.0 GB for LAP-3B's 18 layers, 0.53 GB for the table."""
-        rec = self._dec_w8.get(name)
-        if rec is None or rec[0] != self.ps.version:
-            if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("serving caches are stale inside a stream capture: call refresh_serve_caches() first")
-            src = self.F(name) if name == "llm/embed" else self.W(name)
-            codes, scales = hip.quantize_fp8_rows(src, *(() if rec is None else rec[1:]))
-            self._dec_w8[name] = rec = [self.ps.version, codes, scales]
-        return rec[1], rec[2]
-
-    def _time_grid(self, num_steps: int):
-        dt = -1.0 / num_steps
-        n, t = 0, 1.0
-        while t >= -dt / 2:  # lap.py:669-674 loop condition
-            n += 1
-            t += dt
-        return n, dt
-
-    def refresh_serve_caches(self, num_steps: int = 10):
-        """Bring the sampler's parameter-derived caches (merged LoRA weights, the fused decoder's fp8 weights, adaRMS modulations,
-        packed expert weights) up to the current parameter version, in place.  Eager `sample_actions` does this itself; a captured graph cannot — call it before a replay."""
-        with self._serving_weights():
-            self._refresh_serve_caches(num_steps)
-
-    def _refresh_serve_caches(self, num_steps: int):
-        for name in list(self._merged_w):      # (first: the packed images below are made from them)
-            self.comm.wait_unit("llm" + name.split("/")[1])
-            self._merged(name)
-        for name in list(self._dec_w8):        # (after the merged weights they are quantised from)
+        def build(old):
             self.comm.wait_unit("embed" if name == "llm/embed" else "llm" + name.split("/")[1])
-            self._dec_fp8(name)
-        n, dt = self._time_grid(num_steps)
-        for name in list(self._prefill_pw):
-            kind, l = name.split("/")[:2]
-            self.comm.wait_unit(f"{kind}{l}")
-            self._pw(name)
-        if not self.config.pi05:
-            return          # (pi0 has no adaRMS bank and runs on the generic layer loop: nothing else is cached)
-        self._serve_mods(n, dt)
-        if self._packed_w is not None:
-            self._serve_packed_weights()
+            return hip.quantize_fp8_rows(self.F(name) if name == "llm/embed" else self.W(name), *(old or ()))
+        return self.serving_cache.get(("dec8", name), None, build)
 
-    EOS_TOKEN = 1   # PaliGemma <eos> (lap.py: self.EOS_TOKEN)
-
-    def _vlm_decode_step(self, token, pos, step, cache, gen, qinfo_d, kinfo_prefix, B, Pn):
-        """One expert-0 decode step (lap.py:734-752): embed the sampled token, run the 18 VLM layers on that single row
-        per sample with keys = [prefilled prefix cache | generated tokens incl. this one], return f32 logits [B, V].
-        The reference appends into a fixed-size cache by index (gemma.py:597-605); here the generated keys are a second
-        key segment that grows by one row per step."""
-        v = self.v
-        NH, HD, KV, Dv = v.num_heads, v.head_dim, v.num_kv_heads, v.width
-        dev = self.device
-        x = torch.empty((B, Dv), dtype=torch.bfloat16, device=dev)
-        rows, lo, hi = self.ps.embed_rows()
-        hip.embed_gather(rows, token.view(B, 1).contiguous(), x, B, 1, Dv, 1, 0, math.sqrt(Dv), lo, hi)
-        kinfo = torch.cat([kinfo_prefix, torch.full((B, step + 1), 1 << 24, dtype=torch.int32, device=dev)], 1).contiguous()
-        for l in range(v.depth):
-            p = f"llm/{l}/"
-            h, _ = hip.rmsnorm_fwd(x, scale=self.F(p + "n_attn"), save_rstd=False)
-            qkv = hip.linear_fwd(h, self.W(p + "wqkv0"))
-            q, k, vv = hip.rope_split_fwd(qkv, pos, B, 1, 1, 0, NH, HD, HD ** -0.5)
-            gk, gv = gen[l]
-            gk = k.view(B, 1, -1) if gk is None else torch.cat([gk, k.view(B, 1, -1)], 1)
-            gv = vv.view(B, 1, -1) if gv is None else torch.cat([gv, vv.view(B, 1, -1)], 1)
-            gen[l] = (gk, gv)
-            ck, cv = cache[l]
-            o, _ = hip.attention_fwd([None, q], [ck, gk.view(B * (step + 1), -1)], [cv, gv.view(B * (step + 1), -1)], [0, 1],
-                                     [Pn, step + 1], B, NH, KV, HD, qinfo_d, kinfo, need_lse=False)
-            xa = hip.linear_fwd(o[1], self.W(p + "wo0"), residual=x)
-            hf, _ = hip.rmsnorm_fwd(xa, scale=self.F(p + "n_ffw"), save_rstd=False)
-            act = hip.geglu_fwd(hip.linear_fwd(hf, self.W(p + "wgu0")))
-            x = hip.linear_fwd(act, self.W(p + "wd0"), residual=xa)
-        return self._lm_logits(x)
-
-    def _lm_logits(self, rows):
-        """final norm + Embedder.decode (gemma.py:153-154, 525-527): f32 logits [R, V]."""
-        pl, _ = hip.rmsnorm_fwd(rows, scale=self.F("llm/final_norm"), save_rstd=False)
-        V, Dv = self.config.vocab_size, self.v.width
-        lg = torch.empty((rows.shape[0], V), dtype=torch.float32, device=self.device)
-        hip.gemm(pl, self.W("llm/embed"), lg, M=rows.shape[0], N=V, K=Dv, lda=Dv, ldb=Dv, ldc=V)
-        lo = self.ps.w16lo("llm/embed")      # the f32 table as hi + lo (see _loss_impl)
-        if lo is not None:
-            hip.gemm(pl, lo, lg, M=rows.shape[0], N=V, K=Dv, lda=Dv, ldb=Dv, ldc=V, accum=True)
-        return lg
+    def refresh_serve_caches(self, num_steps=None):
+        """Bring every parameter-derived serving tensor there is (`lap_amd/serve_cache.py`: merged LoRA weights, the fused decoder's
+        fp8 weights, packed weight images, adaRMS modulations) up to the current parameter version, in place.  The eager paths do
+        this on use; a captured graph cannot — call it before a replay.  `num_steps` is accepted and ignored: what a sampler
+        needs exists since its warm-up."""
+        with self._serving_weights():
+            self.serving_cache.refresh()
 
     def sample_tokens(self, rng, observation, *, max_decoding_steps: int = 390, temperature: float = 0.0, collect=None,
                       decode: str = "eager", sampler: str = "host", decode_weights: str = "bf16"):
@@ -1739,225 +1647,14 @@ class LAP:
         of the f32 table (its precision decides greedy near-ties).  The kernels compute what the bf16 ones compute on the
         dequantised weights; the prefill and the embedding gather are unchanged.  The fp8 copies are cached on the model and
         follow the parameters (`refresh_serve_caches`).  Needs decode="fused"."""
-        if decode not in ("eager", "fused"):
-            raise ValueError(f"sample_tokens: decode must be 'eager' or 'fused', got {decode!r}")
-        self._check_decode_weights(decode_weights)
-        if decode_weights != "bf16" and decode != "fused":
-            raise ValueError(f"sample_tokens: decode_weights={decode_weights!r} runs on the fused decode kernels only: pass decode=\"fused\"")
-        if sampler not in ("host", "device"):
-            raise ValueError(f"sample_tokens: sampler must be 'host' or 'device', got {sampler!r}")
-        if decode == "fused":
-            self._check_fused_decode(observation.tokenized_prompt.shape[0])
-        if sampler == "device":
-            hip.sampling_words(rng, temperature)        # (rejects a temperature whose inverse is not finite before any work)
-        with self._serving_weights():
-            if decode == "fused" and sampler == "device":
-                return self._sample_tokens_fused(observation, max_decoding_steps=max_decoding_steps, collect=collect,
-                                                 sampling=(rng, temperature), weights=decode_weights)
-            if decode == "fused" and temperature <= 0.0:
-                return self._sample_tokens_fused(observation, max_decoding_steps=max_decoding_steps, collect=collect,
-                                                 weights=decode_weights)
-            if decode_weights != "bf16":
-                raise ValueError("sample_tokens: decode_weights other than 'bf16' with temperature > 0 needs sampler='device' (the "
-                                 "host sampler keeps the eager loop)")
-            return self._sample_tokens(rng, observation, max_decoding_steps=max_decoding_steps, temperature=temperature, collect=collect,
-                                       device_sampler=sampler == "device")
+        from lap_amd import ar_decode       # (it imports this module)
+        return ar_decode.sample_tokens(self, rng, observation, max_decoding_steps=max_decoding_steps, temperature=temperature,
+                                       collect=collect, decode=decode, sampler=sampler, decode_weights=decode_weights)
 
-    def _ar_prefill(self, observation):
-        """The VLM-only prefill of sample_tokens (lap.py:693-716): (B, Pn, prefix K/V cache per layer, kinfo_prefix [B, Pn],
-        qinfo of the decode query, plen [B], the last valid residual row of every sample [B, D])."""
-        cfg = self.config
-        dev = self.device
-        if self.comm.world_size != 1:
-            raise NotImplementedError("sample_tokens is a serving path: replicas only (SURVEY.md §8e)")
-        self.comm.wait_unit("small")
-        obs = preprocess_observation(observation, train=False, image_keys=cfg.image_keys, image_resolution=cfg.image_resolution)
-        B = obs.tokenized_prompt.shape[0]
-        x0, Pn, _ = self._embed_prefix(obs, False, serve=True)
-        qinfo_p, kinfo_p, ppos = self._serve_infos(obs, 1)[:3]
-        prefix_mask, _ = self._prefix_masks(obs)
-        ar = torch.arange(Pn, device=dev)
-        seqlen = (prefix_mask.to(torch.int64) * ar).max(-1).values + 1          # left_to_right_align's roll amount
-        plen = prefix_mask.sum(-1)                                               # prefill_len
-        in_range = (ar[None] >= (seqlen - plen)[:, None]) & (ar[None] < seqlen[:, None])
-        kinfo_prefix = (in_range.to(torch.int32) << 24).contiguous()
-        qinfo_d = torch.full((B, 1), (1 << 24) | 0xFFFFFF, dtype=torch.int32, device=dev)
-        cache = []
-        if self.serve_fusions and self.gemm_dtype == "bf16":
-            xf0 = self._llm_prefill(x0, ppos, qinfo_p, kinfo_p, B, Pn, cache)
-        else:
-            xf0, _, _ = self._llm_fwd(x0, None, None, ppos, qinfo_p, kinfo_p, B, Pn, 0, False, cache_out=cache)
-        last = (torch.arange(B, device=dev) * Pn + seqlen - 1)
-        return B, Pn, cache, kinfo_prefix, qinfo_d, plen, xf0.index_select(0, last).contiguous()
-
-    def _sample_tokens(self, rng, observation, *, max_decoding_steps: int = 390, temperature: float = 0.0, collect=None,
-                       device_sampler: bool = False):
-        """`sample_tokens` with the weights as `_serving_weights` presents them (merged when the model has adapters)."""
-        dev = self.device
-        B, Pn, cache, kinfo_prefix, qinfo_d, plen, x_last = self._ar_prefill(observation)
-        logits = self._lm_logits(x_last)                                        # decodes the first token (lap.py:716)
-        out = torch.zeros((B, max_decoding_steps), dtype=torch.int32, device=dev)
-        eos = torch.zeros((B,), dtype=torch.bool, device=dev)
-        gen = [(None, None)] * self.v.depth
-        g = _gen(rng, dev) if temperature > 0.0 and not device_sampler else None
-        step = 0
-        while step < max_decoding_steps:
-            if device_sampler and temperature > 0.0:      # one pass over the raw logits, no [B, V] temporaries
-                token = hip.gumbel_argmax_rows(logits, temperature, rng, step)
-            else:
-                if temperature > 0.0:
-                    u = torch.rand(logits.shape, generator=g, device=dev, dtype=torch.float32).clamp_(1e-20, 1.0)
-                    logits = logits / temperature - torch.log(-torch.log(u))
-                token = hip.argmax_rows(logits)
-            if collect is not None:
-                collect[f"logit/{step}"] = logits.clone()
-            out[:, step] = token
-            eos |= token == self.EOS_TOKEN
-            step += 1
-            if step >= max_decoding_steps or bool(eos.all()):   # lap.py:754-756 loop condition (the unused last decode is skipped)
-                break
-            pos = (plen + (step - 1)).to(torch.int32).view(B, 1).contiguous()
-            logits = self._vlm_decode_step(token, pos, step - 1, cache, gen, qinfo_d, kinfo_prefix, B, Pn)
-        return out
-
-    # ---- fused single-token decode (csrc/decode.hip)
-    DECODE_STEPS_PER_CHECK = 8      # fused steps between two host reads of the device stop flag (eager `decode="fused"`)
+    DECODE_WEIGHTS = ("bf16", "fp8", "fp8_layers")
 
     def decode_supported(self, B: int) -> bool:
         """Whether `sample_tokens(decode="fused")` / `GraphedTokenDecoder` serve `B` rows of this model."""
         v = self.v
         return self.comm.world_size == 1 and hip.decode_ok(B, v.width, v.num_heads, v.num_kv_heads, v.head_dim, v.mlp_dim,
                                                             self.config.vocab_size)
-
-    def _check_fused_decode(self, B: int):
-        if self.comm.world_size != 1:
-            raise ValueError("fused decode is a serving path: replicas only (world_size 1)")
-        if not self.decode_supported(B):
-            v = self.v
-            raise ValueError(f"fused decode serves the Gemma-2B widths at 1 <= B <= 8 (D 2048, 8 / 1 heads of 256, MLP 16384); got "
-                             f"B {B}, D {v.width}, heads {v.num_heads} / {v.num_kv_heads} of {v.head_dim}, MLP {v.mlp_dim}")
-
-    DECODE_WEIGHTS = ("bf16", "fp8", "fp8_layers")
-
-    @classmethod
-    def _check_decode_weights(cls, weights):
-        if weights not in cls.DECODE_WEIGHTS:
-            raise ValueError(f"decode_weights must be one of {cls.DECODE_WEIGHTS}, got {weights!r}")
-
-    def _decode_ctx(self, B: int, Pn: int, cap: int, sampling: bool = False, weights: str = "bf16"):
-        self._check_decode_weights(weights)
-        return _DecodeCtx(self, B, Pn, cap, sampling, weights)
-
-    def _dec_w(self, ctx, name):
-        """A layer projection as the fused step of `ctx` streams it: (weight, {}) or (e4m3 codes, {"wscale": row scales})."""
-        if ctx.weights == "bf16":
-            return self.W(name), {}
-        codes, scales = self._dec_fp8(name)
-        return codes, {"wscale": scales}
-
-    def _fused_first_token(self, ctx, pre, logits=None):
-        """Reset the device state for the prefill `pre` (from `_ar_prefill`) and decode the first token from its last rows."""
-        B, Pn, cache, kinfo_prefix, _, plen, x_last = pre
-        ctx.bind(cache, kinfo_prefix)
-        ctx.plen.copy_(plen)
-        hip.decode_init(ctx.state, ctx.plen, ctx.out)
-        self._fused_token(ctx, x_last, logits)
-
-    def _fused_token(self, ctx, x, logits=None):
-        """final norm + LM head over the hi / lo planes + argmax -> out[:, t], EOS mask, t + 1 (lap.py:716-724).  A context
-        with sampling words runs the sampling LM head, which is the greedy one while the words hold inv_t = 0."""
-        if ctx.weights == "fp8":         # one e4m3 plane of the f32 table
-            hi, scales = self._dec_fp8("llm/embed")
-            lo, kw = None, {"wscale": scales}
-        else:
-            hi, lo, kw = self.W("llm/embed"), self.ps.w16lo("llm/embed"), {}
-        if ctx.sampling is not None:
-            hip.decode_lm_head_sample(ctx.state, ctx.sampling, x, self.F("llm/final_norm"), hi, lo, ctx.pval, ctx.pidx, logits, **kw)
-        else:
-            hip.decode_lm_head(ctx.state, x, self.F("llm/final_norm"), hi, lo, ctx.pval, ctx.pidx, logits, **kw)
-        hip.decode_finish(ctx.state, ctx.pval, ctx.pidx, ctx.out, self.EOS_TOKEN)
-
-    def _fused_step(self, ctx, logits=None):
-        """One decode step (lap.py:734-752) + its token, positions and stop condition from the device state: replays unchanged."""
-        v = self.v
-        NH, HD, KV = v.num_heads, v.head_dim, v.num_kv_heads
-        rows, lo, hi = self.ps.embed_rows()
-        hip.decode_embed(ctx.state, rows, lo, hi, ctx.out, ctx.x, math.sqrt(v.width))
-        for l in range(v.depth):
-            p = f"llm/{l}/"
-            gk, gv = ctx.gen[l, 0], ctx.gen[l, 1]
-            w, kw = self._dec_w(ctx, p + "wqkv0")
-            hip.decode_qkv(ctx.state, ctx.x, self.F(p + "n_attn"), w, ctx.q, gk, gv, NH, HD, HD ** -0.5, **kw)
-            ck, cv = ctx.prefix[l]
-            hip.decode_attention(ctx.state, ctx.q, ck, cv, ctx.kinfo, ctx.Pn, gk, gv, ctx.o, ctx.attn_scratch, NH, KV, HD)
-            w, kw = self._dec_w(ctx, p + "wo0")
-            hip.decode_proj_residual(ctx.state, ctx.o, w, ctx.x, ctx.xa, **kw)
-            w, kw = self._dec_w(ctx, p + "wgu0")
-            hip.decode_gate_up(ctx.state, ctx.xa, self.F(p + "n_ffw"), w, ctx.act, **kw)
-            w, kw = self._dec_w(ctx, p + "wd0")
-            hip.decode_proj_residual(ctx.state, ctx.act, w, ctx.xa, ctx.x, kwaves=hip.DECODE_KWAVES_DOWN, **kw)
-        self._fused_token(ctx, ctx.x, logits)
-
-    def _sample_tokens_fused(self, observation, *, max_decoding_steps: int, collect=None, sampling=None, weights: str = "bf16"):
-        """sampling: None (the greedy LM head) or (seed, temperature) for the sampling LM head.  weights: `decode_weights`."""
-        pre = self._ar_prefill(observation)
-        B, Pn = pre[0], pre[1]
-        ctx = self._decode_ctx(B, Pn, max_decoding_steps, sampling is not None, weights)
-        if sampling is not None:
-            ctx.set_sampling(*sampling)
-        lg = torch.empty((B, self.config.vocab_size), dtype=torch.float32, device=self.device) if collect is not None else None
-        self._fused_first_token(ctx, pre, lg)
-        if collect is not None:     # debug: one host read per token
-            collect["logit/0"] = lg.clone()
-            while not bool(ctx.state[1].item()):
-                self._fused_step(ctx, lg)
-                collect[f"logit/{int(ctx.state[0].item()) - 1}"] = lg.clone()
-            return ctx.out
-        n = self.DECODE_STEPS_PER_CHECK
-        for _ in range((max_decoding_steps - 1 + n - 1) // n):
-            if bool(ctx.state[1].item()):
-                break
-            for _ in range(n):
-                self._fused_step(ctx)
-        return ctx.out
-
-
-class _DecodeCtx:
-    """Buffers of one fused decode (B rows, `Pn` prefix keys, `cap` = max_decoding_steps): the device state, the token output,
-    the fixed-capacity generated K/V cache of every layer ([depth, 2, B, cap, head_dim] bf16, 7.2 MB per sample at 390 steps
-    for LAP-3B) and the step's activations.  The prefix K/V cache and kinfo come from the prefill (`bind`)."""
-
-    def __init__(self, model: LAP, B: int, Pn: int, cap: int, sampling: bool = False, weights: str = "bf16"):
-        v = model.v
-        self.weights = weights          # what the steps stream: "bf16", "fp8" (projections + LM head) or "fp8_layers"
-        dev = model.device
-        bf = torch.bfloat16
-        self.B, self.Pn, self.cap = B, Pn, cap
-        self.state = hip.decode_state(B, dev)
-        self.plen = torch.zeros((B,), dtype=torch.int32, device=dev)
-        self.out = torch.zeros((B, cap), dtype=torch.int32, device=dev)
-        self.gen = torch.zeros((v.depth, 2, B, cap, v.head_dim), dtype=bf, device=dev)
-        self.x = torch.zeros((B, v.width), dtype=bf, device=dev)
-        self.xa = torch.zeros((B, v.width), dtype=bf, device=dev)
-        self.q = torch.zeros((B, v.num_heads * v.head_dim), dtype=bf, device=dev)
-        self.o = torch.zeros((B, v.num_heads * v.head_dim), dtype=bf, device=dev)
-        self.act = torch.zeros((B, v.mlp_dim), dtype=bf, device=dev)
-        self.attn_scratch = hip.decode_attn_scratch(B, Pn, cap, dev)
-        self.pval, self.pidx = hip.decode_lm_partials(B, dev)
-        # the sampling words {seed low, seed high, bits of 1 / temperature, 0} of the sampling LM head (zeros: greedy); None:
-        # the context decodes on the greedy LM head
-        self.sampling = hip.decode_sampling(dev) if sampling else None
-        self.prefix = None
-        self.kinfo = None
-
-    def set_sampling(self, seed: int, temperature: float):
-        """Seed and temperature of the next decode (a host-to-device copy; captured graphs keep the buffer's address)."""
-        if self.sampling is None:
-            raise ValueError("this decode context was built without sampling")
-        hip.decode_set_sampling(self.sampling, seed, temperature)
-
-    def bind(self, cache, kinfo_prefix):
-        if kinfo_prefix.shape != (self.B, self.Pn):
-            raise ValueError(f"decode context for B {self.B}, {self.Pn} prefix keys; got kinfo {tuple(kinfo_prefix.shape)}")
-        self.prefix = list(cache)
-        self.kinfo = kinfo_prefix

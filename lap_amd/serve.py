@@ -17,28 +17,42 @@ import time
 import numpy as np
 import torch
 
+from lap_amd import ar_decode
 from lap_amd.model import LAP
 from lap_amd.observation import CoTObservation
+
+
+def _placeholder_obs(model: LAP, batch_size: int, prompt_len: int | None, langact_mask: bool = False) -> CoTObservation:
+    """The observation a captured graph reads: requests are copied into its tensors (`_load`)."""
+    cfg = model.config
+    dev = model.device
+    L = prompt_len or cfg.max_token_len
+    H = cfg.image_size
+    return CoTObservation(
+        images={k: torch.zeros(batch_size, H, H, 3, device=dev) for k in cfg.image_keys},
+        image_masks={k: torch.ones(batch_size, dtype=torch.bool, device=dev) for k in cfg.image_keys},
+        state=torch.zeros(batch_size, cfg.action_dim, device=dev),
+        tokenized_prompt=torch.zeros(batch_size, L, dtype=torch.int32, device=dev),
+        tokenized_prompt_mask=torch.ones(batch_size, L, dtype=torch.bool, device=dev),
+        tokenized_langact_mask=torch.zeros(batch_size, L, dtype=torch.bool, device=dev) if langact_mask else None)
+
+
+def graph_compatible(captured: CoTObservation, obs: CoTObservation) -> bool:
+    """A captured graph is tied to the batch size, image resolution and prompt length of the observation it was captured on."""
+    return (all(k in obs.images and tuple(obs.images[k].shape) == tuple(captured.images[k].shape) for k in captured.images)
+            and tuple(obs.tokenized_prompt.shape) == tuple(captured.tokenized_prompt.shape))
 
 
 class GraphedSampler:
     def __init__(self, model: LAP, batch_size: int = 1, num_steps: int = 10, prompt_len: int | None = None):
         self.model, self.B, self.num_steps = model, batch_size, num_steps
         cfg = model.config
-        dev = model.device
-        L = prompt_len or cfg.max_token_len
-        H = cfg.image_size
-        self.obs = CoTObservation(
-            images={k: torch.zeros(batch_size, H, H, 3, device=dev) for k in cfg.image_keys},
-            image_masks={k: torch.ones(batch_size, dtype=torch.bool, device=dev) for k in cfg.image_keys},
-            state=torch.zeros(batch_size, cfg.action_dim, device=dev),
-            tokenized_prompt=torch.zeros(batch_size, L, dtype=torch.int32, device=dev),
-            tokenized_prompt_mask=torch.ones(batch_size, L, dtype=torch.bool, device=dev))
-        self.noise = torch.zeros(batch_size, cfg.action_horizon, cfg.action_dim, device=dev)
+        self.obs = _placeholder_obs(model, batch_size, prompt_len)
+        self.noise = torch.zeros(batch_size, cfg.action_horizon, cfg.action_dim, device=model.device)
         self.graph = None
         self.out = None
 
-    def _load(self, obs: CoTObservation, noise: torch.Tensor):
+    def _load(self, obs: CoTObservation, noise: torch.Tensor):     # (unlike GraphedTokenDecoder._load: absent image masks and `state` keep the last request's)
         for k in self.obs.images:
             self.obs.images[k].copy_(obs.images[k])
             if k in obs.image_masks and obs.image_masks[k] is not None:
@@ -91,24 +105,14 @@ class GraphedTokenDecoder:
 
     def __init__(self, model: LAP, batch_size: int = 1, max_decoding_steps: int = 390, prompt_len: int | None = None,
                  steps_per_replay: int = 8, sampling: bool = False, weights: str = "bf16"):
-        model._check_fused_decode(batch_size)
-        model._check_decode_weights(weights)
+        ar_decode.check_fused_decode(model, batch_size)
+        ar_decode.check_decode_weights(weights)
         self.weights = weights
         if max_decoding_steps < 1 or steps_per_replay < 1:
             raise ValueError("max_decoding_steps and steps_per_replay must be >= 1")
         self.model, self.B, self.max_steps, self.spr = model, batch_size, max_decoding_steps, steps_per_replay
         self.sampling = bool(sampling)
-        cfg = model.config
-        dev = model.device
-        L = prompt_len or cfg.max_token_len
-        H = cfg.image_size
-        self.obs = CoTObservation(
-            images={k: torch.zeros(batch_size, H, H, 3, device=dev) for k in cfg.image_keys},
-            image_masks={k: torch.ones(batch_size, dtype=torch.bool, device=dev) for k in cfg.image_keys},
-            state=torch.zeros(batch_size, cfg.action_dim, device=dev),
-            tokenized_prompt=torch.zeros(batch_size, L, dtype=torch.int32, device=dev),
-            tokenized_prompt_mask=torch.ones(batch_size, L, dtype=torch.bool, device=dev),
-            tokenized_langact_mask=torch.zeros(batch_size, L, dtype=torch.bool, device=dev))
+        self.obs = _placeholder_obs(model, batch_size, prompt_len, langact_mask=True)
         self.ctx = None
         self.g_prefill = self.g_step = None
 
@@ -130,15 +134,14 @@ class GraphedTokenDecoder:
             self.obs.tokenized_langact_mask.zero_()
 
     def _prefill(self):
-        m = self.model
-        pre = m._ar_prefill(self.obs)
+        pre = ar_decode.prefill(self.model, self.obs)
         if self.ctx is None:
-            self.ctx = m._decode_ctx(self.B, pre[1], self.max_steps, self.sampling, self.weights)
-        m._fused_first_token(self.ctx, pre)
+            self.ctx = ar_decode.DecodeCtx(self.model, self.B, pre.Pn, self.max_steps, self.sampling, self.weights)
+        self.ctx.first_token(pre)
 
     def _steps(self):
         for _ in range(self.spr):
-            self.model._fused_step(self.ctx)
+            self.ctx.step()
 
     def capture(self):
         m = self.model
@@ -159,12 +162,6 @@ class GraphedTokenDecoder:
                 self._steps()
         torch.cuda.synchronize()
         return self
-
-    def compatible(self, obs: CoTObservation) -> bool:
-        """The captured graphs are tied to the batch size, image resolution and prompt length."""
-        g = self.obs
-        return (all(k in obs.images and tuple(obs.images[k].shape) == tuple(g.images[k].shape) for k in g.images)
-                and tuple(obs.tokenized_prompt.shape) == tuple(g.tokenized_prompt.shape))
 
     def __call__(self, obs: CoTObservation, *, temperature: float = 0.0, seed: int = 0) -> torch.Tensor:
         if temperature > 0.0 and not self.sampling:
@@ -222,7 +219,7 @@ class Policy:
             noise = torch.randn((1, cfg.action_horizon, cfg.action_dim), generator=self._gen, device=dev)
         else:
             noise = torch.as_tensor(np.asarray(noise), dtype=torch.float32, device=dev).reshape(1, cfg.action_horizon, cfg.action_dim)
-        if self._sampler is not None and self._graph_compatible(o):
+        if self._sampler is not None and graph_compatible(self._sampler.obs, o):
             a = self._sampler(o, noise)
         else:
             a = self.model.sample_actions(0, o, num_steps=self.num_steps, noise=noise)
@@ -240,12 +237,6 @@ class Policy:
         outputs = self._output_transform({"state": batched["state"][0], "actions": actions})
         outputs["policy_timing"] = {"infer_ms": model_ms}
         return outputs
-
-    def _graph_compatible(self, o: CoTObservation) -> bool:
-        """The captured graph is tied to the model's native image resolution and prompt length."""
-        g = self._sampler.obs
-        return (all(tuple(o.images[k].shape) == tuple(g.images[k].shape) for k in g.images)
-                and tuple(o.tokenized_prompt.shape) == tuple(g.tokenized_prompt.shape))
 
 
 def create_trained_policy(train_config, checkpoint_dir, *, tokenizer_model_path=None, tokenizer=None, repack_transforms=(),
@@ -336,7 +327,7 @@ class ARPolicy:
         # sample_kwargs["decode_weights"] ("fp8" / "fp8_layers") reaches both routes: the decoder is captured on those weights,
         # and sample_tokens gets decode="fused" with it (the fp8 kernels are fused decode kernels), so both decode on the same weights
         weights = self._sample_kwargs.get("decode_weights", "bf16")
-        base.model._check_decode_weights(weights)
+        ar_decode.check_decode_weights(weights)
         if weights != "bf16":
             if self._sample_kwargs.setdefault("decode", "fused") != "fused":
                 raise ValueError(f"ARPolicy: decode_weights={weights!r} needs decode=\"fused\", got {self._sample_kwargs['decode']!r}")
@@ -360,7 +351,7 @@ class ARPolicy:
         self._calls += 1
         temperature = self._sample_kwargs.get("temperature", 0.0)
         if (self._decoder is not None and (temperature <= 0.0 or self._device_sampler)
-                and self._sample_kwargs.get("decode", "eager") in ("eager", "fused") and self._decoder.compatible(o)):
+                and self._sample_kwargs.get("decode", "eager") in ("eager", "fused") and graph_compatible(self._decoder.obs, o)):
             tokens = self._decoder(o, temperature=temperature, seed=self._calls) if self._device_sampler else self._decoder(o)
         else:
             tokens = base.model.sample_tokens(self._calls, o, **self._sample_kwargs)

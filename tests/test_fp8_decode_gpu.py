@@ -210,15 +210,19 @@ def test_fp8_entry_points_reject_bad_arguments(hip):
 def _prefill_once(model, o, mp):
     """Run the (unquantised) prefill once and make `model` hand that result to every decode under `mp`: the fp8 decode and its
     twin then start from the same prefix cache and the same last rows, bit for bit."""
+    from lap_amd import ar_decode
+
     with model._serving_weights():
-        pre = model._ar_prefill(o)
-    mp.setattr(model, "_ar_prefill", lambda obs: pre)
+        pre = ar_decode.prefill(model, o)
+    mp.setattr(ar_decode, "prefill", lambda m, obs: pre)
     return pre
 
 
 def _twin_decode(hip, model, pre, steps, mode):
-    """`_fused_first_token` / `_fused_step` restated over the hip.decode_* calls (the bf16 kernels) with the weights `mode`
+    """`DecodeCtx.first_token` / `DecodeCtx.step` restated over the hip.decode_* calls (the bf16 kernels) with the weights `mode`
     quantises replaced by their dequantised bf16 twins, behind the prefill `pre`.  Returns (tokens, logits)."""
+    from lap_amd.ar_decode import DecodeCtx
+
     v = model.v
     KV = v.num_kv_heads
     with model._serving_weights():
@@ -229,7 +233,7 @@ def _twin_decode(hip, model, pre, steps, mode):
     else:
         hi, lo = model.W("llm/embed"), model.ps.w16lo("llm/embed")
     B, Pn, cache, kinfo_prefix, _, plen, x_last = pre
-    ctx = model._decode_ctx(B, Pn, steps)
+    ctx = DecodeCtx(model, B, Pn, steps)
     ctx.bind(cache, kinfo_prefix)
     ctx.plen.copy_(plen)
     hip.decode_init(ctx.state, ctx.plen, ctx.out)
@@ -324,7 +328,7 @@ def test_fp8_graph_follows_parameter_updates(hip, monkeypatch):
     dec = GraphedTokenDecoder(model, 3, 6, weights="fp8")
     first = dec(o)
     assert torch.equal(first, model.sample_tokens(0, o, max_decoding_steps=6, decode="fused", decode_weights="fp8"))
-    ptrs = {k: (r[1].data_ptr(), r[2].data_ptr()) for k, r in model._dec_w8.items()}
+    ptrs = {k: (r[0].data_ptr(), r[1].data_ptr()) for k, r in model.serving_cache.entries("dec8").items()}
     assert len(ptrs) == 4 * model.v.depth + 1
     # new parameters whose tokens differ: random weights echo the last prompt token, so blank its embedding row
     P2 = O.init_params(oc, seed=32)
@@ -334,7 +338,7 @@ def test_fp8_graph_follows_parameter_updates(hip, monkeypatch):
     P2[key] = E
     model.ps.load_reference_tree(P2)
     second = dec(o)
-    assert {k: (r[1].data_ptr(), r[2].data_ptr()) for k, r in model._dec_w8.items()} == ptrs      # re-quantised in place
+    assert {k: (r[0].data_ptr(), r[1].data_ptr()) for k, r in model.serving_cache.entries("dec8").items()} == ptrs      # re-quantised in place
     fresh = LAP(cfg, params=P2, device=DEV)
     assert torch.equal(second, fresh.sample_tokens(0, o, max_decoding_steps=6, decode="fused", decode_weights="fp8"))
     assert torch.equal(second, model.sample_tokens(0, o, max_decoding_steps=6, decode="fused", decode_weights="fp8"))
@@ -364,7 +368,7 @@ def test_fp8_decode_of_a_lora_model_reads_the_merged_weights(hip, monkeypatch):
     with model._serving_weights():
         merged = model.W("llm/0/wgu0")
     assert not torch.equal(merged, model.ps.w16("llm/0/wgu0"))                      # the adapters are live
-    assert torch.equal(model._dec_w8["llm/0/wgu0"][1].view(torch.uint8), _quant(merged)[0].view(torch.uint8))
+    assert torch.equal(model.serving_cache.entries("dec8")["llm/0/wgu0"][0].view(torch.uint8), _quant(merged)[0].view(torch.uint8))
 
 
 # ----------------------------------------------------------------------------------------------------------- full depth

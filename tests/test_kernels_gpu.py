@@ -1043,7 +1043,7 @@ def test_attention_serve_kernel_matches_reference_and_generic_path(hip, monkeypa
 
 
 @pytest.mark.parametrize("B,NH,Tp,Sq,Sk", [
-    (2, 8, 77, 1, 5),        # single-token decode, a few generated keys (lap.py:734-752 through LAP._vlm_decode_step)
+    (2, 8, 77, 1, 5),        # single-token decode, a few generated keys (lap.py:734-752 through ar_decode._vlm_decode_step)
     (1, 8, 300, 1, 200),     # ... many of them: the fresh keys need two runs
     (2, 8, 0, 3, 40),        # no cached prefix
     (1, 8, 560, 50, 50),     # the denoise step for reference

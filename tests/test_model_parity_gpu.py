@@ -704,7 +704,7 @@ def test_graphed_sampler_follows_parameter_updates_at_full_width(hip, monkeypatc
     o = to_observation(so | {"tokenized_langact_mask": None}, DEV)
     model = _engine(cfg, P)
     sampler = GraphedSampler(model, 1, 10).capture()
-    assert model._prefill_pw and model._packed_w is not None and model.serve_euler_embed      # the paths this test is about are live
+    assert model.serving_cache.entries("panel") and model.serving_cache.entries("chain") and model.serve_euler_embed      # the paths this test is about are live
     out1 = sampler(o, noise.to(DEV)).clone()
     assert torch.equal(out1, model.sample_actions(0, o, num_steps=10, noise=noise.to(DEV)))
     with torch.no_grad():
@@ -722,6 +722,45 @@ def test_graphed_sampler_follows_parameter_updates_at_full_width(hip, monkeypatc
             fresh.ps.master[name].mul_(1.03)
     fresh.ps.refresh_mirror_local()
     assert torch.equal(out2, fresh.sample_actions(0, o, num_steps=10, noise=noise.to(DEV)))
+
+
+def test_refresh_serve_caches_rebuilds_every_record_in_place(hip):
+    """After a parameter update `refresh_serve_caches()` leaves the store (lap_amd/serve_cache.py) with the same keys at the same
+    addresses, every record at the new version, and the serving paths compute what a model built on the new parameters computes."""
+    from lap_amd.serve_cache import _tensors
+
+    cfg = debug_model_cfg()
+    P = O.init_params(oracle_cfg(cfg), seed=19)
+    obs, _, noise, _ = make_inputs(cfg, B=2, ragged=True)
+    so = {k: v for k, v in obs.items() if k != "tokenized_langact_mask"}
+    o = to_observation(so | {"tokenized_langact_mask": None}, DEV)
+
+    def serve(m):
+        return m.sample_actions(0, o, num_steps=10, noise=noise.to(DEV)), m.sample_tokens(0, o, max_decoding_steps=3)
+
+    def updated(m):
+        with torch.no_grad():
+            for name in m.ps.master:
+                m.ps.master[name].mul_(1.03)
+        m.ps.refresh_mirror_local()
+        return m
+
+    def ptrs(m):
+        return {k: [t.data_ptr() for t in _tensors(v)] for k, v in m.serving_cache.entries().items()}
+
+    model = _engine(cfg, P)
+    a1, t1 = serve(model)
+    before = ptrs(model)
+    assert before and not model.serving_cache.stale()
+    updated(model)
+    assert sorted(model.serving_cache.stale(), key=repr) == sorted(before, key=repr)
+    model.refresh_serve_caches()
+    assert ptrs(model) == before and list(ptrs(model)) == list(before) and not model.serving_cache.stale()
+    a2, t2 = serve(model)
+    assert ptrs(model) == before
+    fa, ft = serve(updated(_engine(cfg, P)))
+    assert torch.equal(a2, fa) and torch.equal(t2, ft)
+    assert not torch.equal(a1, a2) and bool(torch.isfinite(a2).all())
 
 
 def test_sample_actions_matches_oracle(hip):
