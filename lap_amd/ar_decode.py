@@ -11,6 +11,7 @@ from typing import NamedTuple
 import torch
 
 from lap_amd import hip
+from lap_amd.loss import lm_logits
 from lap_amd.model import LAP, _gen
 from lap_amd.observation import preprocess_observation
 
@@ -129,13 +130,7 @@ def _vlm_decode_step(model: LAP, token, pos, step, cache, gen, qinfo_d, kinfo_pr
 def _lm_logits(model: LAP, rows):
     """final norm + Embedder.decode (gemma.py:153-154, 525-527): f32 logits [R, V]."""
     pl, _ = hip.rmsnorm_fwd(rows, scale=model.F("llm/final_norm"), save_rstd=False)
-    V, Dv = model.config.vocab_size, model.v.width
-    lg = torch.empty((rows.shape[0], V), dtype=torch.float32, device=model.device)
-    hip.gemm(pl, model.W("llm/embed"), lg, M=rows.shape[0], N=V, K=Dv, lda=Dv, ldb=Dv, ldc=V)
-    lo = model.ps.w16lo("llm/embed")      # the f32 table as hi + lo (see _loss_impl)
-    if lo is not None:
-        hip.gemm(pl, lo, lg, M=rows.shape[0], N=V, K=Dv, lda=Dv, ldb=Dv, ldc=V, accum=True)
-    return lg
+    return lm_logits(model, pl, 0, model.config.vocab_size)      # the f32 table as hi + lo, as in the training loss
 
 
 def _sample_eager(model: LAP, rng, observation, *, max_decoding_steps: int, temperature: float, collect, device_sampler: bool):

@@ -4,7 +4,9 @@ Keeps the reference's model surface (src/lap/models/lap.py):
     compute_loss(rng, observation, actions, *, train=False, ...) -> (loss, metrics)      lap.py:380-602
     sample_actions(rng, observation, *, num_steps=10, noise=None) -> [b, ah, ad]         lap.py:605-675
 and adds `loss_and_grad(...)`, the fused forward + hand-written backward that the train step uses (the
-reference gets it from nnx.value_and_grad, scripts/train.py:358-361).
+reference gets it from nnx.value_and_grad, scripts/train.py:358-361).  `_loss_impl` is the schedule of that step (streams, collectives,
+the order of the passes); the language head, the action head and the sample-weight mixing it calls are in lap_amd/loss.py, token
+decoding is in lap_amd/ar_decode.py.
 
 Everything numeric is a call into liblap_hip.so (lap_amd/hip.py); torch only owns device memory, the stream,
 and a few O(batch x tokens) integer tensors (masks -> per-token info words, positions).  There is no autograd
@@ -29,6 +31,7 @@ import torch
 
 from lap_amd import hip
 from lap_amd.config import LAPConfig, get_gemma_config, get_siglip_config
+from lap_amd.loss import ActionHead, LangHead, action_head_bwd, action_head_fwd, lang_head_bwd, lang_head_fwd, mix_sample_weights
 from lap_amd.observation import CoTObservation, preprocess_observation
 from lap_amd.params import LORA_PROJ, ParamStore, lora_geometry
 from lap_amd.serve_cache import ServeCache
@@ -1127,146 +1130,14 @@ class LAP:
 
         fb = lambda t: t.to(torch.float32)
         sm = obs.sample_mask if obs.sample_mask is not None else torch.ones(B, dtype=torch.bool, device=dev)
-        lang_loss = torch.zeros(B, dtype=torch.float32, device=dev)
-        sel = pl = None
-        verbose_metrics = {}
-        Dv, V = self.v.width, cfg.vocab_size
-        if lang_on:
-            # ---- language loss (lap.py:209-289): rows Pn-Lt .. Pn-2 predict tokens 1 .. Lt-1
-            Lt = obs.tokenized_prompt.shape[1]
-            loss_mask = obs.tokenized_langact_mask[:, 1:] & obs.tokenized_prompt_mask[:, 1:]
-            if obs.token_loss_mask is not None:
-                loss_mask = loss_mask & obs.token_loss_mask[:, 1:]
-            lm_bool = loss_mask if obs.sample_mask is None else loss_mask & obs.sample_mask[:, None]
-            lm = lm_bool.to(torch.float32)
-            cnt = torch.clamp(lm.sum(-1), min=1.0)
-            # Only rows whose loss mask is set matter (the reference multiplies the other rows' cross entropy by 0): with the host
-            # hint `loss_rows_max` the head runs on that many rows per sample — the masked ones first (stable order), padded with
-            # rows of weight 0 — instead of all Lt - 1 (BASELINE shapes: 16 of 47).  A hint smaller than a sample's count would drop
-            # tokens silently, so the device-side check turns the loss into NaN instead (no host sync).
-            n_sel = observation.loss_rows_max if observation.loss_rows_max is not None else obs.loss_rows_max
-            # verbose (lap.py:240-277): the class masks lie inside the reasoning mask but not inside token_loss_mask (reasoning
-            # dropout), so the rows are chosen by loss mask | class masks and the hint is `metric_rows_max`, counted over that union
-            # (no hint: all Lt - 1 rows).  The loss still weighs the rows by `lm` alone.
-            row_mask = lm_bool
-            if verbose:
-                def prep(mk):       # prepare_mask, lap.py:241-247
-                    if mk is None:
-                        return None
-                    mk = mk[:, 1:].to(dev, torch.bool)
-                    return (mk & obs.sample_mask[:, None] if obs.sample_mask is not None else mk).contiguous()
-
-                cls_masks = [prep(obs.critical_token_mask), prep(obs.number_token_mask), prep(obs.direction_token_mask)]
-                for mk in cls_masks:
-                    if mk is not None:
-                        row_mask = row_mask | mk
-                n_sel = observation.metric_rows_max if observation.metric_rows_max is not None else obs.metric_rows_max
-            sel = None
-            if n_sel is not None and 0 < n_sel < Lt - 1 and os.environ.get("LAP_LM_ALL_ROWS", "0") != "1":
-                sel = torch.sort((~row_mask).to(torch.uint8), dim=1, stable=True).indices[:, :n_sel]          # [B, n_sel] in 0 .. Lt-2
-                hint_too_small = ((row_mask.sum(-1) if verbose else lm.sum(-1)) > n_sel).any()
-                Ls = n_sel
-                rowid = (torch.arange(B, device=dev) * Pn + (Pn - Lt))[:, None] + sel
-                rows = xf0.index_select(0, rowid.view(-1))
-                targets = obs.tokenized_prompt[:, 1:].gather(1, sel).to(torch.int32).contiguous().view(-1)
-                lm_s = lm.gather(1, sel)
-            else:
-                Ls = Lt - 1
-                rows = torch.empty((B * Ls, Dv), dtype=torch.bfloat16, device=dev)
-                hip.copy_rows_bf16(xf0, rows, B * Ls, Ls, Dv, Pn, Pn - Lt, Ls, 0)
-                targets = obs.tokenized_prompt[:, 1:].to(torch.int32).contiguous().view(-1)
-                lm_s = lm
-            R = B * Ls
-            pl, rstd_pl = hip.rmsnorm_fwd(rows, scale=self.F("llm/final_norm"), save_rstd=backward)
-            # Embedder.decode (gemma.py:153-154) multiplies the bf16 pre-logits by the F32 table: table = hi + lo, two bf16 planes
-            # (16 mantissa bits; the products are exact in the f32 accumulator) -> logits to ~2^-17 of the f32 product
-            table16, table_lo = self.W("llm/embed"), self.ps.w16lo("llm/embed")
-            if os.environ.get("LAP_LM_NO_LO", "0") == "1":       # A/B switch: the bf16 mirror alone (the pre-round-3 dtype flow)
-                table_lo = None
-            # vocab chunks: one when [R, V] bf16 stays below the 2 GiB buffer-descriptor range of the GEMM (B <= 32 here)
-            vc_max = max(1024, (int(1.5e9) // (2 * R)) // 1024 * 1024)
-            chunks = [(v0, min(vc_max, V - v0)) for v0 in range(0, V, vc_max)]
-            m = torch.full((R,), -3.0e38, dtype=torch.float32, device=dev)
-            lsum = torch.zeros(R, dtype=torch.float32, device=dev); tl = torch.zeros(R, dtype=torch.float32, device=dev)
-            amax = torch.empty(R, dtype=torch.int32, device=dev) if verbose else None      # predictions from the same pass
-            logit_chunks = []
-            for v0, vc in chunks:
-                lg = torch.empty((R, vc), dtype=torch.float32, device=dev)
-                hip.gemm(pl, table16[v0:v0 + vc], lg, M=R, N=vc, K=Dv, lda=Dv, ldb=Dv, ldc=vc)
-                if table_lo is not None:
-                    hip.gemm(pl, table_lo[v0:v0 + vc], lg, M=R, N=vc, K=Dv, lda=Dv, ldb=Dv, ldc=vc, accum=True)
-                if verbose:
-                    hip.ce_chunk_update_argmax(lg, targets, m, lsum, tl, amax, v0)
-                else:
-                    hip.ce_chunk_update(lg, targets, m, lsum, tl, v0)
-                logit_chunks.append(lg if backward else None)
-            nll = (m + torch.log(lsum) - tl).view(B, Ls)
-            lang_loss = (nll * lm_s).sum(-1) / cnt
-            if sel is not None:
-                lang_loss = torch.where(hint_too_small, torch.full_like(lang_loss, float("nan")), lang_loss)
-            if verbose:
-                verbose_metrics = self._token_metrics(amax, targets, nll, lm, sel, cls_masks, obs.tokenized_prompt[:, 1:])
-                if collect is not None:
-                    collect["predictions"], collect["sel"] = amax.view(B, Ls), sel
-
-        # ---- action loss (lap.py:291-301)
-        pre1 = v_t = None
-        if act_on:
-            if cfg.pi05:
-                pre1, rstd_p1 = hip.rmsnorm_fwd(xf1, mod=self._mod_slot(mod, 2 * self.v.depth), rows_per_sample=S, save_rstd=backward)
-            else:       # plain final norm; the action head reads the last S rows of each sample (`suffix_out[:, -ah:]`, lap.py:298)
-                pre1_all, rstd_p1 = hip.rmsnorm_fwd(xf1, scale=self.F("llm/final_norm1"), save_rstd=backward)
-                pre1 = pre1_all.view(B, Sx, self.e.width)[:, 1:].reshape(B * S, self.e.width).contiguous()
-            pre1f = hip.cast_bf16_to_f32(pre1)
-            v_t = self._lin32(pre1f, "act/out_w", "act/out_b")  # [B*S, ad]
-        # ---- combination (lap.py:472-596).  Per-sample weights: language loss x {language, VQA (optionally per dataset),
-        # prediction} weight by sample kind; action loss only on samples that are neither VQA nor prediction samples.
-        mixing = lang_on and (cfg.enable_vqa_training or cfg.enable_prediction_training)
-        vqa = obs.is_vqa_sample.to(dev, torch.bool) if (cfg.enable_vqa_training and obs.is_vqa_sample is not None) else None
-        pred = obs.is_prediction_sample.to(dev, torch.bool) if (cfg.enable_prediction_training and obs.is_prediction_sample is not None) else None
-        extra_metrics = {}
-        if mixing:
-            vqa_m = (vqa if vqa is not None else torch.zeros(B, dtype=torch.bool, device=dev)) & sm      # lap.py:480-486
-            pred_m = (pred if pred is not None else torch.zeros(B, dtype=torch.bool, device=dev)) & sm
-            lang_m = ~((vqa if vqa is not None else vqa_m) | (pred if pred is not None else pred_m)) & sm
-            vqa_w = torch.full((B,), cfg.vqa_loss_weight, dtype=torch.float32, device=dev)               # lap.py:526-543
-            if cfg.enable_vqa_training and cfg.vqa_loss_weights and obs.vqa_dataset_id is not None:
-                from lap_amd.config import VQA_DATASET_ID_MAP
-
-                ids = obs.vqa_dataset_id.to(dev)
-                for name, wgt in cfg.vqa_loss_weights.items():
-                    if name in VQA_DATASET_ID_MAP:
-                        vqa_w = torch.where(ids == VQA_DATASET_ID_MAP[name], torch.full_like(vqa_w, float(wgt)), vqa_w)
-            wl = vqa_w * fb(vqa_m) + cfg.prediction_loss_weight * fb(pred_m) + cfg.language_loss_weight * fb(lang_m)
-            act_mask = ~vqa_m & ~pred_m          # the masks were AND-ed with the sample mask before this point (lap.py:484-485,562-566)
-            n_act_loc = fb(sm).sum()
-            for pfx, msk in (("vqa_", vqa_m), ("pred_", pred_m), ("langact_", lang_m)):   # metrics.py:49-56 (per-rank values)
-                if (pfx == "vqa_" and not cfg.enable_vqa_training) or (pfx == "pred_" and not cfg.enable_prediction_training):
-                    continue
-                extra_metrics[pfx + "loss"] = (lang_loss * fb(msk)).sum() / torch.clamp(fb(msk).sum(), min=1.0)
-                extra_metrics[pfx + "num_samples"] = fb(msk).sum()
-                extra_metrics[pfx + "sample_portion"] = fb(msk).sum() / torch.clamp(n_act_loc, min=1.0)
-            if cfg.enable_vqa_training and obs.vqa_dataset_id is not None:
-                # metrics.py:59-73 (lap.py:500-508): loss and sample count per VQA dataset, one [B, K] indicator for all K datasets
-                from lap_amd.config import VQA_DATASET_ID_MAP
-
-                names = list(VQA_DATASET_ID_MAP)
-                idv = torch.tensor([VQA_DATASET_ID_MAP[n] for n in names], dtype=torch.int64, device=dev)
-                ind = fb((obs.vqa_dataset_id.to(dev).to(torch.int64).view(B, 1) == idv.view(1, -1)) & vqa_m.view(B, 1))
-                ns = ind.sum(0)
-                ls = (lang_loss.view(1, B) @ ind).view(-1) / torch.clamp(ns, min=1.0)
-                for k, n in enumerate(names):
-                    extra_metrics[f"vqa_{n}_loss"] = ls[k]
-                    extra_metrics[f"vqa_{n}_num_samples"] = ns[k]
-            extra_metrics["active_num_samples"] = n_act_loc
-            extra_metrics["active_sample_portion"] = n_act_loc / max(B, 1)
-        else:   # (also the langact-off branch: the VQA / prediction masks reach the action loss as they came, lap.py:557-566)
-            wl = torch.full((B,), cfg.language_loss_weight if lang_on else 0.0, dtype=torch.float32, device=dev)
-            act_mask = torch.ones(B, dtype=torch.bool, device=dev)
-            if vqa is not None:
-                act_mask = act_mask & ~vqa
-            if pred is not None:
-                act_mask = act_mask & ~pred
+        head = lang_head_fwd(self, xf0, obs, observation, B, Pn, backward=backward, verbose=verbose, collect=collect) if lang_on else \
+            LangHead(torch.zeros(B, dtype=torch.float32, device=dev))
+        ah = action_head_fwd(self, xf1, mod, B, S, Sx, backward=backward) if act_on else ActionHead()
+        lang_loss, v_t = head.lang_loss, ah.v_t
+        # the reference's vqa_mask / pred_mask (lap.py:400-409): only where that kind of training is on
+        wl, act_mask, mixing, extra_metrics = mix_sample_weights(
+            cfg, lang_loss, sm, obs.is_vqa_sample if cfg.enable_vqa_training else None,
+            obs.is_prediction_sample if cfg.enable_prediction_training else None, obs.vqa_dataset_id, lang_on=lang_on)
         n_active = torch.clamp(self.comm.all_reduce_sum(fb(sm).sum().view(1)), min=1.0) if obs.sample_mask is not None else \
             self.comm.all_reduce_sum(torch.tensor([float(B)], device=dev))
         # lang_term: sum / active samples, or the batch mean without a sample mask (lap.py:579-596; the action-off branch's
@@ -1283,11 +1154,11 @@ class LAP:
         loss = self.comm.all_reduce_sum((lang_term + action_term).view(1)).view(())
         metrics = {"lang_loss": lang_loss.mean(), "action_loss": (act_loss * fb(act_mask)).sum() / torch.clamp(fb(act_mask).sum(), min=1.0),
                    "langact_loss": (lang_loss * fb(sm)).sum() / torch.clamp(fb(sm).sum(), min=1.0) if not mixing else extra_metrics["langact_loss"],
-                   **{k: v for k, v in extra_metrics.items() if k != "langact_loss"}, **verbose_metrics}
+                   **{k: v for k, v in extra_metrics.items() if k != "langact_loss"}, **head.verbose_metrics}
         if verbose:     # lap.py:569-577: weighted language term plus the weighted, masked action term of each sample
             metrics["per_sample_loss"] = wl * lang_loss + (cfg.action_loss_weight * act_loss * fb(act_mask) if act_on else 0.0)
         if collect is not None:
-            collect.update(pl=pl, pre1=pre1, v_t=v_t.view(B, S, ad) if v_t is not None else None, u_t=u_t, per_sample_lang=lang_loss,
+            collect.update(pl=head.pl, pre1=ah.pre1, v_t=v_t.view(B, S, ad) if v_t is not None else None, u_t=u_t, per_sample_lang=lang_loss,
                            per_sample_action=act_loss)
         if not backward:
             return loss, metrics
@@ -1295,61 +1166,18 @@ class LAP:
         # =============================== backward ===============================
         self.comm.before_backward()
         self._wg_begin()
-        We = self.e.width
-        dmod = dx1 = None
-        if act_on:      # action head
-            dpre1f = self._lin32_bwd(pre1f, dv.view(B * S, ad), "act/out_w", "act/out_b")
-            if cfg.pi05:
-                dmod = torch.zeros(mod.shape, dtype=torch.float32, device=dev)
-                dx1 = hip.rmsnorm_bwd(xf1, hip.cast_f32_to_bf16(dpre1f), rstd_p1, mod=self._mod_slot(mod, 2 * self.v.depth), rows_per_sample=S,
-                                      dmod=self._mod_slot(dmod, 2 * self.v.depth))
-            else:
-                dall = torch.zeros((B, Sx, We), dtype=torch.bfloat16, device=dev)      # (the state token's row of the final norm has no consumer)
-                dall[:, 1:] = hip.cast_f32_to_bf16(dpre1f).view(B, S, We)
-                dx1 = hip.rmsnorm_bwd(xf1, dall.view(B * Sx, We), rstd_p1, scale=self.F("llm/final_norm1"), dscale=self.G("llm/final_norm1"))
+        dx1, dmod = action_head_bwd(self, ah, xf1, mod, dv, B, S, Sx) if act_on else (None, None)
         skip_prefix = self._prefix_frozen()
         dx0 = None
-        if not skip_prefix and not lang_on:
+        if not skip_prefix and lang_on:
+            dx0 = lang_head_bwd(self, head, wl, n_active, B, Pn)
+        elif not skip_prefix:
             # no language loss: the prefix stream's only cotangents are those of its keys / values under the action queries
-            dx0 = torch.zeros((B * Pn, Dv), dtype=torch.bfloat16, device=dev)
+            dx0 = torch.zeros((B * Pn, self.v.width), dtype=torch.bfloat16, device=dev)
             # the LM-head weight-gradient product is what overwrites (beta = 0) the embedding table's f32 gradient buffer; without it the
             # scatter-add of _embed_prefix_bwd would accumulate onto the previous step's values
             if self.ps.is_trainable("llm/embed"):
                 self.G("llm/embed").zero_()
-        elif not skip_prefix:
-            # language head: dlogits = w * (softmax - onehot); w = d loss / d nll.  The cotangent of the f32 logits stays f32 in the
-            # reference (d pre_logits = dlogits . table, d table = dlogits^T . pre_logits in f32): dlogits = dh + dl (two bf16
-            # planes), table = hi + lo -> dh.hi + dl.hi + dh.lo (dl.lo is 2^-16 of the sum) and (dh + dl)^T . pre_logits
-            w = (wl[:, None] * lm_s / cnt[:, None] / n_active).contiguous().view(-1)
-            hilo = table_lo is not None
-            # hi / lo planes stacked along the rows, [dh; dl]: ONE weight-gradient product over 2R rows against [pl; pl] (the f32
-            # [V, D] output is written once instead of accumulated onto), ONE data-gradient product [dh; dl] . hi (the table plane
-            # is read once), plus dh . lo onto its first half
-            RR = 2 * R if hilo else R
-            pl2 = torch.cat([pl, pl], 0) if hilo else pl
-            dpl32 = torch.empty((RR, Dv), dtype=torch.float32, device=dev) if (len(chunks) > 1 or hilo) else None
-            gE = self.G("llm/embed")
-            for ci, (v0, vc) in enumerate(chunks):
-                dlogits = torch.empty((RR, vc), dtype=torch.bfloat16, device=dev)
-                hip.ce_chunk_grad(logit_chunks[ci], targets, m, lsum, w, dlogits[:R], v0, dlogits_lo=dlogits[R:] if hilo else None)
-                logit_chunks[ci] = None
-                if self.ps.is_trainable("llm/embed"):
-                    hip.linear_wgrad(dlogits, pl2, gE[v0:v0 + vc])
-                if dpl32 is None:
-                    dpl = hip.linear_dgrad(dlogits, table16[v0:v0 + vc])
-                else:
-                    hip.linear_dgrad(dlogits, table16[v0:v0 + vc], out=dpl32, accum=ci > 0)
-                    if hilo:
-                        hip.linear_dgrad(dlogits[:R], table_lo[v0:v0 + vc], out=dpl32[:R], accum=True)
-                del dlogits
-            if dpl32 is not None:
-                dpl = hip.cast_f32_to_bf16(dpl32[:R] + dpl32[R:] if hilo else dpl32)
-            drows = hip.rmsnorm_bwd(rows, dpl, rstd_pl, scale=self.F("llm/final_norm"), dscale=self.G("llm/final_norm"))
-            dx0 = torch.zeros((B * Pn, Dv), dtype=torch.bfloat16, device=dev)
-            if sel is not None:
-                dx0.index_copy_(0, rowid.view(-1), drows)
-            else:
-                hip.copy_rows_bf16(drows, dx0, R, Lt - 1, Dv, Lt - 1, 0, Pn, Pn - Lt)
         dx0, dx1 = self._llm_bwd(lctx, dx0, dx1, mod, dmod, pos, qinfo, kinfo, B, Pn, Sx)
         sfx = None
         if act_on and cfg.pi05:
@@ -1368,7 +1196,7 @@ class LAP:
     def compute_loss(self, rng, observation, actions, *, train: bool = False, stage_config=None, verbose_mode=None,
                      return_augmented_images: bool = False, noise=None, time=None, collect=None):
         """lap.py:380-602.  rng: int seed or torch.Generator.  `noise` / `time` may be given explicitly (parity tests).
-        verbose_mode (None: the config's, lap.py:393-394) adds the token-accuracy metrics and `per_sample_loss` (_token_metrics)."""
+        verbose_mode (None: the config's, lap.py:393-394) adds the token-accuracy metrics and `per_sample_loss` (loss._token_metrics)."""
         verbose = bool(self.config.verbose_mode if verbose_mode is None else verbose_mode)
         return self._loss_impl(rng, observation, actions, train=train, noise=noise, time=time, backward=False, collect=collect,
                                verbose=verbose)
@@ -1379,24 +1207,6 @@ class LAP:
         config's `verbose_mode` (the reference's train step runs with the class attribute, scripts/train.py:351)."""
         return self._loss_impl(rng, observation, actions, train=train, noise=noise, time=time, backward=True, collect=collect,
                                verbose=bool(self.config.verbose_mode))
-
-    def _token_metrics(self, amax, targets, nll, lm, sel, cls_masks, labels):
-        """compute_token_accuracy_metrics (metrics.py:7-45) from the LM head's argmax: per-token loss and per-sample (correct, total)
-        counts in one kernel (lap_token_metrics); the batch accuracies from the counts' totals, all-reduced in one collective so that
-        under FSDP they are the global values the reference computes."""
-        crit, num, dirn = cls_masks
-        ptl, counts = hip.token_metrics(amax, targets, nll.reshape(-1).contiguous(), lm.contiguous(),
-                                        sel=sel.to(torch.int32).contiguous() if sel is not None else None,
-                                        critical=crit, number=num, direction=dirn)
-        tot = self.comm.all_reduce_sum(counts.sum(0).reshape(8)).view(4, 2)
-        acc = tot[:, 0] / torch.clamp(tot[:, 1], min=1.0)
-        out = {"token_accuracy": acc[0], "per_token_loss": ptl, "labels": labels}
-        for k, (name, mk) in enumerate((("critical", crit), ("number", num), ("direction", dirn)), start=1):
-            if mk is not None:
-                out[f"{name}_token_accuracy"] = acc[k]
-                out[f"per_sample_{name}_correct"] = counts[:, k, 0]
-                out[f"per_sample_{name}_total"] = counts[:, k, 1]
-        return out
 
     # ================================================================== serving
     @torch.no_grad()

@@ -36,8 +36,9 @@ def test_ce_update_argmax_matches_ce_update_and_argmax_at_full_vocab(hip):
     lg[5, 64 * 4] = lg[5, 4] = big                      # a tie across lanes of one wave
     ref = torch.argmax(lg, dim=1).to(torch.int32)
     assert ref[:6].tolist() == [100, 65535, 70000, 8, 0, 4]
-    vc_max = max(1024, (int(1.5e9) // (2 * R)) // 1024 * 1024)           # the model's chunking (model.py): one chunk at R = 512
-    for chunks in ([(v0, min(vc_max, V - v0)) for v0 in range(0, V, vc_max)],
+    from lap_amd.loss import vocab_chunks
+
+    for chunks in (vocab_chunks(R, V),                                    # the model's chunking: one chunk at R = 512
                    [(v0, min(65536, V - v0)) for v0 in range(0, V, 65536)]):
         st, sa, amax = _ce_pair(hip, lg, targets, chunks)
         for a, b in zip(st, sa):

@@ -662,6 +662,56 @@ def test_language_head_on_loss_rows_only_equals_all_rows(hip):
     assert CoTObservation.from_dict(d, device="cpu").loss_rows_max == n_max
 
 
+def test_language_head_in_several_vocab_chunks_equals_one_chunk(hip, monkeypatch):
+    """The language head over two vocabulary chunks (`loss.vocab_chunks` capped at 1024 of 2048 columns) against one chunk, forward
+    and backward, with the verbose argmax carried across the chunks.  The logits are the same GEMM columns and the cross-entropy
+    kernel's running max, sum and argmax are exact across column splits, so predictions and integer metrics are equal; losses agree
+    to the f32 summation order (the bound of the rows-only test); the table's gradient is exact (each row lies in one chunk), the
+    data gradient sums two products in f32 instead of one."""
+    from lap_amd import loss as loss_mod
+
+    cfg = debug_model_cfg(vocab_size=2048, verbose_mode=True)
+    P = O.init_params(oracle_cfg(cfg), seed=29)
+    obs, actions, noise, time = make_inputs(cfg, B=3, ragged=True)
+    model = _engine(cfg, P)
+    o = to_observation(obs, DEV)
+    seen = []
+
+    def run():
+        for g in model.ps.grad.values():
+            g.zero_()
+        col = {}
+        loss, met = model.loss_and_grad(0, o, actions.to(DEV), noise=noise.to(DEV), time=time.to(DEV), collect=col)
+        torch.cuda.synchronize()
+        return (loss.clone(), {k: v.clone() for k, v in met.items()}, {k: col[k].clone() for k in ("per_sample_lang", "predictions")},
+                {n: model.ps.g(n).detach().clone() for n in model.ps.names()})
+
+    one_chunk = loss_mod.vocab_chunks
+
+    def two_chunks(R, V):
+        seen.append(one_chunk(R, V, cap_cols=1024))
+        return seen[-1]
+
+    l1, m1, c1, g1 = run()
+    assert len(one_chunk(3 * (cfg.max_token_len - 1), cfg.vocab_size)) == 1
+    monkeypatch.setattr(loss_mod, "vocab_chunks", two_chunks)
+    l2, m2, c2, g2 = run()
+    assert seen == [[(0, 1024), (1024, 1024)]]
+    assert torch.equal(c2["predictions"], c1["predictions"])
+    close = lambda a, b: torch.allclose(a, b, rtol=2e-6, atol=1e-7)
+    print(f"loss {l1.item()!r} / {l2.item()!r}; per_sample_lang diff {(c2['per_sample_lang'] - c1['per_sample_lang']).abs().max().item():.3e}")
+    assert close(l2, l1) and close(c2["per_sample_lang"], c1["per_sample_lang"])
+    assert set(m1) == set(m2)
+    for k in m1:
+        if not m1[k].dtype.is_floating_point or k.startswith("per_sample_") and k.endswith(("_correct", "_total")) or k == "labels":
+            assert torch.equal(m2[k], m1[k]), k       # counts and labels
+        else:
+            assert close(m2[k], m1[k]), k
+    for n in g1:
+        print(f"grad {n}: equal {torch.equal(g2[n], g1[n])} rel {rel(g2[n], g1[n]):.3e}")
+        assert torch.equal(g2[n], g1[n]) or rel(g2[n], g1[n]) < 2e-5, n
+
+
 def test_graphed_sampler_replay_equals_eager_and_oracle(hip):
     """BASELINE config 4: the hipGraph-captured batch-1 sampler (serve.GraphedSampler).  Capture once, replay for two
     DIFFERENT requests: every replay must equal the eager sampler bit for bit (same kernels, same order) and agree
