@@ -37,6 +37,7 @@
 #include "common.hpp"
 #include <stdlib.h>
 #include "gemm_common.hpp"
+#include "gemm_route.hpp"
 
 // The staged epilogue's full-row stores go out nontemporal (C is written once and read from HBM by its consumer anyway; the
 // operand panels keep the L2): -0.3 .. -1.0 ms per train step in three A/B pairs, serving unchanged.  LAP_GEMM_NT_STORE=0: plain.
@@ -1458,386 +1459,8 @@ __global__ __launch_bounds__(256) void splitk_tail_reduce_kernel(GemmParams p, i
   }
 }
 
-// Tile heuristic between the two production shapes (measured on MI355X, tools/bench_kernels.py):
-//   tile 5 = 256x256, 16 waves, 1 block/CU  — 1.0-1.3 PF when its rounds over the 256 CUs are well filled;
-//   tile 6 = 128x128,  8 waves, 2 blocks/CU — 0.9-1.0 PF, finer quantisation, better for short K / few tiles.
-// score = round-fill efficiency x relative kernel efficiency (which grows with K for the big tile).
-int pick_tile(int M, int N, int K) {
-  const long long t5 = (long long)((M + 255) / 256) * ((N + 255) / 256);
-  const long long t6 = (long long)((M + 127) / 128) * ((N + 127) / 128);
-  const double fill5 = (double)t5 / (256.0 * ((t5 + 255) / 256));
-  const double fill6 = (double)t6 / (512.0 * ((t6 + 511) / 512));
-  const double eff5 = 1.15 + 0.13 * (K >= 8192 ? 1.0 : K / 8192.0);
-  if (t6 <= 256) return 6;  // not even one round of small tiles: finest granularity (+ split-K) wins
-  return (fill5 * eff5 > fill6) ? 5 : 6;
-}
-
-// Automatic two-phase split-K (only when the caller lends scratch): fills the last round of a poorly filled
-// 256x256 grid, or spreads a GEMM with a handful of output tiles (skinny-M serving, small weights) over the chip.
-int pick_ksplit(int tile, int M, int N, int K, long long scratch_bytes, bool fwd_layout) {
-  const long long cap = scratch_bytes / ((long long)M * N * 4);
-  if (cap < 2) return 1;
-  if (tile == 5 || tile == 8) {
-    const long long t5 = (long long)((M + 255) / 256) * ((N + 255) / 256);
-    const double fill1 = (double)t5 / (256.0 * ((t5 + 255) / 256));
-    if (fill1 >= 0.8 || K < 4096) return 1;
-    int best = 1;
-    double score = fill1;
-    for (int sp = 2; sp <= 4 && sp <= cap; ++sp) {
-      const long long w = t5 * sp;
-      const double sc = (double)w / (256.0 * ((w + 255) / 256)) - 0.02 * sp;
-      if (sc > score) { score = sc; best = sp; }
-    }
-    return best;
-  }
-  if (tile == 6 || tile == 0) {
-    const long long t6 = (long long)((M + 127) / 128) * ((N + 127) / 128);
-    // windows tuned per regime (tools/gemm_sweep.py): the serving prefill (forward layout, M <= 1024) splits up to 256
-    // tiles; the train step's action-expert GEMMs (M = 1600: 104 tiles walking K = 2048 .. 8192) up to 128
-    const bool serving = fwd_layout && M <= 1024;
-    if (t6 > (serving ? 256 : 128) || K < 1024) return 1;
-    // Few tiles (serving prefill at M ~ 512, small weights): a 128x128 block that walks all of K loads 512 * K bytes through
-    // ONE CU's vector-memory path (~45 GB/s, tools/bench_skinny.py) — 22 us at K = 2048 whatever the MFMA rate.  Splitting K
-    // until the chip holds two blocks per CU shortens that chain; the reduce pass costs ~5 us + the slab traffic.
-    long long sp = (t6 > 96 ? 512 : 256) / t6;
-    if (sp > K / 256) sp = K / 256;
-    if (!serving && t6 > 96 && sp > K / 1024) sp = K / 1024;
-    if (sp > 16) sp = 16;
-    if (sp > cap) sp = cap;
-    return sp < 2 ? 1 : (int)sp;
-  }
-  return 1;
-}
-
-}  // namespace
-
-static int g_gemm_dbg = 0;
-
-extern "C" int lap_gemm_set_debug(int bits) {   // ablation knob; has an effect in LAP_GEMM_EXPERIMENTAL builds only
-#ifdef LAP_GEMM_EXPERIMENTAL
-  g_gemm_dbg = bits;
-  return LAP_OK;
-#else
-  return bits ? LAP_ERR_ARG : LAP_OK;
-#endif
-}
-
-// Weight gradient dW [M][N] (f32) = A^T B over K rows (A [K][M], B [K][N]) with its sum of squares folded in where the assembly
-// kernel takes the product (*folded = 1: *sumsq has received sum(dW^2)); every other shape runs as lap_gemm_bf16_ex would run it and
-// leaves the norm to the caller (*folded = 0).  The routing rule is the plain-product rule of lap_gemm_bf16_ex.
-extern "C" int lap_gemm_wgrad_f32(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc, float* sumsq,
-                                  int* folded, void* scratch, long long scratch_bytes, void* stream) {
-  if (!folded) return LAP_ERR_ARG;
-  *folded = 0;
-  static const bool no_asm = getenv("LAP_GEMM_NO_ASM") != nullptr;
-  if (sumsq && !no_asm && M > 0 && N > 0 && lap_gemm_asm_ok(0, 0, 1, M, N, K, lda, ldb, ldc)) {
-    const long long t5 = (long long)(M / 256) * (N / 256);
-    const double fill = (double)t5 / (256.0 * ((t5 + 255) / 256));
-    if (t5 >= 128 && fill >= 0.8) {
-      *folded = 1;
-      return lap_gemm_asm_wgrad(A, B, C, M, N, K, lda, ldb, ldc, sumsq, stream);
-    }
-  }
-  return lap_gemm_bf16_ex(A, B, C, nullptr, nullptr, M, N, K, lda, ldb, ldc, 0, 1.0f, 0, 0, LAP_GEMM_OUT_F32, -1, 0, scratch, scratch_bytes, stream);
-}
-
-// The same for a weight gradient stored as bf16 (dW [M][N] bf16; ParamStore.grad_dtype): the bf16 assembly kernels fold the squares of
-// their f32 accumulators.
-extern "C" int lap_gemm_wgrad_bf16(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc, float* sumsq,
-                                   int* folded, void* scratch, long long scratch_bytes, void* stream) {
-  if (!folded) return LAP_ERR_ARG;
-  *folded = 0;
-  static const bool no_asm = getenv("LAP_GEMM_NO_ASM") != nullptr;
-  if (sumsq && !no_asm && M > 0 && N > 0 && lap_gemm_asm_ok(0, 0, 0, M, N, K, lda, ldb, ldc)) {
-    const long long t5 = (long long)(M / 256) * (N / 256);
-    const double fill = (double)t5 / (256.0 * ((t5 + 255) / 256));
-    if (t5 >= 128 && fill >= 0.8) {
-      *folded = 1;
-      return lap_gemm_asm_wgrad_b16(A, B, C, M, N, K, lda, ldb, ldc, sumsq, stream);
-    }
-  }
-  return lap_gemm_bf16_ex(A, B, C, nullptr, nullptr, M, N, K, lda, ldb, ldc, 0, 1.0f, 0, 0, 0, -1, 0, scratch, scratch_bytes, stream);
-}
-
-extern "C" int lap_gemm_bf16_ex(const void* A, const void* B, void* C, const void* bias, const void* residual,
-                                int M, int N, int K, int lda, int ldb, int ldc, int ldr, float alpha,
-                                int a_kc, int b_kc, int flags, int tile, int ksplit, void* scratch,
-                                long long scratch_bytes, void* stream) {
-  if (M <= 0 || N <= 0 || K <= 0) return LAP_ERR_ARG;
-  // 16-byte chunk granularity along each contiguous axis; 4-wide epilogue stores.
-  if ((N & 3) || (ldc & 3) || (lda & 7) || (ldb & 7)) return LAP_ERR_ARG;
-  if (a_kc ? (K & 7) : (M & 7)) return LAP_ERR_ARG;
-  if (b_kc ? (K & 7) : (N & 7)) return LAP_ERR_ARG;
-  if (residual && (ldr & 3)) return LAP_ERR_ARG;
-  if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15) return LAP_ERR_ARG;
-  // 31-bit byte offsets inside one buffer descriptor.
-  if ((long long)(a_kc ? M : K) * lda * 2 >= 0x7fffffffLL) return LAP_ERR_ARG;
-  if ((long long)(b_kc ? N : K) * ldb * 2 >= 0x7fffffffLL) return LAP_ERR_ARG;
-  const bool f32 = flags & LAP_GEMM_OUT_F32;
-  if ((flags & LAP_GEMM_ACCUM) && !f32) return LAP_ERR_ARG;
-  if ((flags & LAP_GEMM_GELU) && f32) return LAP_ERR_ARG;
-  if (tile < -1 || tile > 19 || ksplit < 0) return LAP_ERR_ARG;
-  if (flags & LAP_GEMM_GEGLU) {   // gate|up projection + GeGLU in one launch (serving prefill): the 320-row tile only
-    if (!a_kc || !b_kc || f32 || bias || residual || (flags & ~(LAP_GEMM_GEGLU | LAP_GEMM_GELU_EXP2)) || (N & 255) || M > 640 || alpha != 1.0f || ksplit > 1 || (tile >= 0 && tile != 15))
-      return LAP_ERR_ARG;
-    tile = 15; ksplit = 1;
-  }
-  // Few output tiles but a very long contraction (LM-head dgrad: 1504 x 2048 over K = 257152; prefill down
-  // projection): the big tile with enough K splits to cover the chip beats the small tile walking all of K.
-  if (tile < 0 && ksplit == 0 && scratch != nullptr && K >= 16384 && !(flags & LAP_GEMM_PARTIALS)) {
-    const long long t5 = (long long)((M + 255) / 256) * ((N + 255) / 256);
-    if (t5 <= 128) {
-      long long sp = 256 / t5;
-      const long long cap = scratch_bytes / ((long long)M * N * 4);
-      if (sp > 8) sp = 8;
-      if (sp > (K + 63) / 64 / 16) sp = (K + 63) / 64 / 16;
-      if (sp > cap) sp = cap;
-      if (sp >= 2) { tile = 5; ksplit = (int)sp; }
-    }
-  }
-  // Plain products over whole 256-tiles (no bias / residual / GELU / accumulate / split): the hand-scheduled assembly main
-  // loop (csrc/gemm_asm_kernels.s: forward bf16, data-gradient bf16, weight-gradient f32 layouts; same accumulation order,
-  // bitwise equal) whenever its persistent rounds are well filled, or the contraction is too short for the tail split
-  // below to pay.  tile 14 forces it (tests); LAP_GEMM_NO_ASM=1 disables it (A/B runs).
-  {
-    static const bool no_asm = getenv("LAP_GEMM_NO_ASM") != nullptr;
-    static const bool no_asm_nn = getenv("LAP_GEMM_NO_ASM_NN") != nullptr;
-    const bool plain = !bias && !residual && !(flags & (LAP_GEMM_GELU | LAP_GEMM_ACCUM | LAP_GEMM_PARTIALS)) && alpha == 1.0f && ksplit <= 1 &&
-                       lap_gemm_asm_ok(a_kc, b_kc, f32, M, N, K, lda, ldb, ldc);
-    // forward + f32 bias per column (Flax Dense of SigLIP: qkv, fc1), N any multiple of 16
-    const bool biased = a_kc && b_kc && !f32 && bias && (flags & LAP_GEMM_BIAS_F32) && !residual &&
-                        !(flags & (LAP_GEMM_GELU | LAP_GEMM_ACCUM | LAP_GEMM_PARTIALS)) && alpha == 1.0f && ksplit <= 1 &&
-                        lap_gemm_asm_bias_ok(M, N, K, lda, ldb, ldc) && !((uintptr_t)bias & 15);
-    // forward + bf16 residual with C's leading dimension (+ optional f32 bias): out / down projections of a block
-    const bool resid = a_kc && b_kc && !f32 && residual && ldr == ldc && !((uintptr_t)residual & 15) &&
-                       (!bias || ((flags & LAP_GEMM_BIAS_F32) && !((uintptr_t)bias & 15))) &&
-                       !(flags & (LAP_GEMM_GELU | LAP_GEMM_ACCUM | LAP_GEMM_PARTIALS)) && alpha == 1.0f && ksplit <= 1 &&
-                       lap_gemm_asm_res_ok(bias != nullptr, M, N, K, lda, ldb, ldc);
-    if (tile == 14 && resid) return lap_gemm_asm_res(A, B, C, (const float*)bias, residual, M, N, K, lda, ldb, ldc, stream);
-    if (tile < 0 && resid && !no_asm) {
-      static const bool no_res = getenv("LAP_GEMM_NO_ASM_RES") != nullptr;      // A/B switch
-      const long long tm = M / 256, tn = (N + 255) / 256, t5 = tm * tn, rounds = t5 / 256;
-      const double fill = (double)t5 / (256.0 * ((t5 + 255) / 256));
-      if (!no_res && t5 >= 128 && (fill >= 0.8 || (bias && K <= 2048))) return lap_gemm_asm_res(A, B, C, (const float*)bias, residual, M, N, K, lda, ldb, ldc, stream);
-      // (the M cut of the plain products below, with the residual rows following the cut)
-      static const bool no_msplit = getenv("LAP_GEMM_NO_MSPLIT") != nullptr;
-      static const bool longk = getenv("LAP_GEMM_NO_MSPLIT_LONGK") == nullptr;   // (A/B switch, see the plain products below)
-      if (!no_res && !no_msplit && !bias && ksplit == 0 && scratch != nullptr && (K <= 4096 || longk) && rounds >= 1 && fill < 0.8 && (rounds * 256) % tn == 0) {
-        const int M0 = (int)(rounds * 256 / tn) * 256;
-        if (int rc = lap_gemm_asm_res(A, B, C, nullptr, residual, M0, N, K, lda, ldb, ldc, stream)) return rc;
-        return lap_gemm_bf16_ex((const char*)A + (long long)M0 * lda * 2, B, (char*)C + (long long)M0 * ldc * 2, nullptr,
-                                (const char*)residual + (long long)M0 * ldr * 2, M - M0, N, K, lda, ldb, ldc, ldr, 1.0f, a_kc, b_kc, flags, -1, 0,
-                                scratch, scratch_bytes, stream);
-      }
-    }
-    if (tile == 14 && biased) return lap_gemm_asm_bias(A, B, C, (const float*)bias, M, N, K, lda, ldb, ldc, stream);
-    if (tile < 0 && biased && !no_asm) {
-      const long long t5 = (long long)(M / 256) * ((N + 255) / 256);
-      const double fill = (double)t5 / (256.0 * ((t5 + 255) / 256));
-      if (t5 >= 128 && fill >= 0.8) return lap_gemm_asm_bias(A, B, C, (const float*)bias, M, N, K, lda, ldb, ldc, stream);
-    }
-    if (tile == 14) return plain ? lap_gemm_asm(A, B, C, M, N, K, lda, ldb, ldc, a_kc, b_kc, f32, stream) : LAP_ERR_ARG;
-    // M = 17,920 rows x N = 2,048 columns are 70 x 8 = 560 tiles: 2.19 rounds of the chip.  The persistent kernel would run a
-    // third round for 48 tiles; the HIP tile splits those 48 along K.  Same cut here, made along M: rows [0, 64 x 256) are
-    // exactly two rounds for the assembly kernel, the last 1,536 rows a product of their own on the automatic route (its
-    // K split covers the chip).  tools/bench_msplit.py (isolated, us): qkv data gradient K = 2560 195 -> 152, out data gradient
-    // K = 2048 161 -> 124, plain forward K = 2048 129 -> 121.  LAP_GEMM_NO_MSPLIT=1: off (A/B).
-    // Long contractions with a K-contiguous A (gate|up data gradient K = 32768, down forward + residual K = 16384; the engine pads
-    // A's rows off the 16 KiB stride): isolated the cut is a wash (1726 vs 1762 us, 922 vs 949 us: the last 1536 rows cost 181 /
-    // 100 us on the HIP tile's K split either way), in the train step it is worth 2.8 ms (302.0 -> 299.2 ms, interleaved on
-    // one box) — the assembly kernel's two rounds leave the optimizer stream more of the chip than the HIP tile's.
-    // LAP_GEMM_NO_MSPLIT_LONGK=1: off (A/B).
-    static const bool msplit_longk = getenv("LAP_GEMM_NO_MSPLIT_LONGK") == nullptr;
-    if (tile < 0 && plain && !no_asm && ksplit == 0 && scratch != nullptr && (K <= 4096 || (msplit_longk && a_kc))) {
-      static const bool off = getenv("LAP_GEMM_NO_MSPLIT") != nullptr;
-      const long long tm = M / 256, tn = N / 256, t5 = tm * tn, rounds = t5 / 256;
-      const double fill = (double)t5 / (256.0 * ((t5 + 255) / 256));
-      if (!off && rounds >= 1 && fill < 0.8 && (rounds * 256) % tn == 0) {
-        const int M0 = (int)(rounds * 256 / tn) * 256;
-        const int esz = f32 ? 4 : 2;
-        const void* A1 = a_kc ? (const void*)((const char*)A + (long long)M0 * lda * 2) : (const void*)((const char*)A + (long long)M0 * 2);
-        void* C1 = (void*)((char*)C + (long long)M0 * ldc * esz);
-        if (int rc = lap_gemm_asm(A, B, C, M0, N, K, lda, ldb, ldc, a_kc, b_kc, f32, stream)) return rc;
-        return lap_gemm_bf16_ex(A1, B, C1, nullptr, nullptr, M - M0, N, K, lda, ldb, ldc, 0, 1.0f, a_kc, b_kc, flags, -1, 0, scratch, scratch_bytes, stream);
-      }
-    }
-    // Ragged M with very many rows (the embedding table's weight gradient: 257,152 = 1004.5 x 256 rows): the whole m-tiles on the
-    // assembly kernel, the last M % 256 rows as a product of their own (weight-gradient layout only: A's tail is a column offset)
-    if (tile < 0 && !no_asm && !a_kc && !b_kc && f32 && (M & 255) && M >= 65536 && !bias && !residual &&
-        !(flags & (LAP_GEMM_GELU | LAP_GEMM_ACCUM | LAP_GEMM_PARTIALS)) && alpha == 1.0f && ksplit == 0) {
-      const int M0 = M & ~255;
-      if (lap_gemm_asm_ok(0, 0, 1, M0, N, K, lda, ldb, ldc)) {
-        if (int rc = lap_gemm_asm(A, B, C, M0, N, K, lda, ldb, ldc, 0, 0, 1, stream)) return rc;
-        return lap_gemm_bf16_ex((const char*)A + (long long)M0 * 2, B, (char*)C + (long long)M0 * ldc * 4, nullptr, nullptr, M - M0, N, K, lda, ldb,
-                                ldc, 0, 1.0f, 0, 0, flags, -1, 0, scratch, scratch_bytes, stream);
-      }
-    }
-    if (tile < 0 && plain && !no_asm) {
-      const long long t5 = (long long)(M / 256) * (N / 256);
-      const double fill = (double)t5 / (256.0 * ((t5 + 255) / 256));
-      // measured against the HIP tiles (tools/bench_asm_gemm.py bench): forward +10-17 % whenever the rounds are filled or the
-      // contraction is short; weight gradient +10 % (tall outputs run as the wide product of the swapped operands with
-      // transposed stores, see lap_gemm_asm); data gradient: 0 .. +14 % on short contractions with filled rounds (the
-      // ping-pong tile's rate on a weight with 32 KiB rows varies from box to box), long ones keep the tail split
-      const bool win = (a_kc && b_kc) ? (fill >= 0.8 || K <= 4096) : (!a_kc && !b_kc) ? fill >= 0.8 : (fill >= 0.8 && K <= 4096 && !no_asm_nn);
-      if (t5 >= 128 && win) return lap_gemm_asm(A, B, C, M, N, K, lda, ldb, ldc, a_kc, b_kc, f32, stream);
-    }
-  }
-  // N = 256 j + 128 with many rows (SigLIP's width 1152 at B x 512 rows: out / fc2 forward, qkv / fc1 data gradients): the 256-wide
-  // tiling needs j + 1 column tiles of which the last is half empty, e.g. 64 x 4.5 -> 320 tile slots = two rounds of the chip for
-  // 1.13 rounds of work.  Cut the product along N instead: columns [0, 256 j) are whole tiles (64 x 4 = exactly one round at
-  // B = 32, and a plain / bias-only product of that shape is eligible for the assembly kernels), the last 128 columns a second,
-  // small product on the 128 x 128 tile (with its automatic K split: those 128 columns see another f32 summation order,
-  // everything else keeps its bits).
-  // tools/bench_nsplit.py (isolated, us): fc2 forward K = 4304 240 -> 200, qkv data gradient K = 3456 141 -> 122, fc1 data gradient
-  // K = 4304 172 -> 159; K = 1152 (out projection) loses 4 us to the second launch, so short contractions stay whole.  The tail
-  // product re-reads all of A for 128 columns, which is what keeps the gain below the 1.5 / 2 rounds it removes.
-  // LAP_GEMM_NO_NSPLIT=1: off (A/B).
-  if (tile < 0 && ksplit == 0 && (N & 255) == 128 && N >= 640 && N <= 2048 + 128 && M >= 4096 && K >= 2048 && !(flags & LAP_GEMM_PARTIALS)) {
-    static const bool off = getenv("LAP_GEMM_NO_NSPLIT") != nullptr;
-    const long long tm = (M + 255) / 256, t_all = tm * (N / 256 + 1), t_whole = tm * (N / 256);
-    const double fill_all = (double)t_all / (256.0 * ((t_all + 255) / 256)), fill_whole = (double)t_whole / (256.0 * ((t_whole + 255) / 256));
-    if (!off && fill_all < 0.8 && fill_whole >= 0.9) {
-      const int N0 = N - 128;
-      const int esz = f32 ? 4 : 2;
-      const char* Bp = (const char*)B;
-      const void* B1 = b_kc ? (const void*)(Bp + (long long)N0 * ldb * 2) : (const void*)(Bp + (long long)N0 * 2);
-      const void* bias1 = bias ? (const void*)((const char*)bias + (long long)N0 * ((flags & LAP_GEMM_BIAS_F32) ? 4 : 2)) : nullptr;
-      const void* res1 = residual ? (const void*)((const char*)residual + (long long)N0 * 2) : nullptr;
-      void* C1 = (void*)((char*)C + (long long)N0 * esz);
-      if (int rc = lap_gemm_bf16_ex(A, B, C, bias, residual, M, N0, K, lda, ldb, ldc, ldr, alpha, a_kc, b_kc, flags, -1, 0, scratch, scratch_bytes, stream)) return rc;
-      return lap_gemm_bf16_ex(A, B1, C1, bias1, res1, M, 128, K, lda, ldb, ldc, ldr, alpha, a_kc, b_kc, flags, -1, 0, scratch, scratch_bytes, stream);
-    }
-  }
-  // Serving prefill (batch-1 action chunk: 512 SigLIP rows, 560 Gemma rows; forward layout, bf16 out).  Every block of such
-  // a GEMM is bound by what it pulls through its CU's vector-memory path (~45 GB/s), so the tile is the one with the fewest
-  // operand bytes per block that still covers the chip WITHOUT a split-K reduce pass behind it (tools/bench_prefill_gemm.py,
-  // hipGraph-timed, automatic choice -> here): SigLIP qkv 22.8 -> 12.5 us, out 14.7 -> 10.1, fc1 24.5 -> 16.8, head 19.3 ->
-  // 10.1; Gemma qkv 22.2 -> 17.1, out 18.2 -> 17.4, gate|up 90.8 -> 74.2 (a 320-row tile: 560 rows are 2 x 280, not 3 x 256).
-  // Long contractions (SigLIP fc2, Gemma down: K >= 4096) keep their K split.  LAP_GEMM_NO_SERVING_TILES=1: off (A/B).
-  if (tile < 0 && ksplit == 0 && a_kc && b_kc && M > 256 && M <= 768 && !(flags & LAP_GEMM_PARTIALS) && (f32 || !(flags & LAP_GEMM_ACCUM))) {
-    static const bool off = getenv("LAP_GEMM_NO_SERVING_TILES") != nullptr;
-    if (!off) {
-      if (K <= 1536 && N >= 1024) { tile = N >= 3072 ? 16 : 17; ksplit = 1; }     // (also the f32 hi / lo stem products)
-      else if (f32) {}
-      else if (K <= 2560 && N >= 8192 && M > 512 && M <= 640) { tile = 15; ksplit = 1; }
-      else if (K <= 2560 && N >= 2048 && N < 8192) { tile = 16; ksplit = 1; }
-    }
-  }
-  if (tile < 0) tile = pick_tile(M, N, K);
-  // Tail split (256x256 kernel, automatic split only): the full rounds of 256 tiles run unsplit; only the tiles of
-  // the last, poorly filled round are split along K so that they fill the chip for 1/sp of a round.
-  int tail_tiles = 0, tail_sp = 0;
-  if (ksplit == 0 && scratch != nullptr && tile == 5 && !(flags & LAP_GEMM_PARTIALS)) {
-    const long long t5 = (long long)((M + 255) / 256) * ((N + 255) / 256);
-    const int tail = (int)(t5 % 256), nkt = (K + 63) / 64;
-    if (t5 > 256 && tail > 0 && tail < 200) {
-      // Cost model (microseconds, calibrated on in-situ traces): a tile costs ~6 + 1.9 per 64-deep k-tile; splitting the
-      // tail sp ways shortens that to nkt / sp k-tiles but adds a reduce pass over sp f32 slabs + the output
-      // (~25 us of launch + latency + bytes at ~2.5 TB/s).  Short contractions (K <= 2048) are cheaper unsplit
-      // (measured: tools/bench_tail.py).
-      int smax = 256 / tail;
-      if (smax > 8) smax = 8;
-      const long long cap = scratch_bytes / ((long long)tail * 65536 * 4);
-      if (smax > cap) smax = (int)cap;
-      const double whole = 6.0 + 1.9 * nkt;
-      double best = whole;
-      int sp = 1;
-      for (int c = 2; c <= smax; ++c) {
-        const double cost = 6.0 + 1.9 * ((nkt + c - 1) / c) + 25.0 + (double)tail * 65536.0 * (4.0 * c + 2.0) / 2.5e6;
-        if (cost < best - 4.0) { best = cost; sp = c; }   // (a split has to pay for its extra launch clearly)
-      }
-      // third option, for short contractions: the tail as 4 x tail quadrants on the 128x128 kernel (one round of it when
-      // tail <= 128), modelled as 0.64 of a 256x256 tile time + its launch.  Measured gain is small: 4-9 us per GEMM
-      // isolated (tools/bench_tail.py), 345.0 -> 344.1 ms per train step in an interleaved A/B (within noise)
-      if (tail <= 128 && 0.64 * whole + 6.0 < best - 4.0) { tail_tiles = tail; tail_sp = 1; }
-      else if (sp >= 2) { tail_tiles = tail; tail_sp = sp; }
-    }
-  }
-  if (ksplit == 0 && scratch != nullptr && !tail_tiles) ksplit = pick_ksplit(tile, M, N, K, scratch_bytes, a_kc && b_kc);
-  // K % 8 == 0: the software-pipelined 8-wave kernel (tile 10) for the forward layout, the ping-pong kernel (tile 12) as
-  // soon as an operand is M-contiguous (data / weight gradients: +5-11 % measured, tools/bench_kernels.py; on the forward
-  // layout its 64-byte k-half rows cost more in LDS-DMA requests than the ping-pong gains); else the 16-wave kernel
-  static const bool no_pq = getenv("LAP_GEMM_NO_PINGPONG") != nullptr;   // A/B switch for benchmarks
-  static const bool no_ktail = getenv("LAP_GEMM_NO_KTAIL") != nullptr;      // A/B switch: ragged K back on the lockstep tile
-  const int big = (!(K & 7) && (!(K & 63) || !no_ktail)) ? ((a_kc && b_kc) || no_pq ? 10 : 12) : 5;
-  if (tile == 5) tile = big;
-  const bool two_phase = ksplit > 1 && scratch != nullptr;
-  if (two_phase && scratch_bytes < (long long)ksplit * M * N * 4) return LAP_ERR_ARG;
-  if (ksplit > 1 && !two_phase && (!f32 || !(flags & LAP_GEMM_ACCUM) || bias || residual)) return LAP_ERR_ARG;
-  GemmParams p = {};
-  p.A = (const bf16*)A; p.B = (const bf16*)B; p.C = C; p.bias = bias; p.R = (const bf16*)residual;
-  p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.ldr = ldr; p.alpha = alpha;
-  p.bias_kind = bias ? ((flags & LAP_GEMM_BIAS_F32) ? 2 : 1) : 0;
-  p.gelu = (flags & LAP_GEMM_GELU) ? ((flags & LAP_GEMM_GELU_BF16) ? 2 : 1) : 0;
-  p.accum = (flags & LAP_GEMM_ACCUM) ? 1 : 0;
-  p.geglu = (flags & LAP_GEMM_GEGLU) ? ((flags & LAP_GEMM_GELU_EXP2) ? 2 : 1) : 0;
-  p.ksplit = ksplit > 1 ? ksplit : 1;
-  p.dbg = g_gemm_dbg;
-  p.part = two_phase ? (float*)scratch : nullptr;
-  hipStream_t s = (hipStream_t)stream;
-  if (flags & LAP_GEMM_PARTIALS) {
-    if (!scratch || ksplit < 1 || scratch_bytes < (long long)(ksplit > 1 ? ksplit : 1) * M * N * 4) return LAP_ERR_ARG;
-    p.part = (float*)scratch;   // also valid for ksplit == 1: one slab
-  }
-  if (tail_tiles) {
-    const int t5 = ((M + 255) / 256) * ((N + 255) / 256);
-    int rc;
-    // (a) the full rounds, straight to C
-    p.ksplit = 1; p.part = nullptr; p.tile_base = 0; p.tile_count = t5 - tail_tiles;
-    if (f32) {
-      if (a_kc && b_kc) rc = dispatch_tile<true, true, true>(p, big, s);
-      else if (a_kc && !b_kc) rc = dispatch_tile<true, false, true>(p, big, s);
-      else if (!a_kc && !b_kc) rc = dispatch_tile<false, false, true>(p, big, s);
-      else rc = dispatch_tile<false, true, true>(p, big, s);
-    } else {
-      if (a_kc && b_kc) rc = dispatch_tile<true, true, false>(p, big, s);
-      else if (a_kc && !b_kc) rc = dispatch_tile<true, false, false>(p, big, s);
-      else if (!a_kc && !b_kc) rc = dispatch_tile<false, false, false>(p, big, s);
-      else rc = dispatch_tile<false, true, false>(p, big, s);
-    }
-    if (rc) return rc;
-    if (tail_sp == 1) {
-      // (b') the tail tiles as quadrants on the 128x128 kernel, straight to C with the caller's epilogue
-      p.sub256 = 1; p.tile_base = t5 - tail_tiles; p.tile_count = tail_tiles;
-      if (f32) {
-        if (a_kc && b_kc) return dispatch_tile<true, true, true>(p, 6, s);
-        if (a_kc && !b_kc) return dispatch_tile<true, false, true>(p, 6, s);
-        if (!a_kc && !b_kc) return dispatch_tile<false, false, true>(p, 6, s);
-        return dispatch_tile<false, true, true>(p, 6, s);
-      }
-      if (a_kc && b_kc) return dispatch_tile<true, true, false>(p, 6, s);
-      if (a_kc && !b_kc) return dispatch_tile<true, false, false>(p, 6, s);
-      if (!a_kc && !b_kc) return dispatch_tile<false, false, false>(p, 6, s);
-      return dispatch_tile<false, true, false>(p, 6, s);
-    }
-    // (b) the tail tiles, split along K into compact f32 slabs, then reduce + epilogue
-    p.ksplit = tail_sp; p.part = (float*)scratch; p.part_compact = 1; p.tile_base = t5 - tail_tiles; p.tile_count = tail_tiles;
-    if (a_kc && b_kc) rc = dispatch_tile<true, true, true>(p, big, s);
-    else if (a_kc && !b_kc) rc = dispatch_tile<true, false, true>(p, big, s);
-    else if (!a_kc && !b_kc) rc = dispatch_tile<false, false, true>(p, big, s);
-    else rc = dispatch_tile<false, true, true>(p, big, s);
-    if (rc) return rc;
-    p.tiles_m = (M + 255) / 256; p.tiles_n = (N + 255) / 256;
-    if (f32) hipLaunchKernelGGL(splitk_tail_reduce_kernel<true>, dim3(tail_tiles * 64), dim3(256), 0, s, p, tail_tiles);
-    else hipLaunchKernelGGL(splitk_tail_reduce_kernel<false>, dim3(tail_tiles * 64), dim3(256), 0, s, p, tail_tiles);
-    LAP_CHECK_LAUNCH();
-    return LAP_OK;
-  }
-  if (two_phase || (flags & LAP_GEMM_PARTIALS)) {
-    int rc;
-    if (a_kc && b_kc) rc = dispatch_tile<true, true, true>(p, tile, s);
-    else if (a_kc && !b_kc) rc = dispatch_tile<true, false, true>(p, tile, s);
-    else if (!a_kc && !b_kc) rc = dispatch_tile<false, false, true>(p, tile, s);
-    else rc = dispatch_tile<false, true, true>(p, tile, s);
-    if (rc) return rc;
-    if (flags & LAP_GEMM_PARTIALS) return LAP_OK;
-    const long long n4 = (long long)M * N / 4;
-    if (f32) hipLaunchKernelGGL(splitk_reduce_kernel<true>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(splitk_reduce_kernel<false>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, p);
-    LAP_CHECK_LAUNCH();
-    return LAP_OK;
-  }
+// run-time (layout, output type) -> the tile launchers' instantiation
+int dispatch(const GemmParams& p, int tile, bool a_kc, bool b_kc, bool f32, hipStream_t s) {
   if (f32) {
     if (a_kc && b_kc) return dispatch_tile<true, true, true>(p, tile, s);
     if (a_kc && !b_kc) return dispatch_tile<true, false, true>(p, tile, s);
@@ -1848,6 +1471,158 @@ extern "C" int lap_gemm_bf16_ex(const void* A, const void* B, void* C, const voi
   if (a_kc && !b_kc) return dispatch_tile<true, false, false>(p, tile, s);
   if (!a_kc && !b_kc) return dispatch_tile<false, false, false>(p, tile, s);
   return dispatch_tile<false, true, false>(p, tile, s);
+}
+
+int g_gemm_dbg = 0;
+
+// The A/B switches of the routing (LAP_GEMM_NO_ASM=1 ... -> LAP_ROUTE_NO_ASM ...), read once per process.
+unsigned route_switches_from_env() {
+  static const unsigned sw = [] {
+    static const struct { const char* name; unsigned bit; } k[] = {
+        {"LAP_GEMM_NO_ASM", LAP_ROUTE_NO_ASM}, {"LAP_GEMM_NO_ASM_NN", LAP_ROUTE_NO_ASM_NN}, {"LAP_GEMM_NO_ASM_RES", LAP_ROUTE_NO_ASM_RES},
+        {"LAP_GEMM_NO_MSPLIT", LAP_ROUTE_NO_MSPLIT}, {"LAP_GEMM_NO_MSPLIT_LONGK", LAP_ROUTE_NO_MSPLIT_LONGK}, {"LAP_GEMM_NO_NSPLIT", LAP_ROUTE_NO_NSPLIT},
+        {"LAP_GEMM_NO_SERVING_TILES", LAP_ROUTE_NO_SERVING_TILES}, {"LAP_GEMM_NO_PINGPONG", LAP_ROUTE_NO_PINGPONG}, {"LAP_GEMM_NO_KTAIL", LAP_ROUTE_NO_KTAIL}};
+    unsigned m = 0;
+    for (const auto& e : k)
+      if (getenv(e.name) != nullptr) m |= e.bit;
+    return m;
+  }();
+  return sw;
+}
+
+// the caller's arguments as the planner takes them
+struct GemmCall {
+  const void* A; const void* B; void* C; const void* bias; const void* residual;
+  int M, N, K, lda, ldb, ldc, ldr;
+  float alpha;
+  int a_kc, b_kc, flags, tile, ksplit;
+  void* scratch;
+  long long scratch_bytes;
+};
+
+int plan_gemm(const GemmCall& g, unsigned switches, lap_route::Plan& plan) {
+  lap_route::Call c = {};
+  c.A = (uintptr_t)g.A; c.B = (uintptr_t)g.B; c.C = (uintptr_t)g.C; c.bias = (uintptr_t)g.bias; c.res = (uintptr_t)g.residual;
+  c.M = g.M; c.N = g.N; c.K = g.K; c.lda = g.lda; c.ldb = g.ldb; c.ldc = g.ldc; c.ldr = g.ldr; c.alpha = g.alpha;
+  c.a_kc = g.a_kc; c.b_kc = g.b_kc; c.flags = g.flags; c.tile = g.tile; c.ksplit = g.ksplit;
+  c.scratch = g.scratch != nullptr; c.scratch_bytes = g.scratch_bytes; c.sw = switches;
+  return lap_route::plan_call(c, plan);
+}
+
+// Launches the legs of a plan in order on the caller's stream; the first failing launch ends the walk with its code.
+int run_plan(const lap_route::Plan& plan, const GemmCall& g, float* sumsq, void* stream) {
+  const bool f32 = g.flags & LAP_GEMM_OUT_F32;
+  hipStream_t s = (hipStream_t)stream;
+  for (int i = 0; i < plan.n; ++i) {
+    const lap_gemm_leg& l = plan.legs[i];
+    const void* A = (const char*)g.A + l.off_a * 2;
+    const void* B = (const char*)g.B + l.off_b * 2;
+    void* C = (char*)g.C + l.off_c * (f32 ? 4 : 2);
+    const void* bias = g.bias ? (const char*)g.bias + l.off_bias * ((g.flags & LAP_GEMM_BIAS_F32) ? 4 : 2) : nullptr;
+    const void* residual = g.residual ? (const char*)g.residual + l.off_res * 2 : nullptr;
+    int rc;
+    switch (l.engine) {
+      case LAP_LEG_ASM: rc = lap_gemm_asm(A, B, C, l.M, l.N, g.K, g.lda, g.ldb, g.ldc, g.a_kc, g.b_kc, f32, stream); break;
+      case LAP_LEG_ASM_BIAS: rc = lap_gemm_asm_bias(A, B, C, (const float*)bias, l.M, l.N, g.K, g.lda, g.ldb, g.ldc, stream); break;
+      case LAP_LEG_ASM_RES: rc = lap_gemm_asm_res(A, B, C, (const float*)bias, residual, l.M, l.N, g.K, g.lda, g.ldb, g.ldc, stream); break;
+      case LAP_LEG_ASM_WGRAD_SUMSQ:
+        rc = f32 ? lap_gemm_asm_wgrad(A, B, C, l.M, l.N, g.K, g.lda, g.ldb, g.ldc, sumsq, stream)
+                 : lap_gemm_asm_wgrad_b16(A, B, C, l.M, l.N, g.K, g.lda, g.ldb, g.ldc, sumsq, stream);
+        break;
+      default: {
+        GemmParams p = {};
+        p.A = (const bf16*)A; p.B = (const bf16*)B; p.C = C; p.bias = bias; p.R = (const bf16*)residual;
+        p.M = l.M; p.N = l.N; p.K = g.K; p.lda = g.lda; p.ldb = g.ldb; p.ldc = g.ldc; p.ldr = g.ldr; p.alpha = g.alpha;
+        p.bias_kind = bias ? ((g.flags & LAP_GEMM_BIAS_F32) ? 2 : 1) : 0;
+        p.gelu = (g.flags & LAP_GEMM_GELU) ? ((g.flags & LAP_GEMM_GELU_BF16) ? 2 : 1) : 0;
+        p.accum = (g.flags & LAP_GEMM_ACCUM) ? 1 : 0;
+        p.geglu = (g.flags & LAP_GEMM_GEGLU) ? ((g.flags & LAP_GEMM_GELU_EXP2) ? 2 : 1) : 0;
+        p.ksplit = l.ksplit;
+        p.dbg = g_gemm_dbg;
+        p.part = l.part ? (float*)g.scratch : nullptr;
+        p.tile_base = l.tile_base; p.tile_count = l.tile_count; p.sub256 = l.sub256; p.part_compact = l.part_compact;
+        rc = dispatch(p, l.engine, g.a_kc, g.b_kc, l.f32_tile, s);
+        if (rc || l.reduce == LAP_LEG_REDUCE_NONE) break;
+        if (l.reduce == LAP_LEG_REDUCE_TAIL) {
+          p.tiles_m = (l.M + 255) / 256; p.tiles_n = (l.N + 255) / 256;
+          if (f32) hipLaunchKernelGGL(splitk_tail_reduce_kernel<true>, dim3(l.tile_count * 64), dim3(256), 0, s, p, l.tile_count);
+          else hipLaunchKernelGGL(splitk_tail_reduce_kernel<false>, dim3(l.tile_count * 64), dim3(256), 0, s, p, l.tile_count);
+        } else {
+          const long long n4 = (long long)l.M * l.N / 4;
+          if (f32) hipLaunchKernelGGL(splitk_reduce_kernel<true>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, p);
+          else hipLaunchKernelGGL(splitk_reduce_kernel<false>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, p);
+        }
+        LAP_CHECK_LAUNCH();
+      }
+    }
+    if (rc) return rc;
+  }
+  return LAP_OK;
+}
+
+int gemm_planned(const GemmCall& g, unsigned switches, float* sumsq, int* folded, void* stream) {
+  lap_route::Plan plan;
+  if (int rc = plan_gemm(g, switches, plan)) return rc;
+  if (folded) *folded = plan.legs[0].engine == LAP_LEG_ASM_WGRAD_SUMSQ;
+  return run_plan(plan, g, sumsq, stream);
+}
+
+// Weight gradient dW [M][N] (f32 or bf16) = A^T B over K rows (A [K][M], B [K][N]) with its sum of squares folded in where the
+// assembly kernel takes the product (*folded = 1: *sumsq has received sum(dW^2)); every other shape runs as lap_gemm_bf16_ex would
+// run it and leaves the norm to the caller (*folded = 0).  The routing rule is the plain-product rule of lap_gemm_bf16_ex.
+int gemm_wgrad(bool f32, const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc, float* sumsq, int* folded,
+               void* scratch, long long scratch_bytes, void* stream) {
+  if (!folded) return LAP_ERR_ARG;
+  *folded = 0;
+  const GemmCall g = {A, B, C, nullptr, nullptr, M, N, K, lda, ldb, ldc, 0, 1.0f, 0, 0, f32 ? LAP_GEMM_OUT_F32 : 0, -1, 0, scratch, scratch_bytes};
+  return gemm_planned(g, route_switches_from_env() | (sumsq ? LAP_ROUTE_WGRAD_SUMSQ : 0), sumsq, folded, stream);
+}
+
+}  // namespace
+
+extern "C" int lap_gemm_set_debug(int bits) {   // ablation knob; has an effect in LAP_GEMM_EXPERIMENTAL builds only
+#ifdef LAP_GEMM_EXPERIMENTAL
+  g_gemm_dbg = bits;
+  return LAP_OK;
+#else
+  return bits ? LAP_ERR_ARG : LAP_OK;
+#endif
+}
+
+extern "C" int lap_gemm_wgrad_f32(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc, float* sumsq,
+                                  int* folded, void* scratch, long long scratch_bytes, void* stream) {
+  return gemm_wgrad(true, A, B, C, M, N, K, lda, ldb, ldc, sumsq, folded, scratch, scratch_bytes, stream);
+}
+
+// The same for a weight gradient stored as bf16 (dW [M][N] bf16; ParamStore.grad_dtype): the bf16 assembly kernels fold the squares of
+// their f32 accumulators.
+extern "C" int lap_gemm_wgrad_bf16(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc, float* sumsq,
+                                   int* folded, void* scratch, long long scratch_bytes, void* stream) {
+  return gemm_wgrad(false, A, B, C, M, N, K, lda, ldb, ldc, sumsq, folded, scratch, scratch_bytes, stream);
+}
+
+// Plan (csrc/gemm_route.hpp: every routing rule lives there), then launch the legs.
+extern "C" int lap_gemm_bf16_ex(const void* A, const void* B, void* C, const void* bias, const void* residual,
+                                int M, int N, int K, int lda, int ldb, int ldc, int ldr, float alpha,
+                                int a_kc, int b_kc, int flags, int tile, int ksplit, void* scratch,
+                                long long scratch_bytes, void* stream) {
+  const GemmCall g = {A, B, C, bias, residual, M, N, K, lda, ldb, ldc, ldr, alpha, a_kc, b_kc, flags, tile, ksplit, scratch, scratch_bytes};
+  return gemm_planned(g, route_switches_from_env(), nullptr, nullptr, stream);
+}
+
+extern "C" int lap_gemm_plan(const void* A, const void* B, const void* C, const void* bias, const void* residual,
+                             int M, int N, int K, int lda, int ldb, int ldc, int ldr, float alpha,
+                             int a_kc, int b_kc, int flags, int tile, int ksplit, const void* scratch, long long scratch_bytes,
+                             unsigned switches, lap_gemm_leg* legs, int max_legs, int* n_legs) {
+  if (!legs || !n_legs || max_legs < 0) return LAP_ERR_ARG;
+  *n_legs = 0;
+  const GemmCall g = {A, B, (void*)C, bias, residual, M, N, K, lda, ldb, ldc, ldr, alpha, a_kc, b_kc, flags, tile, ksplit, (void*)scratch, scratch_bytes};
+  lap_route::Plan plan;
+  if (int rc = plan_gemm(g, switches, plan)) return rc;
+  if (plan.n > max_legs) return LAP_ERR_ARG;
+  for (int i = 0; i < plan.n; ++i) legs[i] = plan.legs[i];
+  *n_legs = plan.n;
+  return LAP_OK;
 }
 
 extern "C" int lap_gemm_bf16(const void* A, const void* B, void* C, const void* bias, const void* residual,

@@ -93,6 +93,18 @@ class AttnBwdArgs(C.Structure):
     ]
 
 
+class GemmLeg(C.Structure):
+    """lap_gemm_leg (include/lap_hip.h): one launch of a planned GEMM."""
+    _fields_ = [(n, _ll) for n in ("off_a", "off_b", "off_c", "off_bias", "off_res")] + [
+        (n, _i) for n in ("engine", "M", "N", "ksplit", "tile_base", "tile_count", "sub256", "part_compact", "f32_tile", "part", "reduce")]
+
+
+GEMM_MAX_LEGS = 6                    # LAP_GEMM_MAX_LEGS
+LEG_ASM, LEG_ASM_BIAS, LEG_ASM_RES, LEG_ASM_WGRAD_SUMSQ = 32, 33, 34, 35
+ROUTE_WGRAD_SUMSQ = 65536
+ROUTE_SWITCHES = {"LAP_GEMM_NO_ASM": 1, "LAP_GEMM_NO_ASM_NN": 2, "LAP_GEMM_NO_ASM_RES": 4, "LAP_GEMM_NO_MSPLIT": 8, "LAP_GEMM_NO_MSPLIT_LONGK": 16,
+                  "LAP_GEMM_NO_NSPLIT": 32, "LAP_GEMM_NO_SERVING_TILES": 64, "LAP_GEMM_NO_PINGPONG": 128, "LAP_GEMM_NO_KTAIL": 256}
+
 # name -> argtypes; every entry point of include/lap_hip.h must be listed here (tests check it).
 SIGNATURES: dict[str, list] = {
     "lap_abi_version": [],
@@ -102,6 +114,7 @@ SIGNATURES: dict[str, list] = {
     "lap_gemm_asm": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "lap_gemm_asm_ok": [_i, _i, _i, _i, _i, _i, _i, _i, _i],
     "lap_gemm_asm_launch_counts": [C.POINTER(C.c_longlong), _i],
+    "lap_gemm_plan": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _i, _i, _vp, _ll, C.c_uint, _vp, _i, C.POINTER(_i)],
     "lap_gemm_asm_bias": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "lap_gemm_asm_bias_ok": [_i, _i, _i, _i, _i, _i],
     "lap_gemm_asm_res": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
@@ -334,6 +347,17 @@ def linear_wgrad(dy, x, out, *, accum=False, ksplit=0, tile=-1):
     Kin = x.shape[1]
     return gemm(dy, x, out, M=Nout, N=Kin, K=Mrows, lda=dy.stride(0), ldb=x.stride(0), ldc=out.stride(0), a_kc=False,
                 b_kc=False, accum=accum, ksplit=ksplit, tile=tile)
+
+
+def gemm_plan(*, M, N, K, lda, ldb, ldc, ldr=0, alpha=1.0, a_kc=True, b_kc=True, flags=0, tile=-1, ksplit=0, a=256, b=256, c=256, bias=None,
+              residual=None, scratch=None, scratch_bytes=0, switches=0):
+    """What lap_gemm_bf16_ex would launch for these arguments under the LAP_ROUTE_* `switches` (include/lap_hip.h: lap_gemm_plan): a list
+    of GemmLeg.  No device is touched; pointers are plain integers (None: null) that only their alignment matters of.  Rejected
+    arguments raise LapHipError with the code of the real call."""
+    legs, n = (GemmLeg * GEMM_MAX_LEGS)(), _i(0)
+    _chk(_fn["lap_gemm_plan"](a, b, c, bias, residual, M, N, K, lda, ldb, ldc, ldr, float(alpha), int(a_kc), int(b_kc), flags, tile, ksplit,
+                              scratch, scratch_bytes, switches, legs, GEMM_MAX_LEGS, C.byref(n)), "lap_gemm_plan")
+    return list(legs[:n.value])
 
 
 ASM_KERNELS = ("nt", "nn", "tn", "nt_bias", "tn_t", "nt_res", "nt_bias_res", "nn_geglu_bwd", "nt_geglu", "nn_gelu_bwd", "nt_bias_gelu",
