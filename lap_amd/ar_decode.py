@@ -32,8 +32,48 @@ def check_decode_weights(weights):
         raise ValueError(f"decode_weights must be one of {LAP.DECODE_WEIGHTS}, got {weights!r}")
 
 
+def check_allowed_tokens(ids, vocab_size: int, eos_token: int) -> torch.Tensor:
+    """The allowed set of a constrained decode as the kernels take it: sorted unique int32 ids (on the CPU) from any integer
+    sequence or tensor; duplicates and order are normalised.  ValueError for an empty set, a non-integer dtype, an id outside
+    [0, vocab_size), or a set without the EOS token when that token is in the vocabulary (such a request could only end at its
+    budget)."""
+    if not isinstance(ids, torch.Tensor) and not hasattr(ids, "__array__"):
+        ids = list(ids)
+    t = torch.as_tensor(ids).detach().cpu()
+    if t.numel() == 0:
+        raise ValueError("allowed_tokens: the set is empty")
+    if t.dtype == torch.bool or t.is_floating_point() or t.is_complex():
+        raise ValueError(f"allowed_tokens: expected integer ids, got {t.dtype}")
+    t = t.reshape(-1).to(torch.int64)
+    lo, hi = int(t.min()), int(t.max())
+    if lo < 0 or hi >= vocab_size:
+        raise ValueError(f"allowed_tokens: ids must lie in [0, {vocab_size}), got {lo if lo < 0 else hi}")
+    t = torch.unique(t)     # (sorted)
+    if 0 <= eos_token < vocab_size and not bool((t == eos_token).any()):
+        raise ValueError(f"allowed_tokens: the EOS token {eos_token} is not in the set, so no request could stop before its budget")
+    return t.to(torch.int32)
+
+
+class AllowedSet(NamedTuple):
+    """A checked allowed set on the model's device, with what it was checked against (`allowed_set`)."""
+    ids: torch.Tensor               # sorted unique int32 ids
+    vocab_size: int
+    eos_token: int
+
+
+def allowed_set(model: LAP, allowed_tokens) -> AllowedSet:
+    """`check_allowed_tokens` for `model`, once: an AllowedSet that was checked against this model's vocabulary, EOS token and
+    device is handed back as it is, so a server normalises its set at start-up and not per request."""
+    V, eos = model.config.vocab_size, model.EOS_TOKEN
+    if isinstance(allowed_tokens, AllowedSet):
+        if (allowed_tokens.vocab_size, allowed_tokens.eos_token) == (V, eos) and allowed_tokens.ids.device.type == model.device.type:
+            return allowed_tokens
+        allowed_tokens = allowed_tokens.ids
+    return AllowedSet(check_allowed_tokens(allowed_tokens, V, eos).to(model.device), V, eos)
+
+
 def sample_tokens(model: LAP, rng, observation, *, max_decoding_steps: int = 390, temperature: float = 0.0, collect=None,
-                  decode: str = "eager", sampler: str = "host", decode_weights: str = "bf16"):
+                  decode: str = "eager", sampler: str = "host", decode_weights: str = "bf16", allowed_tokens=None):
     """`LAP.sample_tokens` (documented there): every argument is checked before any device work."""
     if decode not in ("eager", "fused"):
         raise ValueError(f"sample_tokens: decode must be 'eager' or 'fused', got {decode!r}")
@@ -46,15 +86,19 @@ def sample_tokens(model: LAP, rng, observation, *, max_decoding_steps: int = 390
         check_fused_decode(model, observation.tokenized_prompt.shape[0])
     if sampler == "device":
         hip.sampling_words(rng, temperature)        # (rejects a temperature whose inverse is not finite before any work)
+    allowed = None
+    if allowed_tokens is not None:
+        allowed = allowed_set(model, allowed_tokens).ids
     with model._serving_weights():
         if decode == "fused" and (sampler == "device" or temperature <= 0.0):   # (the host sampler's noise cannot run on the device state)
             return _sample_fused(model, observation, max_decoding_steps=max_decoding_steps, collect=collect,
-                                 sampling=(rng, temperature) if sampler == "device" else None, weights=decode_weights)
+                                 sampling=(rng, temperature) if sampler == "device" else None, weights=decode_weights,
+                                 allowed=allowed)
         if decode_weights != "bf16":
             raise ValueError("sample_tokens: decode_weights other than 'bf16' with temperature > 0 needs sampler='device' (the "
                              "host sampler keeps the eager loop)")
         return _sample_eager(model, rng, observation, max_decoding_steps=max_decoding_steps, temperature=temperature, collect=collect,
-                             device_sampler=sampler == "device")
+                             device_sampler=sampler == "device", allowed=allowed)
 
 
 class Prefill(NamedTuple):
@@ -133,7 +177,9 @@ def _lm_logits(model: LAP, rows):
     return lm_logits(model, pl, 0, model.config.vocab_size)      # the f32 table as hi + lo, as in the training loss
 
 
-def _sample_eager(model: LAP, rng, observation, *, max_decoding_steps: int, temperature: float, collect, device_sampler: bool):
+def _sample_eager(model: LAP, rng, observation, *, max_decoding_steps: int, temperature: float, collect, device_sampler: bool,
+                  allowed=None):
+    """allowed: int32 device ids; the logits outside the set are -inf before the argmax or the noise."""
     dev = model.device
     B, Pn, cache, kinfo_prefix, qinfo_d, plen, x_last = prefill(model, observation)
     logits = _lm_logits(model, x_last)                                      # decodes the first token (lap.py:716)
@@ -141,8 +187,14 @@ def _sample_eager(model: LAP, rng, observation, *, max_decoding_steps: int, temp
     eos = torch.zeros((B,), dtype=torch.bool, device=dev)
     gen = [(None, None)] * model.v.depth
     g = _gen(rng, dev) if temperature > 0.0 and not device_sampler else None
+    outside = None
+    if allowed is not None:
+        outside = torch.ones((model.config.vocab_size,), dtype=torch.bool, device=dev)
+        outside[allowed.long()] = False
     step = 0
     while step < max_decoding_steps:
+        if outside is not None:
+            logits = logits.masked_fill(outside, float("-inf"))
         if device_sampler and temperature > 0.0:      # one pass over the raw logits, no [B, V] temporaries
             token = hip.gumbel_argmax_rows(logits, temperature, rng, step)
         else:
@@ -163,13 +215,19 @@ def _sample_eager(model: LAP, rng, observation, *, max_decoding_steps: int, temp
 
 
 # ---- the fused step: single-token kernels, state on the device (csrc/decode.hip)
-def _sample_fused(model: LAP, observation, *, max_decoding_steps: int, collect=None, sampling=None, weights: str = "bf16"):
-    """sampling: None (the greedy LM head) or (seed, temperature) for the sampling LM head.  weights: `decode_weights`."""
+def _sample_fused(model: LAP, observation, *, max_decoding_steps: int, collect=None, sampling=None, weights: str = "bf16",
+                  allowed=None):
+    """sampling: None (the greedy LM head) or (seed, temperature) for the sampling LM head.  weights: `decode_weights`.
+    allowed: None or the int32 device ids of `check_allowed_tokens`."""
     pre = prefill(model, observation)
-    ctx = DecodeCtx(model, pre.B, pre.Pn, max_decoding_steps, sampling is not None, weights)
+    ctx = DecodeCtx(model, pre.B, pre.Pn, max_decoding_steps, sampling is not None, weights, allowed=allowed)
     if sampling is not None:
         ctx.set_sampling(*sampling)
-    lg = torch.empty((pre.B, model.config.vocab_size), dtype=torch.float32, device=model.device) if collect is not None else None
+    lg = None
+    if collect is not None:     # (the constrained LM head writes the allowed columns only: the rest keeps the fill)
+        lg = torch.empty((pre.B, model.config.vocab_size), dtype=torch.float32, device=model.device)
+        if allowed is not None:
+            lg.fill_(float("-inf"))
     ctx.first_token(pre, lg)
     if collect is not None:     # debug: one host read per token
         collect["logit/0"] = lg.clone()
@@ -191,8 +249,11 @@ class DecodeCtx:
     the fixed-capacity generated K/V cache of every layer ([depth, 2, B, cap, head_dim] bf16, 7.2 MB per sample at 390 steps
     for LAP-3B) and the step's activations.  The prefix K/V cache and kinfo come from the prefill (`first_token` -> `bind`)."""
 
-    def __init__(self, model: LAP, B: int, Pn: int, cap: int, sampling: bool = False, weights: str = "bf16"):
+    def __init__(self, model: LAP, B: int, Pn: int, cap: int, sampling: bool = False, weights: str = "bf16", allowed=None):
         check_decode_weights(weights)
+        if allowed is not None and (allowed.dtype != torch.int32 or not allowed.is_cuda or allowed.dim() != 1):
+            raise ValueError("DecodeCtx: allowed must be the int32 device ids of check_allowed_tokens")
+        self.allowed = allowed          # None, or the allowed set of every token (captured graphs keep the buffer's address)
         v = model.v
         self.model = model
         self.weights = weights          # what the steps stream: "bf16", "fp8" (projections + LM head) or "fp8_layers"
@@ -251,6 +312,8 @@ class DecodeCtx:
             lo, kw = None, {"wscale": scales}
         else:
             hi, lo, kw = m.W("llm/embed"), m.ps.w16lo("llm/embed"), {}
+        if self.allowed is not None:      # the LM head streams the allowed rows only
+            kw["ids"] = self.allowed
         if self.sampling is not None:
             hip.decode_lm_head_sample(self.state, self.sampling, x, m.F("llm/final_norm"), hi, lo, self.pval, self.pidx, logits, **kw)
         else:

@@ -555,6 +555,147 @@ __global__ __launch_bounds__(256) void dec_lm_head_kernel(P p) {
   }
 }
 
+// The logits of vocabulary rows f0 and f1 (f1 == f0: one row) for all B rows of `sx`, wave-uniform after the wave_sums: the
+// debug store, and either lane b's pair (SAMPLE: y0 / y1 of lane b = row b) or the running best of every row (greedy).  This
+// restates the unit body of dec_lm_head_kernel (k-to-lane map, order of the fmas, wave_sums), so that a row's logit is the
+// same bits in both; that kernel keeps its own text because its code must not move.
+template <int B, bool SAMPLE, class P>
+__device__ __forceinline__ void lm_row_pair(const P p, const bf16* sx, int lane, int f0, int f1, float (&bv)[B], int (&bi)[B],
+                                            float& y0, float& y1) {
+  constexpr bool F8 = std::is_same<P, LmP8>::value;
+  float h0[B], h1[B], l0[B], l1[B];
+#pragma unroll
+  for (int b = 0; b < B; ++b) { h0[b] = 0.f; h1[b] = 0.f; l0[b] = 0.f; l1[b] = 0.f; }
+  if constexpr (F8) {
+    const uint8_t* c0p = reinterpret_cast<const uint8_t*>(p.hi) + (long long)f0 * p.D;
+    const uint8_t* c1p = reinterpret_cast<const uint8_t*>(p.hi) + (long long)f1 * p.D;
+#pragma unroll 2
+    for (int k = lane * F8L; k < p.D; k += 64 * F8L) {
+      const f8w w0 = ldw8(c0p + k), w1 = ldw8(c1p + k);
+      float c0[F8L], c1[F8L];
+      widen8(w0, c0);
+      widen8(w1, c1);
+#pragma unroll
+      for (int b = 0; b < B; ++b) {
+        float xv[F8L];
+        ldxf(sx + b * p.D + k, xv);
+        h0[b] = dotf8(c0, xv, h0[b]);
+        h1[b] = dotf8(c1, xv, h1[b]);
+      }
+    }
+  } else {
+#pragma unroll (B > 4 ? 2 : 4)            // (4 at B = 7 spills)
+    for (int k = lane * 8; k < p.D; k += 512) {
+      const bf16x8 w0 = ldw(p.hi + (long long)f0 * p.D + k), w1 = ldw(p.hi + (long long)f1 * p.D + k);
+      bf16x8 z0 = w0, z1 = w1;
+      if (p.lo) { z0 = ldw(p.lo + (long long)f0 * p.D + k); z1 = ldw(p.lo + (long long)f1 * p.D + k); }
+#pragma unroll
+      for (int b = 0; b < B; ++b) {
+        float xv[8];
+        ld8f(sx + b * p.D + k, xv);
+        h0[b] = dot8(w0, xv, h0[b]);
+        h1[b] = dot8(w1, xv, h1[b]);
+        if (p.lo) { l0[b] = dot8(z0, xv, l0[b]); l1[b] = dot8(z1, xv, l1[b]); }
+      }
+    }
+  }
+  float r0 = 1.f, r1 = 1.f;
+  if constexpr (F8) { r0 = 1.0f / p.wscale[f0]; r1 = 1.0f / p.wscale[f1]; }     // 2^-e: exact
+#pragma unroll
+  for (int b = 0; b < B; ++b) {
+    float v0 = wave_sum(h0[b]), v1 = wave_sum(h1[b]);
+    if constexpr (F8) { v0 *= r0; v1 *= r1; }
+    else if (p.lo) { v0 += wave_sum(l0[b]); v1 += wave_sum(l1[b]); }   // the eager path: C = hi.h, then C += lo.h
+    if (p.logits && lane == 0) {
+      p.logits[(long long)b * p.V + f0] = v0;
+      if (f1 != f0) p.logits[(long long)b * p.V + f1] = v1;
+    }
+    if (SAMPLE) {
+      if (b == lane) { y0 = v0; y1 = v1; }
+    } else {
+      if (better(v0, f0, bv[b], bi[b])) { bv[b] = v0; bi[b] = f0; }
+      if (f1 != f0 && better(v1, f1, bv[b], bi[b])) { bv[b] = v1; bi[b] = f1; }
+    }
+  }
+}
+
+// The block's partial of every row from its four waves' bests (greedy: bv / bi of lane 0; SAMPLE: lbv / lbi of lane b).
+template <int B, bool SAMPLE, class P>
+__device__ __forceinline__ void lm_block_partials(const P p, int lane, int w, const float (&bv)[B], const int (&bi)[B], float lbv,
+                                                  int lbi, float (*sv)[B], int (*si)[B]) {
+  if (SAMPLE) {
+    if (lane < B) { sv[w][lane] = lbv; si[w][lane] = lbi; }
+  } else if (lane == 0) {
+#pragma unroll
+    for (int b = 0; b < B; ++b) { sv[w][b] = bv[b]; si[w][b] = bi[b]; }
+  }
+  __syncthreads();
+  if (threadIdx.x < B) {
+    const int b = threadIdx.x;
+    float v = sv[0][b];
+    int i = si[0][b];
+    for (int k = 1; k < 4; ++k)
+      if (better(sv[k][b], si[k][b], v, i)) { v = sv[k][b]; i = si[k][b]; }
+    p.pval[(long long)blockIdx.x * B + b] = v;
+    p.pidx[(long long)blockIdx.x * B + b] = i;
+  }
+}
+
+// The LM head over an allowed set: `ids` are n vocabulary rows, sorted ascending, unique, inside [0, V).  A unit is the pair
+// ids[2u], ids[2u + 1] (the last unit of an odd n is one row) and runs lm_row_pair, so the logit of row j is the full kernel's
+// logit of j bit for bit; partials and the debug logits carry the vocabulary index, and the partial count stays
+// lap_decode_lm_blocks().  Units go to blocks first and to a block's waves second, so that a set of a few hundred rows is
+// streamed by as many CUs; a block without a unit writes the neutral partial and skips the norm.  An id outside [0, V) (a
+// broken caller) is never used as an address: its row is left out.
+// SAMPLE: row j takes word j & 1 of the Philox block (j >> 1, b, t, 0), as everywhere; the two rows of a unit share a block
+// only when they are 2m and 2m + 1.
+template <int B, bool SAMPLE, class P = LmP>
+__global__ __launch_bounds__(256) void dec_lm_head_subset_kernel(P p, const int* ids, int n) {
+  __shared__ __attribute__((aligned(16))) bf16 sx[B * DEC_D];
+  __shared__ float red[4];
+  __shared__ float sv[4][B];
+  __shared__ int si[4][B];
+  if (p.state[1]) return;
+  const int units = (n + 1) / 2;
+  if ((int)blockIdx.x >= units) {
+    if (threadIdx.x < B) {
+      p.pval[(long long)blockIdx.x * B + threadIdx.x] = -INFINITY;
+      p.pidx[(long long)blockIdx.x * B + threadIdx.x] = 0x7fffffff;
+    }
+    return;
+  }
+  norm_rows_to_lds<B>(p.x, p.gamma, p.D, p.eps, sx, red);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  float bv[B];
+  int bi[B];
+#pragma unroll
+  for (int b = 0; b < B; ++b) { bv[b] = -INFINITY; bi[b] = 0x7fffffff; }
+  float lbv = -INFINITY;
+  int lbi = 0x7fffffff;
+  uint32_t seed_lo = 0, seed_hi = 0, step = 0;
+  float inv_t = 0.f;
+  if (SAMPLE) {
+    seed_lo = (uint32_t)p.samp[0]; seed_hi = (uint32_t)p.samp[1]; inv_t = __int_as_float(p.samp[2]);
+    step = (uint32_t)p.state[0];
+  }
+  for (int u = blockIdx.x + w * gridDim.x; u < units; u += gridDim.x * 4) {
+    int f0 = ids[2 * u], f1 = ids[min(2 * u + 1, n - 1)];
+    const bool ok0 = (unsigned)f0 < (unsigned)p.V, ok1 = (unsigned)f1 < (unsigned)p.V;
+    if (!ok0 && !ok1) continue;
+    if (!ok0) f0 = f1;
+    if (!ok1) f1 = f0;
+    float y0 = 0.f, y1 = 0.f;
+    lm_row_pair<B, SAMPLE>(p, sx, lane, f0, f1, bv, bi, y0, y1);
+    if (SAMPLE) {
+      if (inv_t != 0.f)
+        lap_sampling::gumbel_scores_at(y0, y1, inv_t, seed_lo, seed_hi, step, (uint32_t)lane, (uint32_t)f0, (uint32_t)f1, y0, y1);
+      if (better(y0, f0, lbv, lbi)) { lbv = y0; lbi = f0; }
+      if (f1 != f0 && better(y1, f1, lbv, lbi)) { lbv = y1; lbi = f1; }
+    }
+  }
+  lm_block_partials<B, SAMPLE>(p, lane, w, bv, bi, lbv, lbi, sv, si);
+}
+
 // one block: per sample, the best of the partials (lowest index among ties); then out[:, t], EOS mask, t + 1, done.
 __global__ __launch_bounds__(256) void dec_finish_kernel(int* state, const float* pval, const int* pidx, int nblk, int* out, int cap,
                                                          int B, int eos_token) {
@@ -717,16 +858,28 @@ int proj_residual_impl(const int* state, const void* a, const void* w, const flo
   return LAP_OK;
 }
 
-// sampling == NULL: the greedy head.  f8: `hi` holds the code plane, `lo` is not used.
+// sampling == NULL: the greedy head.  f8: `hi` holds the code plane, `lo` is not used.  subset: the head over ids[0 .. n).
 int lm_head_impl(const int* state, const int* sampling, bool sample, const void* x, const float* gamma, const void* hi, const void* lo,
-                 const float* wscale, bool f8, int B, int D, int V, float eps, float* logits, float* pval, int* pidx, void* stream) {
+                 const float* wscale, bool f8, int B, int D, int V, float eps, float* logits, float* pval, int* pidx, void* stream,
+                 bool subset = false, const int* ids = nullptr, int n = 0) {
   if (!state || (sample && !sampling) || !gamma || !hi || !pval || !pidx || B < 1 || B > DEC_MAXB || D != DEC_D || V < 2 ||
-      !aligned16(x) || !aligned16(hi) || (lo && !aligned16(lo)) || (f8 && (!wscale || !f8_k_ok(D, 1)))) return LAP_ERR_ARG;
+      !aligned16(x) || !aligned16(hi) || (lo && !aligned16(lo)) || (f8 && (!wscale || !f8_k_ok(D, 1))) ||
+      (subset && (!ids || n < 1 || n > V))) return LAP_ERR_ARG;
   LmP8 p{};
   p.state = state; p.x = (const bf16*)x; p.gamma = gamma; p.eps = eps; p.hi = (const bf16*)hi; p.lo = f8 ? nullptr : (const bf16*)lo;
   p.V = V; p.D = D; p.logits = logits; p.pval = pval; p.pidx = pidx; p.samp = sampling;
   p.wscale = wscale;
   const LmP& pb = p;
+  if (subset) {
+    const dim3 g(LM_BLOCKS), t(256);
+    if (f8) {
+      if (sample) { DISPATCH_B(B, hipLaunchKernelGGL((dec_lm_head_subset_kernel<BB, true, LmP8>), g, t, 0, S_, p, ids, n)); }
+      else { DISPATCH_B(B, hipLaunchKernelGGL((dec_lm_head_subset_kernel<BB, false, LmP8>), g, t, 0, S_, p, ids, n)); }
+    } else if (sample) { DISPATCH_B(B, hipLaunchKernelGGL((dec_lm_head_subset_kernel<BB, true>), g, t, 0, S_, pb, ids, n)); }
+    else { DISPATCH_B(B, hipLaunchKernelGGL((dec_lm_head_subset_kernel<BB, false>), g, t, 0, S_, pb, ids, n)); }
+    LAP_CHECK_LAUNCH();
+    return LAP_OK;
+  }
   if (f8) {
     if (sample) { DISPATCH_B(B, hipLaunchKernelGGL((dec_lm_head_kernel<BB, true, LmP8>), dim3(LM_BLOCKS), dim3(256), 0, S_, p)); }
     else { DISPATCH_B(B, hipLaunchKernelGGL((dec_lm_head_kernel<BB, false, LmP8>), dim3(LM_BLOCKS), dim3(256), 0, S_, p)); }
@@ -859,4 +1012,29 @@ extern "C" int lap_decode_lm_head_sample_fp8(const int* state, const int* sampli
                                              const float* wscale, int B, int D, int V, float eps, float* logits, float* pval, int* pidx,
                                              void* stream) {
   return lm_head_impl(state, sampling, true, x, gamma, w8, nullptr, wscale, true, B, D, V, eps, logits, pval, pidx, stream);
+}
+
+// ---- constrained decoding: the four LM heads over an allowed set of vocabulary rows (ids: int32 [n], sorted, unique, in [0, V))
+extern "C" int lap_decode_lm_head_subset(const int* state, const void* x, const float* gamma, const void* hi, const void* lo,
+                                         const int* ids, int n, int B, int D, int V, float eps, float* logits, float* pval, int* pidx,
+                                         void* stream) {
+  return lm_head_impl(state, nullptr, false, x, gamma, hi, lo, nullptr, false, B, D, V, eps, logits, pval, pidx, stream, true, ids, n);
+}
+
+extern "C" int lap_decode_lm_head_subset_sample(const int* state, const int* sampling, const void* x, const float* gamma, const void* hi,
+                                                const void* lo, const int* ids, int n, int B, int D, int V, float eps, float* logits,
+                                                float* pval, int* pidx, void* stream) {
+  return lm_head_impl(state, sampling, true, x, gamma, hi, lo, nullptr, false, B, D, V, eps, logits, pval, pidx, stream, true, ids, n);
+}
+
+extern "C" int lap_decode_lm_head_subset_fp8(const int* state, const void* x, const float* gamma, const void* w8, const float* wscale,
+                                             const int* ids, int n, int B, int D, int V, float eps, float* logits, float* pval,
+                                             int* pidx, void* stream) {
+  return lm_head_impl(state, nullptr, false, x, gamma, w8, nullptr, wscale, true, B, D, V, eps, logits, pval, pidx, stream, true, ids, n);
+}
+
+extern "C" int lap_decode_lm_head_subset_sample_fp8(const int* state, const int* sampling, const void* x, const float* gamma,
+                                                    const void* w8, const float* wscale, const int* ids, int n, int B, int D, int V,
+                                                    float eps, float* logits, float* pval, int* pidx, void* stream) {
+  return lm_head_impl(state, sampling, true, x, gamma, w8, nullptr, wscale, true, B, D, V, eps, logits, pval, pidx, stream, true, ids, n);
 }

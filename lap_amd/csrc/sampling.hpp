@@ -36,4 +36,16 @@ __device__ __forceinline__ void gumbel_scores(float v0, float v1, float inv_t, u
   s1 = __fadd_rn(__fmul_rn(v1, inv_t), gumbel_from_word(w1));
 }
 
+// scores of vocabulary rows j0 and j1 of `row` (any two rows; j1 == j0: s1 is s0): row j takes word j & 1 of block j >> 1, and
+// one block serves both rows when they share it
+__device__ __forceinline__ void gumbel_scores_at(float v0, float v1, float inv_t, uint32_t seed_lo, uint32_t seed_hi, uint32_t step,
+                                                 uint32_t row, uint32_t j0, uint32_t j1, float& s0, float& s1) {
+  uint32_t a0, a1, b0, b1;
+  philox4x32_10(j0 >> 1, row, step, 0u, seed_lo, seed_hi, a0, a1);
+  b0 = a0; b1 = a1;
+  if ((j1 >> 1) != (j0 >> 1)) philox4x32_10(j1 >> 1, row, step, 0u, seed_lo, seed_hi, b0, b1);
+  s0 = __fadd_rn(__fmul_rn(v0, inv_t), gumbel_from_word((j0 & 1u) ? a1 : a0));
+  s1 = __fadd_rn(__fmul_rn(v1, inv_t), gumbel_from_word((j1 & 1u) ? b1 : b0));
+}
+
 }  // namespace lap_sampling

@@ -232,6 +232,10 @@ SIGNATURES: dict[str, list] = {
     "lap_decode_proj_residual_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "lap_decode_lm_head_fp8": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
     "lap_decode_lm_head_sample_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
+    "lap_decode_lm_head_subset": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
+    "lap_decode_lm_head_subset_sample": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
+    "lap_decode_lm_head_subset_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
+    "lap_decode_lm_head_subset_sample_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
 }
 
 _fn = {}
@@ -1446,24 +1450,38 @@ def decode_gate_up(state, x, gamma, wgu, act, eps=1e-6, wscale=None):
     call("lap_decode_gate_up", _p(state), _p(x), _p(gamma), _p(wgu), _p(act), B, D, act.shape[1], float(eps))
 
 
-def decode_lm_head(state, x, gamma, hi, lo, pval, pidx, logits=None, eps=1e-6, wscale=None):
-    """logits (debug): f32 [B, V] written when given.  wscale given: `hi` is the one e4m3 code plane of the table, lo is None."""
+def _ids_req(ids, V):
+    """The allowed set of a constrained LM head: int32 device ids [n], 1 <= n <= V (sorted, unique and inside [0, V): the caller's
+    part, see ar_decode.check_allowed_tokens; checking it here would read the device on every token)."""
+    _dreq(ids, torch.int32, "ids")
+    if ids.dim() != 1 or not 1 <= ids.numel() <= V:
+        raise ValueError(f"ids: expected 1 <= n <= V = {V} ids in one dimension, got shape {tuple(ids.shape)}")
+
+
+def decode_lm_head(state, x, gamma, hi, lo, pval, pidx, logits=None, eps=1e-6, wscale=None, ids=None):
+    """logits (debug): f32 [B, V] written when given.  wscale given: `hi` is the one e4m3 code plane of the table, lo is None.
+    ids given: the head over that allowed set only (lap_decode_lm_head_subset*): partials over the rows ids[.], logits written
+    at those indices alone."""
     _dreq(x, torch.bfloat16, "x"); _dreq(gamma, torch.float32, "gamma")
     if logits is not None:
         _dreq(logits, torch.float32, "logits")
     B, D = x.shape
+    sub, tail = "", ()
+    if ids is not None:
+        _ids_req(ids, hi.shape[0])
+        sub, tail = "_subset", (_p(ids), ids.numel())
     if wscale is not None:
         _f8req(hi, wscale, "hi")
         if lo is not None:
             raise TypeError("decode_lm_head: the fp8 table is one plane (lo must be None)")
-        call("lap_decode_lm_head_fp8", _p(state), _p(x), _p(gamma), _p(hi), _p(wscale), B, D, hi.shape[0], float(eps), _p(logits),
-             _p(pval), _p(pidx))
+        call(f"lap_decode_lm_head{sub}_fp8", _p(state), _p(x), _p(gamma), _p(hi), _p(wscale), *tail, B, D, hi.shape[0], float(eps),
+             _p(logits), _p(pval), _p(pidx))
         return
     _dreq(hi, torch.bfloat16, "hi")
     if lo is not None:
         _dreq(lo, torch.bfloat16, "lo")
-    call("lap_decode_lm_head", _p(state), _p(x), _p(gamma), _p(hi), _p(lo), B, D, hi.shape[0], float(eps), _p(logits), _p(pval),
-         _p(pidx))
+    call(f"lap_decode_lm_head{sub}", _p(state), _p(x), _p(gamma), _p(hi), _p(lo), *tail, B, D, hi.shape[0], float(eps), _p(logits),
+         _p(pval), _p(pidx))
 
 
 def decode_sampling(device):
@@ -1482,8 +1500,9 @@ def decode_set_sampling(buf, seed, temperature):
     buf.copy_(torch.from_numpy(words))
 
 
-def decode_lm_head_sample(state, sampling, x, gamma, hi, lo, pval, pidx, logits=None, eps=1e-6, wscale=None):
-    """`decode_lm_head` with the sampler of `sampling` (see `decode_sampling`) as its epilogue; logits (debug) stay raw."""
+def decode_lm_head_sample(state, sampling, x, gamma, hi, lo, pval, pidx, logits=None, eps=1e-6, wscale=None, ids=None):
+    """`decode_lm_head` with the sampler of `sampling` (see `decode_sampling`) as its epilogue; logits (debug) stay raw.  ids: the
+    allowed set, as in `decode_lm_head`; the noise of a row stays that of its vocabulary index."""
     _dreq(x, torch.bfloat16, "x"); _dreq(gamma, torch.float32, "gamma")
     _dreq(sampling, torch.int32, "sampling")
     if sampling.numel() < _fn["lap_decode_sampling_words"]():
@@ -1491,18 +1510,22 @@ def decode_lm_head_sample(state, sampling, x, gamma, hi, lo, pval, pidx, logits=
     if logits is not None:
         _dreq(logits, torch.float32, "logits")
     B, D = x.shape
+    sub, tail = "", ()
+    if ids is not None:
+        _ids_req(ids, hi.shape[0])
+        sub, tail = "_subset", (_p(ids), ids.numel())
     if wscale is not None:
         _f8req(hi, wscale, "hi")
         if lo is not None:
             raise TypeError("decode_lm_head_sample: the fp8 table is one plane (lo must be None)")
-        call("lap_decode_lm_head_sample_fp8", _p(state), _p(sampling), _p(x), _p(gamma), _p(hi), _p(wscale), B, D, hi.shape[0],
-             float(eps), _p(logits), _p(pval), _p(pidx))
+        call(f"lap_decode_lm_head{sub}_sample_fp8", _p(state), _p(sampling), _p(x), _p(gamma), _p(hi), _p(wscale), *tail, B, D,
+             hi.shape[0], float(eps), _p(logits), _p(pval), _p(pidx))
         return
     _dreq(hi, torch.bfloat16, "hi")
     if lo is not None:
         _dreq(lo, torch.bfloat16, "lo")
-    call("lap_decode_lm_head_sample", _p(state), _p(sampling), _p(x), _p(gamma), _p(hi), _p(lo), B, D, hi.shape[0], float(eps),
-         _p(logits), _p(pval), _p(pidx))
+    call(f"lap_decode_lm_head{sub}_sample", _p(state), _p(sampling), _p(x), _p(gamma), _p(hi), _p(lo), *tail, B, D, hi.shape[0],
+         float(eps), _p(logits), _p(pval), _p(pidx))
 
 
 def decode_finish(state, pval, pidx, out, eos_token):

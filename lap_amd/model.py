@@ -1421,7 +1421,7 @@ class LAP:
             self.serving_cache.refresh()
 
     def sample_tokens(self, rng, observation, *, max_decoding_steps: int = 390, temperature: float = 0.0, collect=None,
-                      decode: str = "eager", sampler: str = "host", decode_weights: str = "bf16"):
+                      decode: str = "eager", sampler: str = "host", decode_weights: str = "bf16", allowed_tokens=None):
         """lap.py:678-766 (LAP_AR serving mode): VLM-only prefill, then single-token decode until every sample has emitted
         EOS or `max_decoding_steps` tokens; returns int32 [B, max_decoding_steps] (zeros after the stop).
 
@@ -1456,10 +1456,20 @@ class LAP:
         head, half and a quarter of the bytes; "fp8_layers": the projections only, the LM head stays on the hi / lo bf16 planes
         of the f32 table (its precision decides greedy near-ties).  The kernels compute what the bf16 ones compute on the
         dequantised weights; the prefill and the embedding gather are unchanged.  The fp8 copies are cached on the model and
-        follow the parameters (`refresh_serve_caches`).  Needs decode="fused"."""
+        follow the parameters (`refresh_serve_caches`).  Needs decode="fused".
+
+        allowed_tokens: constrained decoding.  None (default): the whole vocabulary, as before.  Any integer sequence or tensor
+        of token ids, one set for all rows (duplicates and order do not matter; it must hold the EOS token, ids outside the
+        vocabulary and an empty set raise ValueError): every token is the argmax over the set of the score the unconstrained
+        decode gives that vocabulary index, lowest index among ties, i.e. what the unconstrained rule picks on logits set to
+        -inf outside the set; under sampler="device" the noise of index j stays that of j.  decode="fused" streams only the
+        set's rows of the LM head (lap_decode_lm_head_subset*), with logits equal to the unconstrained kernel's bit for bit;
+        decode="eager" masks its stored logits.  `collect["logit/<t>"]` is full width with -inf outside the set.
+        `policy_io.allowed_token_ids` builds a set from example language actions."""
         from lap_amd import ar_decode       # (it imports this module)
         return ar_decode.sample_tokens(self, rng, observation, max_decoding_steps=max_decoding_steps, temperature=temperature,
-                                       collect=collect, decode=decode, sampler=sampler, decode_weights=decode_weights)
+                                       collect=collect, decode=decode, sampler=sampler, decode_weights=decode_weights,
+                                       allowed_tokens=allowed_tokens)
 
     DECODE_WEIGHTS = ("bf16", "fp8", "fp8_layers")
 

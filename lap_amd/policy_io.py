@@ -541,6 +541,19 @@ class PaligemmaTokenizer:
         return self._tokenizer.encode(text, add_bos=add_bos, add_eos=add_eos)
 
 
+def allowed_token_ids(tokenizer: PaligemmaTokenizer, texts, extra_ids=()) -> np.ndarray:
+    """The allowed set of a constrained decode (`LAP.sample_tokens(allowed_tokens=...)`) from example language actions of one's
+    format: the sorted unique ids (int32) of the tokenizer's encodings of `texts` (cleaned as `tokenize` cleans a language
+    action before it encodes it), of its EOS token and of `extra_ids`.  The examples must cover every word, digit and sign the
+    format can produce; the grammar of a format is not enumerated here."""
+    sp = tokenizer._tokenizer
+    ids = {int(sp.eos_id())}
+    for text in texts:
+        ids.update(int(t) for t in sp.encode(text.strip().replace("_", " ").replace("\n", " "), add_bos=False, add_eos=False))
+    ids.update(int(t) for t in extra_ids)
+    return np.asarray(sorted(ids), dtype=np.int32)
+
+
 @dataclasses.dataclass(frozen=True)
 class TokenizePromptAndReasoning:
     """transforms.py:27-113: consumes prompt / language_actions / dataset_name / frame_description / time horizon, adds the

@@ -101,13 +101,19 @@ class GraphedTokenDecoder:
 
     weights: `sample_tokens`' `decode_weights` ("bf16", "fp8", "fp8_layers"): the step graph is captured on the fp8 kernels and
     holds the addresses of the model's fp8 weight cache, which `refresh_serve_caches` re-quantises in place before a replay
-    when the parameters have changed.  Composes with sampling=True."""
+    when the parameters have changed.  Composes with sampling=True.
+
+    allowed_tokens: `sample_tokens`' constrained decoding, fixed at construction (the graphs hold the address of the id buffer):
+    every call decodes inside that set.  None: the whole vocabulary.  Composes with sampling= and weights=."""
 
     def __init__(self, model: LAP, batch_size: int = 1, max_decoding_steps: int = 390, prompt_len: int | None = None,
-                 steps_per_replay: int = 8, sampling: bool = False, weights: str = "bf16"):
+                 steps_per_replay: int = 8, sampling: bool = False, weights: str = "bf16", allowed_tokens=None):
         ar_decode.check_fused_decode(model, batch_size)
         ar_decode.check_decode_weights(weights)
         self.weights = weights
+        self.allowed = None
+        if allowed_tokens is not None:
+            self.allowed = ar_decode.allowed_set(model, allowed_tokens).ids
         if max_decoding_steps < 1 or steps_per_replay < 1:
             raise ValueError("max_decoding_steps and steps_per_replay must be >= 1")
         self.model, self.B, self.max_steps, self.spr = model, batch_size, max_decoding_steps, steps_per_replay
@@ -136,7 +142,8 @@ class GraphedTokenDecoder:
     def _prefill(self):
         pre = ar_decode.prefill(self.model, self.obs)
         if self.ctx is None:
-            self.ctx = ar_decode.DecodeCtx(self.model, self.B, pre.Pn, self.max_steps, self.sampling, self.weights)
+            self.ctx = ar_decode.DecodeCtx(self.model, self.B, pre.Pn, self.max_steps, self.sampling, self.weights,
+                                           allowed=self.allowed)
         self.ctx.first_token(pre)
 
     def _steps(self):
@@ -331,9 +338,14 @@ class ARPolicy:
         if weights != "bf16":
             if self._sample_kwargs.setdefault("decode", "fused") != "fused":
                 raise ValueError(f"ARPolicy: decode_weights={weights!r} needs decode=\"fused\", got {self._sample_kwargs['decode']!r}")
+        # sample_kwargs["allowed_tokens"] (constrained decoding) reaches both routes as well: the set is checked and put on the
+        # device once, here; the decoder is captured with it and sample_tokens gets the checked set on every call
+        if self._sample_kwargs.get("allowed_tokens") is not None:
+            self._sample_kwargs["allowed_tokens"] = ar_decode.allowed_set(base.model, self._sample_kwargs["allowed_tokens"])
         if use_graph and base.model.decode_supported(1):
             self._decoder = GraphedTokenDecoder(base.model, 1, self._sample_kwargs.get("max_decoding_steps", 390),
-                                                sampling=self._device_sampler, weights=weights)
+                                                sampling=self._device_sampler, weights=weights,
+                                                allowed_tokens=self._sample_kwargs.get("allowed_tokens"))
 
     def __getattr__(self, name):
         return getattr(self._base, name)
@@ -377,7 +389,8 @@ def create_trained_policy_ar(*args, sample_kwargs: dict | None = None, language_
     as in the reference's standard stack it would act on the normalised `state` only).
     ar_graph: serve greedy requests through a GraphedTokenDecoder (ARPolicy(use_graph=True)); off by default.  With
     sample_kwargs={"temperature": T, "sampler": "device"} the same graphs serve sampled requests too;
-    sample_kwargs={"decode_weights": "fp8" | "fp8_layers"} decodes on fp8 weights (implies decode="fused") on either route."""
+    sample_kwargs={"decode_weights": "fp8" | "fp8_layers"} decodes on fp8 weights (implies decode="fused") on either route;
+    sample_kwargs={"allowed_tokens": ids} constrains every token to that set on either route (`policy_io.allowed_token_ids`)."""
     from lap_amd import policy_io as pio
 
     base = create_trained_policy(*args, use_graph=False, **kwargs)

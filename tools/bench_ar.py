@@ -4,6 +4,7 @@ rate against the 6.29 TB/s measured copy rate.  Random weights, the reference pr
 run decodes N tokens.  One JSON line.
 
     python tools/bench_ar.py [--tokens 64] [--config lap_bench] [--kwaves 4] [--temperature T] [--weights bf16 fp8 fp8_layers]
+                             [--allowed N]
 
 --temperature T > 0 adds the sampled figures: the eager loop with the torch-generator noise (sampler="host"), the eager loop and
 the fused steps with the device noise (sampler="device"), and a GraphedTokenDecoder(sampling=True) called sampled and greedy.
@@ -12,6 +13,10 @@ the fused steps with the device noise (sampler="device"), and a GraphedTokenDeco
 side by side and in the same process, its fused and graphed ms per token, its bytes per token and achieved rate, how many of the
 graphed tokens agree with the bf16 graph's, and the relative error of its first and second tokens' logits against bf16's.
 --profile-graphed replays the graph of the LAST value named.
+--allowed N adds constrained decoding (`allowed_tokens=` the N lowest ids; EOS stays disabled, so the set need not hold it): for
+bf16 and every --weights value, in the same process, the graphed ms per token without and with the set (the mean and the
+[min, max] of the timed repeats, which is the run-to-run spread to read the difference against), the bytes per token with the
+set and whether every constrained token lies in it.  --profile-graphed --allowed N replays the constrained graph.
 """
 import argparse
 import json
@@ -36,6 +41,7 @@ ap.add_argument("--profile-graphed", action="store_true", help="capture, replay 
 ap.add_argument("--temperature", type=float, default=0.0, help="> 0: also measure sampled decoding at this temperature")
 ap.add_argument("--weights", nargs="+", default=["bf16"], choices=list(LAP.DECODE_WEIGHTS),
                 help="decode weights to measure next to bf16 (fp8, fp8_layers)")
+ap.add_argument("--allowed", type=int, default=0, help="> 0: also measure constrained decoding over the N lowest token ids")
 a = ap.parse_args()
 hip.DECODE_KWAVES_DOWN = a.kwaves
 
@@ -63,12 +69,13 @@ def timeit(fn, n):
 
 
 T = a.temperature
+allowed = list(range(a.allowed)) if a.allowed > 0 else None
 if a.profile_graphed:
     if T > 0.0:
-        sdec = GraphedTokenDecoder(model, 1, N, sampling=True, weights=a.weights[-1])
+        sdec = GraphedTokenDecoder(model, 1, N, sampling=True, weights=a.weights[-1], allowed_tokens=allowed)
         sdec(o, temperature=T, seed=1)
-    elif a.weights[-1] != "bf16":
-        GraphedTokenDecoder(model, 1, N, weights=a.weights[-1])(o)
+    elif a.weights[-1] != "bf16" or allowed is not None:
+        GraphedTokenDecoder(model, 1, N, weights=a.weights[-1], allowed_tokens=allowed)(o)
     else:
         dec(o)
     torch.cuda.synchronize()
@@ -108,6 +115,33 @@ for wname in dict.fromkeys(w for w in a.weights if w != "bf16"):
         "tokens_equal_to_bf16_graph": int((qgot == got).sum()), "leading_tokens_equal_to_bf16_graph": int((qgot == got).cumprod(1).sum()),
         "first_token_logit_rel_err_vs_bf16": round(float((c8["logit/0"] - c16["logit/0"]).norm() / c16["logit/0"].norm()), 5),
         "second_token_logit_rel_err_vs_bf16": round(float((c8["logit/1"] - c16["logit/1"]).norm() / c16["logit/1"].norm()), 5)}
+constrained = {}
+if allowed is not None:
+    def per_token(d):
+        """mean and [min, max] over the timed repeats of the graphed ms per token of decoder `d`"""
+        d.capture()
+        t0 = timeit(lambda: (d.g_prefill.replay()), a.reps)
+        ms = [per(timeit(lambda: d(o), 1), t0) for _ in range(max(a.reps, 3))]
+        return round(sum(ms) / len(ms), 3), [round(min(ms), 3), round(max(ms), 3)]
+
+    row = 2 * v.width
+    for wname in dict.fromkeys(["bf16", *a.weights]):
+        free_ms, free_spread = per_token(GraphedTokenDecoder(model, 1, N, weights=wname))
+        cdec = GraphedTokenDecoder(model, 1, N, weights=wname, allowed_tokens=allowed)
+        c_ms, c_spread = per_token(cdec)
+        cgot = cdec(o)
+        f8_head = wname == "fp8"
+        layers = v.depth * layer // (1 if wname == "bf16" else 2)
+        c_head = a.allowed * (row // 2 if f8_head else row * (2 if model.ps.w16lo("llm/embed") is not None else 1))
+        constrained[wname] = {
+            "graphed_ms_per_token": free_ms, "graphed_ms_per_token_min_max": free_spread,
+            "constrained_graphed_ms_per_token": c_ms, "constrained_graphed_ms_per_token_min_max": c_spread,
+            "constrained_speedup": round(free_ms / c_ms, 3),
+            "algorithmic_bytes_per_token": layers + (head // 4 if f8_head else head),
+            "constrained_algorithmic_bytes_per_token": layers + c_head,
+            "constrained_tokens_inside_the_set": bool((cgot < a.allowed).all()),
+            "constrained_equals_fused_constrained": bool(torch.equal(cgot, model.sample_tokens(
+                0, o, max_decoding_steps=N, decode="fused", decode_weights=wname, allowed_tokens=allowed)))}
 sampled = {}
 if T > 0.0:
     st = lambda **kw: (lambda: model.sample_tokens(1, o, max_decoding_steps=N, temperature=T, **kw))
@@ -137,4 +171,5 @@ print(json.dumps({
     "graphed_vs_eager_leading_tokens_equal": agree, "graphed_equals_eager": bool(torch.equal(got, eager)),
     "algorithmic_bytes_per_token": bytes_tok, "floor_ms_per_token_at_6.29TBps": round(bytes_tok / 6.29e12 * 1e3, 3),
     "achieved_GBps_graphed": round(bytes_tok / (g_ms * 1e-3) / 1e9, 1),
-    "share_of_6.29TBps": round(bytes_tok / (g_ms * 1e-3) / 6.29e12, 3), "down_proj_kwaves": a.kwaves} | sampled | ({"weights": quant} if quant else {})))
+    "share_of_6.29TBps": round(bytes_tok / (g_ms * 1e-3) / 6.29e12, 3), "down_proj_kwaves": a.kwaves} | sampled | ({"weights": quant} if quant else {})
+    | ({"allowed": a.allowed, "constrained": constrained} if constrained else {})))
