@@ -22,6 +22,12 @@
 //   lm_head_sample   lm_head whose partials are over score = logit * inv_t + Gumbel noise of (seed, t, b, vocabulary row)
 //               (sampling.hpp) when the sampling words {seed low, seed high, bits of inv_t, 0} hold inv_t != 0, and lm_head's
 //               partials bit for bit when inv_t == 0                                        (lap_gumbel_argmax_rows_f32)
+//   lm_head_subset*  the same heads over an allowed set of vocabulary rows (constrained decoding)
+//               All LM heads are ONE kernel template, dec_lm_head_kernel<B, SAMPLE, SUBSET, P>, over ONE statement of the row
+//               dot product (lm_row_pair) and of the block partials (lm_block_partials): full or subset, greedy or sampling, a
+//               head differs only in which two rows a unit is, which wave takes it and which noise call it makes.  So the
+//               logit of vocabulary row j is the same bits in every head by construction, and tests/test_decode_bits_gpu.py
+//               pins those bits (and the projections') to a recorded fixture: a change to the arithmetic shows there.
 //   finish      one block: argmax over the partials with the lowest index among ties, out[:, t] = token, EOS mask, t += 1,
 //               done                                                                         (lap_argmax_rows_f32)
 // Rounding points are those of the eager step; only the summation order of the dot products differs.
@@ -439,128 +445,25 @@ struct LmP {
   float* logits;                       // debug: f32 [B][V] or NULL
   float* pval; int* pidx;              // partials [gridDim.x][B]
   const int* samp;                     // SAMPLE: {seed low, seed high, bits of inv_t (0 = greedy), reserved}
+  const int* ids; int n;               // SUBSET: the allowed vocabulary rows, sorted ascending, unique, inside [0, V)
 };
 
-// SAMPLE: the sampler is the epilogue of a unit.  After the wave_sums the two logits of all B rows are wave-uniform; lane b
-// keeps row b's pair, runs row b's Philox block and its four logarithms (B <= 8 lanes carry data, the instruction count is that
-// of one row) and folds the two scores into ITS running best, so the B-fold compare chain of the greedy form becomes one.
-// The <B, false> instances are the greedy kernel unchanged.
 // P = LmP8: `hi` is ONE plane of e4m3 codes with a scale per vocabulary row instead of the hi / lo bf16 planes; partials,
-// sampling epilogue and the debug logits are those of the LmP instances, which are the bf16 kernels unchanged.
+// sampling epilogue and the debug logits are those of the LmP instances.
 struct LmP8 : LmP {
   const float* wscale;                 // [V] 2^e per vocabulary row
 };
 
-template <int B, bool SAMPLE, class P = LmP>
-__global__ __launch_bounds__(256) void dec_lm_head_kernel(P p) {
-  constexpr bool F8 = std::is_same<P, LmP8>::value;
-  __shared__ __attribute__((aligned(16))) bf16 sx[B * DEC_D];
-  __shared__ float red[4];
-  __shared__ float sv[4][B];
-  __shared__ int si[4][B];
-  if (p.state[1]) return;
-  norm_rows_to_lds<B>(p.x, p.gamma, p.D, p.eps, sx, red);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  float bv[B];
-  int bi[B];
-#pragma unroll
-  for (int b = 0; b < B; ++b) { bv[b] = -INFINITY; bi[b] = 0x7fffffff; }
-  float lbv = -INFINITY;               // SAMPLE: lane b's running best of row b
-  int lbi = 0x7fffffff;
-  uint32_t seed_lo = 0, seed_hi = 0, step = 0;
-  float inv_t = 0.f;
-  if (SAMPLE) {
-    seed_lo = (uint32_t)p.samp[0]; seed_hi = (uint32_t)p.samp[1]; inv_t = __int_as_float(p.samp[2]);
-    step = (uint32_t)p.state[0];
-  }
-  const int units = (p.V + 1) / 2;
-  for (int u = blockIdx.x * 4 + w; u < units; u += gridDim.x * 4) {
-    const int f0 = 2 * u, f1 = min(2 * u + 1, p.V - 1);
-    float h0[B], h1[B], l0[B], l1[B];
-#pragma unroll
-    for (int b = 0; b < B; ++b) { h0[b] = 0.f; h1[b] = 0.f; l0[b] = 0.f; l1[b] = 0.f; }
-    if constexpr (F8) {
-      const uint8_t* c0p = reinterpret_cast<const uint8_t*>(p.hi) + (long long)f0 * p.D;
-      const uint8_t* c1p = reinterpret_cast<const uint8_t*>(p.hi) + (long long)f1 * p.D;
-#pragma unroll 2
-      for (int k = lane * F8L; k < p.D; k += 64 * F8L) {
-        const f8w w0 = ldw8(c0p + k), w1 = ldw8(c1p + k);
-        float c0[F8L], c1[F8L];
-        widen8(w0, c0);
-        widen8(w1, c1);
-#pragma unroll
-        for (int b = 0; b < B; ++b) {
-          float xv[F8L];
-          ldxf(sx + b * p.D + k, xv);
-          h0[b] = dotf8(c0, xv, h0[b]);
-          h1[b] = dotf8(c1, xv, h1[b]);
-        }
-      }
-    } else {
-#pragma unroll (B > 4 ? 2 : 4)            // (4 at B = 7 spills)
-      for (int k = lane * 8; k < p.D; k += 512) {
-        const bf16x8 w0 = ldw(p.hi + (long long)f0 * p.D + k), w1 = ldw(p.hi + (long long)f1 * p.D + k);
-        bf16x8 z0 = w0, z1 = w1;
-        if (p.lo) { z0 = ldw(p.lo + (long long)f0 * p.D + k); z1 = ldw(p.lo + (long long)f1 * p.D + k); }
-#pragma unroll
-        for (int b = 0; b < B; ++b) {
-          float xv[8];
-          ld8f(sx + b * p.D + k, xv);
-          h0[b] = dot8(w0, xv, h0[b]);
-          h1[b] = dot8(w1, xv, h1[b]);
-          if (p.lo) { l0[b] = dot8(z0, xv, l0[b]); l1[b] = dot8(z1, xv, l1[b]); }
-        }
-      }
-    }
-    float y0 = 0.f, y1 = 0.f;
-    float r0 = 1.f, r1 = 1.f;
-    if constexpr (F8) { r0 = 1.0f / p.wscale[f0]; r1 = 1.0f / p.wscale[f1]; }     // 2^-e: exact
-#pragma unroll
-    for (int b = 0; b < B; ++b) {
-      float v0 = wave_sum(h0[b]), v1 = wave_sum(h1[b]);
-      if constexpr (F8) { v0 *= r0; v1 *= r1; }
-      else if (p.lo) { v0 += wave_sum(l0[b]); v1 += wave_sum(l1[b]); }   // the eager path: C = hi.h, then C += lo.h
-      if (p.logits && lane == 0) {
-        p.logits[(long long)b * p.V + f0] = v0;
-        if (f1 != f0) p.logits[(long long)b * p.V + f1] = v1;
-      }
-      if (SAMPLE) {
-        if (b == lane) { y0 = v0; y1 = v1; }
-      } else {
-        if (better(v0, f0, bv[b], bi[b])) { bv[b] = v0; bi[b] = f0; }
-        if (f1 != f0 && better(v1, f1, bv[b], bi[b])) { bv[b] = v1; bi[b] = f1; }
-      }
-    }
-    if (SAMPLE) {
-      if (inv_t != 0.f) lap_sampling::gumbel_scores(y0, y1, inv_t, seed_lo, seed_hi, step, (uint32_t)lane, (uint32_t)u, y0, y1);
-      if (better(y0, f0, lbv, lbi)) { lbv = y0; lbi = f0; }
-      if (f1 != f0 && better(y1, f1, lbv, lbi)) { lbv = y1; lbi = f1; }
-    }
-  }
-  if (SAMPLE) {
-    if (lane < B) { sv[w][lane] = lbv; si[w][lane] = lbi; }
-  } else if (lane == 0) {
-#pragma unroll
-    for (int b = 0; b < B; ++b) { sv[w][b] = bv[b]; si[w][b] = bi[b]; }
-  }
-  __syncthreads();
-  if (threadIdx.x < B) {
-    const int b = threadIdx.x;
-    float v = sv[0][b];
-    int i = si[0][b];
-    for (int k = 1; k < 4; ++k)
-      if (better(sv[k][b], si[k][b], v, i)) { v = sv[k][b]; i = si[k][b]; }
-    p.pval[(long long)blockIdx.x * B + b] = v;
-    p.pidx[(long long)blockIdx.x * B + b] = i;
-  }
-}
-
-// The logits of vocabulary rows f0 and f1 (f1 == f0: one row) for all B rows of `sx`, wave-uniform after the wave_sums: the
-// debug store, and either lane b's pair (SAMPLE: y0 / y1 of lane b = row b) or the running best of every row (greedy).  This
-// restates the unit body of dec_lm_head_kernel (k-to-lane map, order of the fmas, wave_sums), so that a row's logit is the
-// same bits in both; that kernel keeps its own text because its code must not move.
+// The row dot product of the LM head.  Every head (full or subset, greedy or sampling, bf16 or fp8) runs this one statement of
+// it, so the logit of vocabulary row j is the same bits in all of them by construction; tests/test_decode_bits_gpu.py pins
+// those bits to a recorded fixture.  The logits of rows f0 and f1 (f1 == f0: one row) for all B rows of `sx` are wave-uniform
+// after the wave_sums: the debug store, and either lane b's pair (SAMPLE: y0 / y1 of lane b = row b) or the running best of
+// every row (greedy).
+// SAMPLE: the sampler is the epilogue of a unit.  Lane b keeps row b's pair, runs row b's Philox block and its four logarithms
+// (B <= 8 lanes carry data, the instruction count is that of one row) and folds the two scores into ITS running best, so the
+// B-fold compare chain of the greedy form becomes one.
 template <int B, bool SAMPLE, class P>
-__device__ __forceinline__ void lm_row_pair(const P p, const bf16* sx, int lane, int f0, int f1, float (&bv)[B], int (&bi)[B],
+__device__ __forceinline__ void lm_row_pair(const P& p, const bf16* sx, int lane, int f0, int f1, float (&bv)[B], int (&bi)[B],
                                             float& y0, float& y1) {
   constexpr bool F8 = std::is_same<P, LmP8>::value;
   float h0[B], h1[B], l0[B], l1[B];
@@ -621,7 +524,7 @@ __device__ __forceinline__ void lm_row_pair(const P p, const bf16* sx, int lane,
 
 // The block's partial of every row from its four waves' bests (greedy: bv / bi of lane 0; SAMPLE: lbv / lbi of lane b).
 template <int B, bool SAMPLE, class P>
-__device__ __forceinline__ void lm_block_partials(const P p, int lane, int w, const float (&bv)[B], const int (&bi)[B], float lbv,
+__device__ __forceinline__ void lm_block_partials(const P& p, int lane, int w, const float (&bv)[B], const int (&bi)[B], float lbv,
                                                   int lbi, float (*sv)[B], int (*si)[B]) {
   if (SAMPLE) {
     if (lane < B) { sv[w][lane] = lbv; si[w][lane] = lbi; }
@@ -641,23 +544,25 @@ __device__ __forceinline__ void lm_block_partials(const P p, int lane, int w, co
   }
 }
 
-// The LM head over an allowed set: `ids` are n vocabulary rows, sorted ascending, unique, inside [0, V).  A unit is the pair
-// ids[2u], ids[2u + 1] (the last unit of an odd n is one row) and runs lm_row_pair, so the logit of row j is the full kernel's
-// logit of j bit for bit; partials and the debug logits carry the vocabulary index, and the partial count stays
-// lap_decode_lm_blocks().  Units go to blocks first and to a block's waves second, so that a set of a few hundred rows is
-// streamed by as many CUs; a block without a unit writes the neutral partial and skips the norm.  An id outside [0, V) (a
-// broken caller) is never used as an address: its row is left out.
-// SAMPLE: row j takes word j & 1 of the Philox block (j >> 1, b, t, 0), as everywhere; the two rows of a unit share a block
-// only when they are 2m and 2m + 1.
-template <int B, bool SAMPLE, class P = LmP>
-__global__ __launch_bounds__(256) void dec_lm_head_subset_kernel(P p, const int* ids, int n) {
+// The LM heads.  A unit is two vocabulary rows run through lm_row_pair by one wave; the heads differ only in which rows a unit
+// is and which wave takes it.
+// Full: unit u is rows 2u, 2u + 1 (the last unit of an odd V is one row), unit u = 4 blockIdx.x + w.  SAMPLE: the rows share the
+// Philox block (u, b, t, 0).
+// SUBSET (the head over an allowed set p.ids[0 .. n)): unit u is the pair ids[2u], ids[2u + 1] (the last unit of an odd n is one
+// row); partials and the debug logits carry the vocabulary index, and the partial count stays lap_decode_lm_blocks().  Units go
+// to blocks first and to a block's waves second, so that a set of a few hundred rows is streamed by as many CUs; a block
+// without a unit writes the neutral partial and skips the norm.  An id outside [0, V) (a broken caller) is never used as an
+// address: its row is left out.  SAMPLE: row j takes word j & 1 of the Philox block (j >> 1, b, t, 0), as everywhere; the two
+// rows of a unit share a block only when they are 2m and 2m + 1.
+template <int B, bool SAMPLE, bool SUBSET, class P>
+__global__ __launch_bounds__(256) void dec_lm_head_kernel(P p) {
   __shared__ __attribute__((aligned(16))) bf16 sx[B * DEC_D];
   __shared__ float red[4];
   __shared__ float sv[4][B];
   __shared__ int si[4][B];
   if (p.state[1]) return;
-  const int units = (n + 1) / 2;
-  if ((int)blockIdx.x >= units) {
+  const int units = ((SUBSET ? p.n : p.V) + 1) / 2;
+  if (SUBSET && (int)blockIdx.x >= units) {
     if (threadIdx.x < B) {
       p.pval[(long long)blockIdx.x * B + threadIdx.x] = -INFINITY;
       p.pidx[(long long)blockIdx.x * B + threadIdx.x] = 0x7fffffff;
@@ -670,7 +575,7 @@ __global__ __launch_bounds__(256) void dec_lm_head_subset_kernel(P p, const int*
   int bi[B];
 #pragma unroll
   for (int b = 0; b < B; ++b) { bv[b] = -INFINITY; bi[b] = 0x7fffffff; }
-  float lbv = -INFINITY;
+  float lbv = -INFINITY;               // SAMPLE: lane b's running best of row b
   int lbi = 0x7fffffff;
   uint32_t seed_lo = 0, seed_hi = 0, step = 0;
   float inv_t = 0.f;
@@ -678,17 +583,24 @@ __global__ __launch_bounds__(256) void dec_lm_head_subset_kernel(P p, const int*
     seed_lo = (uint32_t)p.samp[0]; seed_hi = (uint32_t)p.samp[1]; inv_t = __int_as_float(p.samp[2]);
     step = (uint32_t)p.state[0];
   }
-  for (int u = blockIdx.x + w * gridDim.x; u < units; u += gridDim.x * 4) {
-    int f0 = ids[2 * u], f1 = ids[min(2 * u + 1, n - 1)];
-    const bool ok0 = (unsigned)f0 < (unsigned)p.V, ok1 = (unsigned)f1 < (unsigned)p.V;
-    if (!ok0 && !ok1) continue;
-    if (!ok0) f0 = f1;
-    if (!ok1) f1 = f0;
+  for (int u = SUBSET ? blockIdx.x + w * gridDim.x : blockIdx.x * 4 + w; u < units; u += gridDim.x * 4) {
+    int f0, f1;
+    if (SUBSET) {
+      f0 = p.ids[2 * u]; f1 = p.ids[min(2 * u + 1, p.n - 1)];
+      const bool ok0 = (unsigned)f0 < (unsigned)p.V, ok1 = (unsigned)f1 < (unsigned)p.V;
+      if (!ok0 && !ok1) continue;
+      if (!ok0) f0 = f1;
+      if (!ok1) f1 = f0;
+    } else {
+      f0 = 2 * u; f1 = min(2 * u + 1, p.V - 1);
+    }
     float y0 = 0.f, y1 = 0.f;
     lm_row_pair<B, SAMPLE>(p, sx, lane, f0, f1, bv, bi, y0, y1);
     if (SAMPLE) {
-      if (inv_t != 0.f)
-        lap_sampling::gumbel_scores_at(y0, y1, inv_t, seed_lo, seed_hi, step, (uint32_t)lane, (uint32_t)f0, (uint32_t)f1, y0, y1);
+      if (inv_t != 0.f) {
+        if (SUBSET) lap_sampling::gumbel_scores_at(y0, y1, inv_t, seed_lo, seed_hi, step, (uint32_t)lane, (uint32_t)f0, (uint32_t)f1, y0, y1);
+        else lap_sampling::gumbel_scores(y0, y1, inv_t, seed_lo, seed_hi, step, (uint32_t)lane, (uint32_t)u, y0, y1);
+      }
       if (better(y0, f0, lbv, lbi)) { lbv = y0; lbi = f0; }
       if (f1 != f0 && better(y1, f1, lbv, lbi)) { lbv = y1; lbi = f1; }
     }
@@ -805,6 +717,18 @@ __global__ __launch_bounds__(256) void quant_fp8_rows_kernel(const T* src, uint8
 // a wave's K slice is whole lane loads of the code stream (a slice of 512 codes keeps half the lanes of a 16-byte load busy)
 inline bool f8_k_ok(int K, int kwaves) { return K % 16 == 0 && K % kwaves == 0 && (K / kwaves) % F8L == 0; }
 
+// the launch of one projection (EPI, NORM, KW) on the bf16 or the fp8 weight stream, at the batch B
+template <int EPI, bool NORM, int KW, class P>
+int launch_proj_p(const P& p, int B, dim3 grid, void* stream) {
+  DISPATCH_B(B, hipLaunchKernelGGL((dec_proj_kernel<EPI, BB, NORM, KW, P>), grid, dim3(256), 0, S_, p));
+  LAP_CHECK_LAUNCH();
+  return LAP_OK;
+}
+template <int EPI, bool NORM, int KW>
+int launch_proj(const ProjP8& p, bool f8, int B, dim3 grid, void* stream) {
+  return f8 ? launch_proj_p<EPI, NORM, KW, ProjP8>(p, B, grid, stream) : launch_proj_p<EPI, NORM, KW, ProjP>(p, B, grid, stream);
+}
+
 int qkv_impl(const int* state, const void* x, const float* gamma, const void* wqkv, const float* wscale, bool f8, void* q,
              void* cache_k, void* cache_v, int B, int D, int NH, int HD, int cap, float q_scale, float eps, void* stream) {
   if (!lap_decode_ok(B, D, NH, 1, HD, DEC_H, 2) || !state || !gamma || !q || !cache_k || !cache_v || cap < 1 ||
@@ -813,12 +737,7 @@ int qkv_impl(const int* state, const void* x, const float* gamma, const void* wq
   p.state = state; p.x = (const bf16*)x; p.gamma = gamma; p.w = (const bf16*)wqkv; p.K = D; p.units = (NH + 2) * HD / 2;
   p.eps = eps; p.q = (bf16*)q; p.ck = (bf16*)cache_k; p.cv = (bf16*)cache_v; p.cap = cap; p.NH = NH; p.HD = HD; p.q_scale = q_scale;
   p.wscale = wscale;
-  const ProjP& pb = p;
-  const dim3 grid((p.units + 3) / 4);
-  if (f8) { DISPATCH_B(B, hipLaunchKernelGGL((dec_proj_kernel<EPI_QKV, BB, true, 1, ProjP8>), grid, dim3(256), 0, S_, p)); }
-  else { DISPATCH_B(B, hipLaunchKernelGGL((dec_proj_kernel<EPI_QKV, BB, true, 1>), grid, dim3(256), 0, S_, pb)); }
-  LAP_CHECK_LAUNCH();
-  return LAP_OK;
+  return launch_proj<EPI_QKV, true, 1>(p, f8, B, dim3((p.units + 3) / 4), stream);
 }
 
 int gate_up_impl(const int* state, const void* x, const float* gamma, const void* wgu, const float* wscale, bool f8, void* act,
@@ -829,12 +748,7 @@ int gate_up_impl(const int* state, const void* x, const float* gamma, const void
   p.state = state; p.x = (const bf16*)x; p.gamma = gamma; p.w = (const bf16*)wgu; p.K = D; p.units = H; p.H = H; p.eps = eps;
   p.out = (bf16*)act;
   p.wscale = wscale;
-  const ProjP& pb = p;
-  const dim3 grid(min(H / 4, 1024));
-  if (f8) { DISPATCH_B(B, hipLaunchKernelGGL((dec_proj_kernel<EPI_GEGLU, BB, true, 1, ProjP8>), grid, dim3(256), 0, S_, p)); }
-  else { DISPATCH_B(B, hipLaunchKernelGGL((dec_proj_kernel<EPI_GEGLU, BB, true, 1>), grid, dim3(256), 0, S_, pb)); }
-  LAP_CHECK_LAUNCH();
-  return LAP_OK;
+  return launch_proj<EPI_GEGLU, true, 1>(p, f8, B, dim3(min(H / 4, 1024)), stream);
 }
 
 int proj_residual_impl(const int* state, const void* a, const void* w, const float* wscale, bool f8, const void* x, void* y, int B,
@@ -846,14 +760,14 @@ int proj_residual_impl(const int* state, const void* a, const void* w, const flo
   p.state = state; p.x = (const bf16*)a; p.w = (const bf16*)w; p.K = K; p.units = N / 2; p.N = N; p.res = (const bf16*)x;
   p.out = (bf16*)y;
   p.wscale = wscale;
-  const ProjP& pb = p;
   const int nu = 4 / kwaves;
   const dim3 grid(min((p.units + nu - 1) / nu, 2048));
-  if (f8) {
-    if (kwaves == 4) { DISPATCH_B(B, hipLaunchKernelGGL((dec_proj_kernel<EPI_RES, BB, false, 4, ProjP8>), grid, dim3(256), 0, S_, p)); }
-    else { DISPATCH_B(B, hipLaunchKernelGGL((dec_proj_kernel<EPI_RES, BB, false, 1, ProjP8>), grid, dim3(256), 0, S_, p)); }
-  } else if (kwaves == 4) { DISPATCH_B(B, hipLaunchKernelGGL((dec_proj_kernel<EPI_RES, BB, false, 4>), grid, dim3(256), 0, S_, pb)); }
-  else { DISPATCH_B(B, hipLaunchKernelGGL((dec_proj_kernel<EPI_RES, BB, false, 1>), grid, dim3(256), 0, S_, pb)); }
+  return kwaves == 4 ? launch_proj<EPI_RES, false, 4>(p, f8, B, grid, stream) : launch_proj<EPI_RES, false, 1>(p, f8, B, grid, stream);
+}
+
+template <bool SAMPLE, bool SUBSET, class P>
+int launch_lm_head(const P& p, int B, void* stream) {
+  DISPATCH_B(B, hipLaunchKernelGGL((dec_lm_head_kernel<BB, SAMPLE, SUBSET, P>), dim3(LM_BLOCKS), dim3(256), 0, S_, p));
   LAP_CHECK_LAUNCH();
   return LAP_OK;
 }
@@ -867,26 +781,18 @@ int lm_head_impl(const int* state, const int* sampling, bool sample, const void*
       (subset && (!ids || n < 1 || n > V))) return LAP_ERR_ARG;
   LmP8 p{};
   p.state = state; p.x = (const bf16*)x; p.gamma = gamma; p.eps = eps; p.hi = (const bf16*)hi; p.lo = f8 ? nullptr : (const bf16*)lo;
-  p.V = V; p.D = D; p.logits = logits; p.pval = pval; p.pidx = pidx; p.samp = sampling;
+  p.V = V; p.D = D; p.logits = logits; p.pval = pval; p.pidx = pidx; p.samp = sampling; p.ids = ids; p.n = n;
   p.wscale = wscale;
-  const LmP& pb = p;
-  if (subset) {
-    const dim3 g(LM_BLOCKS), t(256);
-    if (f8) {
-      if (sample) { DISPATCH_B(B, hipLaunchKernelGGL((dec_lm_head_subset_kernel<BB, true, LmP8>), g, t, 0, S_, p, ids, n)); }
-      else { DISPATCH_B(B, hipLaunchKernelGGL((dec_lm_head_subset_kernel<BB, false, LmP8>), g, t, 0, S_, p, ids, n)); }
-    } else if (sample) { DISPATCH_B(B, hipLaunchKernelGGL((dec_lm_head_subset_kernel<BB, true>), g, t, 0, S_, pb, ids, n)); }
-    else { DISPATCH_B(B, hipLaunchKernelGGL((dec_lm_head_subset_kernel<BB, false>), g, t, 0, S_, pb, ids, n)); }
-    LAP_CHECK_LAUNCH();
-    return LAP_OK;
+  switch ((sample ? 4 : 0) | (f8 ? 2 : 0) | (subset ? 1 : 0)) {
+    case 0: return launch_lm_head<false, false, LmP>(p, B, stream);
+    case 1: return launch_lm_head<false, true, LmP>(p, B, stream);
+    case 2: return launch_lm_head<false, false, LmP8>(p, B, stream);
+    case 3: return launch_lm_head<false, true, LmP8>(p, B, stream);
+    case 4: return launch_lm_head<true, false, LmP>(p, B, stream);
+    case 5: return launch_lm_head<true, true, LmP>(p, B, stream);
+    case 6: return launch_lm_head<true, false, LmP8>(p, B, stream);
+    default: return launch_lm_head<true, true, LmP8>(p, B, stream);
   }
-  if (f8) {
-    if (sample) { DISPATCH_B(B, hipLaunchKernelGGL((dec_lm_head_kernel<BB, true, LmP8>), dim3(LM_BLOCKS), dim3(256), 0, S_, p)); }
-    else { DISPATCH_B(B, hipLaunchKernelGGL((dec_lm_head_kernel<BB, false, LmP8>), dim3(LM_BLOCKS), dim3(256), 0, S_, p)); }
-  } else if (sample) { DISPATCH_B(B, hipLaunchKernelGGL((dec_lm_head_kernel<BB, true>), dim3(LM_BLOCKS), dim3(256), 0, S_, pb)); }
-  else { DISPATCH_B(B, hipLaunchKernelGGL((dec_lm_head_kernel<BB, false>), dim3(LM_BLOCKS), dim3(256), 0, S_, pb)); }
-  LAP_CHECK_LAUNCH();
-  return LAP_OK;
 }
 
 }  // namespace

@@ -1458,11 +1458,15 @@ def _ids_req(ids, V):
         raise ValueError(f"ids: expected 1 <= n <= V = {V} ids in one dimension, got shape {tuple(ids.shape)}")
 
 
-def decode_lm_head(state, x, gamma, hi, lo, pval, pidx, logits=None, eps=1e-6, wscale=None, ids=None):
-    """logits (debug): f32 [B, V] written when given.  wscale given: `hi` is the one e4m3 code plane of the table, lo is None.
-    ids given: the head over that allowed set only (lap_decode_lm_head_subset*): partials over the rows ids[.], logits written
-    at those indices alone."""
+def _decode_lm_head(fn, sampling, state, x, gamma, hi, lo, pval, pidx, logits, eps, wscale, ids):
+    """The body of `decode_lm_head` (sampling None) and `decode_lm_head_sample`; `fn` names the caller in error messages."""
     _dreq(x, torch.bfloat16, "x"); _dreq(gamma, torch.float32, "gamma")
+    smp, lead = "", (_p(state),)
+    if sampling is not None:
+        _dreq(sampling, torch.int32, "sampling")
+        if sampling.numel() < _fn["lap_decode_sampling_words"]():
+            raise TypeError("sampling: int32 [lap_decode_sampling_words()]")
+        smp, lead = "_sample", (_p(state), _p(sampling))
     if logits is not None:
         _dreq(logits, torch.float32, "logits")
     B, D = x.shape
@@ -1473,15 +1477,22 @@ def decode_lm_head(state, x, gamma, hi, lo, pval, pidx, logits=None, eps=1e-6, w
     if wscale is not None:
         _f8req(hi, wscale, "hi")
         if lo is not None:
-            raise TypeError("decode_lm_head: the fp8 table is one plane (lo must be None)")
-        call(f"lap_decode_lm_head{sub}_fp8", _p(state), _p(x), _p(gamma), _p(hi), _p(wscale), *tail, B, D, hi.shape[0], float(eps),
-             _p(logits), _p(pval), _p(pidx))
-        return
-    _dreq(hi, torch.bfloat16, "hi")
-    if lo is not None:
-        _dreq(lo, torch.bfloat16, "lo")
-    call(f"lap_decode_lm_head{sub}", _p(state), _p(x), _p(gamma), _p(hi), _p(lo), *tail, B, D, hi.shape[0], float(eps), _p(logits),
+            raise TypeError(f"{fn}: the fp8 table is one plane (lo must be None)")
+        planes, f8 = (_p(hi), _p(wscale)), "_fp8"
+    else:
+        _dreq(hi, torch.bfloat16, "hi")
+        if lo is not None:
+            _dreq(lo, torch.bfloat16, "lo")
+        planes, f8 = (_p(hi), _p(lo)), ""
+    call(f"lap_decode_lm_head{sub}{smp}{f8}", *lead, _p(x), _p(gamma), *planes, *tail, B, D, hi.shape[0], float(eps), _p(logits),
          _p(pval), _p(pidx))
+
+
+def decode_lm_head(state, x, gamma, hi, lo, pval, pidx, logits=None, eps=1e-6, wscale=None, ids=None):
+    """logits (debug): f32 [B, V] written when given.  wscale given: `hi` is the one e4m3 code plane of the table, lo is None.
+    ids given: the head over that allowed set only (lap_decode_lm_head_subset*): partials over the rows ids[.], logits written
+    at those indices alone."""
+    _decode_lm_head("decode_lm_head", None, state, x, gamma, hi, lo, pval, pidx, logits, eps, wscale, ids)
 
 
 def decode_sampling(device):
@@ -1503,29 +1514,7 @@ def decode_set_sampling(buf, seed, temperature):
 def decode_lm_head_sample(state, sampling, x, gamma, hi, lo, pval, pidx, logits=None, eps=1e-6, wscale=None, ids=None):
     """`decode_lm_head` with the sampler of `sampling` (see `decode_sampling`) as its epilogue; logits (debug) stay raw.  ids: the
     allowed set, as in `decode_lm_head`; the noise of a row stays that of its vocabulary index."""
-    _dreq(x, torch.bfloat16, "x"); _dreq(gamma, torch.float32, "gamma")
-    _dreq(sampling, torch.int32, "sampling")
-    if sampling.numel() < _fn["lap_decode_sampling_words"]():
-        raise TypeError("sampling: int32 [lap_decode_sampling_words()]")
-    if logits is not None:
-        _dreq(logits, torch.float32, "logits")
-    B, D = x.shape
-    sub, tail = "", ()
-    if ids is not None:
-        _ids_req(ids, hi.shape[0])
-        sub, tail = "_subset", (_p(ids), ids.numel())
-    if wscale is not None:
-        _f8req(hi, wscale, "hi")
-        if lo is not None:
-            raise TypeError("decode_lm_head_sample: the fp8 table is one plane (lo must be None)")
-        call(f"lap_decode_lm_head{sub}_sample_fp8", _p(state), _p(sampling), _p(x), _p(gamma), _p(hi), _p(wscale), *tail, B, D,
-             hi.shape[0], float(eps), _p(logits), _p(pval), _p(pidx))
-        return
-    _dreq(hi, torch.bfloat16, "hi")
-    if lo is not None:
-        _dreq(lo, torch.bfloat16, "lo")
-    call(f"lap_decode_lm_head{sub}_sample", _p(state), _p(sampling), _p(x), _p(gamma), _p(hi), _p(lo), *tail, B, D, hi.shape[0],
-         float(eps), _p(logits), _p(pval), _p(pidx))
+    _decode_lm_head("decode_lm_head_sample", sampling, state, x, gamma, hi, lo, pval, pidx, logits, eps, wscale, ids)
 
 
 def decode_finish(state, pval, pidx, out, eos_token):
