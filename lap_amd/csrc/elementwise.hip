@@ -52,12 +52,16 @@ inline dim3 flat_grid(long long n, int per_block = 256) { return dim3((unsigned)
 // key head of the row (they only depend on the position and the frequency index), then the value head is copied.
 // HSPLIT (few rows: serving prefill, 560 rows = 35 blocks walking ten heads one after the other, latency bound): one thread per
 // (row, head, chunk) instead — the same arithmetic, sin / cos evaluated per head.
-template <bool BWD, bool HSPLIT = false>
+// QIDX (the last layer of a train step, whose prefix queries are the loss rows only): q / dq are COMPACT, qrow[row] is the
+// compact row of `row` or -1.  FWD writes no q for a row without one (k and v are written for every row, the angle is the
+// row's own position); BWD writes zeros into its q columns of dqkv, so the full-height dqkv needs no fill pass in front.
+template <bool BWD, bool HSPLIT = false, bool QIDX = false>
 __global__ __launch_bounds__(256) void rope_split_kernel(const bf16* __restrict__ a0, const bf16* __restrict__ a1,
                                                          const bf16* __restrict__ a2, const int32_t* __restrict__ pos,
                                                          bf16* __restrict__ o0, bf16* __restrict__ o1,
                                                          bf16* __restrict__ o2, int rows, int T_seg, int T_total,
-                                                         int seg_off, int NH, int HD, float q_scale) {
+                                                         int seg_off, int NH, int HD, float q_scale,
+                                                         const int32_t* __restrict__ qrow) {
   // FWD: a0 = qkv, outputs o0 = q, o1 = k, o2 = v.   BWD: a0 = dq, a1 = dk, a2 = dv, output o0 = dqkv.
   const int cph = HD / 16;               // 8-wide frequency chunks per head = threads per row
   long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -75,14 +79,24 @@ __global__ __launch_bounds__(256) void rope_split_kernel(const bf16* __restrict_
   const int W = (NH + 2) * HD;
   const int half = HD / 2;
   const float p = (float)pos[(long long)b * T_total + seg_off + t];
+  long long qr = row;   // row of q / dq
+  if constexpr (QIDX) qr = qrow[row];
   float sn[8], cs[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) rope_sincos(p, c * 8 + e, HD, sn[e], cs[e]);
 #pragma unroll 2
   for (int h = h_lo; h < h_hi; ++h) {
+    if (QIDX && h < NH && qr < 0) {
+      if (BWD) {
+        const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        st8(o0 + (long long)row * W + h * HD + c * 8, z);
+        st8(o0 + (long long)row * W + h * HD + half + c * 8, z);
+      }
+      continue;
+    }
     const bf16* src;
     if (!BWD) src = a0 + (long long)row * W + h * HD;
-    else if (h < NH) src = a0 + (long long)row * NH * HD + h * HD;
+    else if (h < NH) src = a0 + qr * NH * HD + h * HD;
     else if (h == NH) src = a1 + (long long)row * HD;
     else src = a2 + (long long)row * HD;
     float x1[8], x2[8], y1[8], y2[8];
@@ -109,7 +123,7 @@ __global__ __launch_bounds__(256) void rope_split_kernel(const bf16* __restrict_
     }
     bf16* dst;
     if (BWD) dst = o0 + (long long)row * W + h * HD;
-    else if (h < NH) dst = o0 + (long long)row * NH * HD + h * HD;
+    else if (h < NH) dst = o0 + qr * NH * HD + h * HD;
     else if (h == NH) dst = o1 + (long long)row * HD;
     else dst = o2 + (long long)row * HD;
     st8(dst + c * 8, y1);
@@ -356,14 +370,15 @@ __global__ __launch_bounds__(256) void copy2d_kernel(const bf16* __restrict__ sr
   const int r = (int)(gid / cols8), c = (int)(gid % cols8) * 8;
   *reinterpret_cast<bf16x8*>(dst + (long long)r * ldd + c) = *reinterpret_cast<const bf16x8*>(src + (long long)r * lds_ + c);
 }
+// (src_idx, optional: the source row of r is src_idx[r] — a gather — instead of the re-blocking rule)
 __global__ __launch_bounds__(256) void copy_rows_kernel(const bf16* __restrict__ src, bf16* __restrict__ dst, int rows,
                                                         int T, int D8, int src_rps, int src_off, int dst_rps,
-                                                        int dst_off, int accumulate) {
+                                                        int dst_off, int accumulate, const int32_t* __restrict__ src_idx) {
   const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
   if (gid >= (long long)rows * D8) return;
   const int r = (int)(gid / D8), c = (int)(gid % D8) * 8;
   const long long D = (long long)D8 * 8;
-  const long long srow = (long long)(r / T) * src_rps + src_off + r % T;
+  const long long srow = src_idx ? (long long)src_idx[r] : (long long)(r / T) * src_rps + src_off + r % T;
   const long long drow = (long long)(r / T) * dst_rps + dst_off + r % T;
   if (accumulate) {
     float a[8], b[8];
@@ -624,10 +639,23 @@ extern "C" int lap_rope_split_fwd(const void* qkv, const int32_t* pos, void* q, 
   const long long n = (long long)B * T_seg * (HD / 16);
   if (n < 65536)   // fewer than 256 blocks: one thread per head as well
     hipLaunchKernelGGL((rope_split_kernel<false, true>), flat_grid(n * (NH + 2)), dim3(256), 0, S_, (const bf16*)qkv, nullptr, nullptr, pos,
-                       (bf16*)q, (bf16*)k, (bf16*)v, B * T_seg, T_seg, T_total, seg_off, NH, HD, q_scale);
+                       (bf16*)q, (bf16*)k, (bf16*)v, B * T_seg, T_seg, T_total, seg_off, NH, HD, q_scale, nullptr);
   else
     hipLaunchKernelGGL(rope_split_kernel<false>, flat_grid(n), dim3(256), 0, S_, (const bf16*)qkv, nullptr, nullptr, pos,
-                       (bf16*)q, (bf16*)k, (bf16*)v, B * T_seg, T_seg, T_total, seg_off, NH, HD, q_scale);
+                       (bf16*)q, (bf16*)k, (bf16*)v, B * T_seg, T_seg, T_total, seg_off, NH, HD, q_scale, nullptr);
+  LAP_CHECK_LAUNCH();
+  return LAP_OK;
+}
+extern "C" int lap_rope_split_fwd_rows(const void* qkv, const int32_t* pos, const int32_t* qrow, void* q, void* k, void* v, int B,
+                                       int T_seg, int T_total, int seg_off, int NH, int HD, float q_scale, void* stream) {
+  if (B <= 0 || T_seg <= 0 || (HD & 15) || NH <= 0 || !qrow) return LAP_ERR_ARG;
+  const long long n = (long long)B * T_seg * (HD / 16);
+  if (n < 65536)
+    hipLaunchKernelGGL((rope_split_kernel<false, true, true>), flat_grid(n * (NH + 2)), dim3(256), 0, S_, (const bf16*)qkv, nullptr, nullptr,
+                       pos, (bf16*)q, (bf16*)k, (bf16*)v, B * T_seg, T_seg, T_total, seg_off, NH, HD, q_scale, qrow);
+  else
+    hipLaunchKernelGGL((rope_split_kernel<false, false, true>), flat_grid(n), dim3(256), 0, S_, (const bf16*)qkv, nullptr, nullptr, pos,
+                       (bf16*)q, (bf16*)k, (bf16*)v, B * T_seg, T_seg, T_total, seg_off, NH, HD, q_scale, qrow);
   LAP_CHECK_LAUNCH();
   return LAP_OK;
 }
@@ -637,7 +665,18 @@ extern "C" int lap_rope_split_bwd(const void* dq, const void* dk, const void* dv
   const long long n = (long long)B * T_seg * (HD / 16);
   hipLaunchKernelGGL(rope_split_kernel<true>, flat_grid(n), dim3(256), 0, S_, (const bf16*)dq, (const bf16*)dk,
                      (const bf16*)dv, pos, (bf16*)dqkv, nullptr, nullptr, B * T_seg, T_seg, T_total, seg_off, NH, HD,
-                     q_scale);
+                     q_scale, nullptr);
+  LAP_CHECK_LAUNCH();
+  return LAP_OK;
+}
+extern "C" int lap_rope_split_bwd_rows(const void* dq, const void* dk, const void* dv, const int32_t* pos, const int32_t* qrow,
+                                       void* dqkv, int B, int T_seg, int T_total, int seg_off, int NH, int HD, float q_scale,
+                                       void* stream) {
+  if (B <= 0 || T_seg <= 0 || (HD & 15) || NH <= 0 || !qrow) return LAP_ERR_ARG;
+  const long long n = (long long)B * T_seg * (HD / 16);
+  hipLaunchKernelGGL((rope_split_kernel<true, false, true>), flat_grid(n), dim3(256), 0, S_, (const bf16*)dq, (const bf16*)dk,
+                     (const bf16*)dv, pos, (bf16*)dqkv, nullptr, nullptr, B * T_seg, T_seg, T_total, seg_off, NH, HD,
+                     q_scale, qrow);
   LAP_CHECK_LAUNCH();
   return LAP_OK;
 }
@@ -771,7 +810,14 @@ extern "C" int lap_copy_rows_bf16(const void* src, void* dst, int rows, int T, i
                                   int dst_rps, int dst_off, int accumulate, void* stream) {
   if (rows <= 0 || T <= 0 || (D & 7)) return LAP_ERR_ARG;
   hipLaunchKernelGGL(copy_rows_kernel, flat_grid((long long)rows * (D / 8)), dim3(256), 0, S_, (const bf16*)src,
-                     (bf16*)dst, rows, T, D / 8, src_rps, src_off, dst_rps, dst_off, accumulate);
+                     (bf16*)dst, rows, T, D / 8, src_rps, src_off, dst_rps, dst_off, accumulate, nullptr);
+  LAP_CHECK_LAUNCH();
+  return LAP_OK;
+}
+extern "C" int lap_gather_rows_bf16(const void* src, const int32_t* idx, void* dst, int rows, int D, void* stream) {
+  if (rows <= 0 || D <= 0 || (D & 7) || !idx) return LAP_ERR_ARG;
+  hipLaunchKernelGGL(copy_rows_kernel, flat_grid((long long)rows * (D / 8)), dim3(256), 0, S_, (const bf16*)src,
+                     (bf16*)dst, rows, rows, D / 8, 0, 0, rows, 0, 0, idx);
   LAP_CHECK_LAUNCH();
   return LAP_OK;
 }

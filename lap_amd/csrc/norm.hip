@@ -73,13 +73,16 @@ __global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(const bf16* __restrict
 
 // ------------------------------------------------------------------ RMSNorm bwd
 // Group g covers rows [g*G, (g+1)*G).  Adaptive: G == rows_per_sample.
-template <int NCH>
+// IDX: what a row's dx is added onto is not dx itself but row add_row[row] of the compact `addend` (none where that is < 0) —
+// the residual branch of a layer that kept only some of its rows, scattered back in the pass that writes dx anyway.
+template <int NCH, bool IDX = false>
 __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16* __restrict__ x, const float* __restrict__ scale,
                                                           const bf16* __restrict__ mod, const float* __restrict__ rstd,
                                                           const bf16* __restrict__ dy, bf16* __restrict__ dx,
                                                           float* __restrict__ dscale, float* __restrict__ dmod,
                                                           int rows, int D, int G, int mod_ld, int dmod_ld,
-                                                          int accum_dx) {
+                                                          int accum_dx, const int32_t* __restrict__ add_row,
+                                                          const bf16* __restrict__ addend) {
   extern __shared__ __attribute__((aligned(16))) float red[];  // [NWAVE][2*D] (adaptive) / [NWAVE][D]
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int g = blockIdx.x;
@@ -125,11 +128,18 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16* __restrict
   if (r0 + w < r1) fetch(r0 + w);
   for (int row = r0 + w; row < r1; row += NWAVE) {
     bf16x8 cx[NCH], cdy[NCH], cold[NCH];
+    const bf16* oldr = dx + (long long)row * D;     // the row added onto, if any
+    bool has_old = accum_dx;
+    if constexpr (IDX) {
+      const int j = add_row[row];
+      has_old = j >= 0;
+      oldr = addend + (long long)(j >= 0 ? j : 0) * D;
+    }
 #pragma unroll
     for (int p = 0; p < NCH; ++p) {
       cx[p] = nx[p]; cdy[p] = ndy[p];
       const int c = (lane + 64 * p) * 8;
-      if (NCH <= 3 && accum_dx && c < D) cold[p] = *reinterpret_cast<const bf16x8*>(dx + (long long)row * D + c);     // requested HERE: in flight under the row's arithmetic and reduction
+      if (NCH <= 3 && has_old && c < D) cold[p] = *reinterpret_cast<const bf16x8*>(oldr + c);     // requested HERE: in flight under the row's arithmetic and reduction
       // (NCH = 4, D = 2048: 16 more live registers cost the kernel its second wave per SIMD — it keeps the late request below)
     }
     const float r = nr;
@@ -162,8 +172,8 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16* __restrict
         float o[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) o[e] = r * gv[p][e] - xv[p][e] * cc;
-        if (accum_dx) {
-          if constexpr (NCH > 3) cold[p] = *reinterpret_cast<const bf16x8*>(dxr + c);
+        if (has_old) {
+          if constexpr (NCH > 3) cold[p] = *reinterpret_cast<const bf16x8*>(oldr + c);
 #pragma unroll
           for (int e = 0; e < 8; ++e) o[e] += (float)cold[p][e];
         }
@@ -391,7 +401,23 @@ extern "C" int lap_rmsnorm_bwd(const void* x, const float* scale, const void* mo
   const size_t shm = (size_t)NWAVE * (mod ? 2 : 1) * D * sizeof(float);
   DISPATCH_NCH(D, hipLaunchKernelGGL(rmsnorm_bwd_kernel<NCH>, grid, dim3(256), shm, s, (const bf16*)x, scale,
                                      (const bf16*)mod, rstd, (const bf16*)dy, (bf16*)dx, dscale, dmod, rows, D, G,
-                                     mod_ld, dmod_ld, accum_dx));
+                                     mod_ld, dmod_ld, accum_dx, nullptr, nullptr));
+  LAP_CHECK_LAUNCH();
+  return LAP_OK;
+}
+
+extern "C" int lap_rmsnorm_bwd_rows(const void* x, const float* scale, const float* rstd, const void* dy, void* dx,
+                                    float* dscale, const int32_t* add_row, const void* addend, int rows, int D,
+                                    void* stream) {
+  if (rows <= 0 || D <= 0 || (D & 7) || !rstd || !scale || !dscale || !add_row || !addend || dx == addend) return LAP_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  static const int g_env = getenv("LAP_NORM_BWD_ROWS") ? atoi(getenv("LAP_NORM_BWD_ROWS")) : 64;   // (as lap_rmsnorm_bwd)
+  const int G = g_env;
+  dim3 grid((rows + G - 1) / G);
+  const size_t shm = (size_t)NWAVE * D * sizeof(float);
+  DISPATCH_NCH(D, hipLaunchKernelGGL((rmsnorm_bwd_kernel<NCH, true>), grid, dim3(256), shm, s, (const bf16*)x, scale,
+                                     (const bf16*)nullptr, rstd, (const bf16*)dy, (bf16*)dx, dscale, (float*)nullptr, rows,
+                                     D, G, 0, 0, 0, add_row, (const bf16*)addend));
   LAP_CHECK_LAUNCH();
   return LAP_OK;
 }

@@ -136,11 +136,14 @@ SIGNATURES: dict[str, list] = {
     "lap_gemm_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _vp],
     "lap_rmsnorm_fwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp],
     "lap_rmsnorm_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
+    "lap_rmsnorm_bwd_rows": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
     "lap_layernorm_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp],
     "lap_layernorm_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "lap_layernorm_bwd_sum": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "lap_rope_split_fwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp],
     "lap_rope_split_bwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp],
+    "lap_rope_split_fwd_rows": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp],
+    "lap_rope_split_bwd_rows": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp],
     "lap_geglu_fwd": [_vp, _vp, _i, _i, _vp],
     "lap_geglu_bwd": [_vp, _vp, _vp, _i, _i, _vp],
     "lap_geglu_fwd_ld": [_vp, _vp, _i, _i, _i, _i, _vp],
@@ -159,6 +162,7 @@ SIGNATURES: dict[str, list] = {
     "lap_add_bf16": [_vp, _vp, _vp, _ll, _vp],
     "lap_copy2d_bf16": [_vp, _vp, _i, _i, _i, _i, _vp],
     "lap_copy_rows_bf16": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "lap_gather_rows_bf16": [_vp, _vp, _vp, _i, _i, _vp],
     "lap_im2col_patch": [_vp, _vp, _i, _i, _i, _i, _i, _vp],
     "lap_augment_images": [_vp, _vp, _vp, _i, _i, _i, _vp],
     "lap_add_posemb_cast": [_vp, _vp, _vp, _i, _i, _i, _vp],
@@ -451,10 +455,28 @@ def rmsnorm_fwd(x, scale=None, mod=None, rows_per_sample=0, eps=1e-6, save_rstd=
     return y, rstd
 
 
-def rmsnorm_bwd(x, dy, rstd, scale=None, mod=None, rows_per_sample=0, dx=None, dscale=None, dmod=None, accum_dx=False):
+def _row_map(t, n, name):
+    """`t`: int32 [n] on the device, every entry -1 or a row of a compact tensor (the caller keeps them in range: no host sync here)."""
+    _req(t, torch.int32, name)
+    if t.dim() != 1 or t.numel() != n or not t.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous int32 [{n}] tensor, got shape {tuple(t.shape)}")
+
+
+def rmsnorm_bwd(x, dy, rstd, scale=None, mod=None, rows_per_sample=0, dx=None, dscale=None, dmod=None, accum_dx=False, add_row=None,
+                addend=None):
+    """add_row / addend (plain form only): dx[r] = norm-backward(dy)[r] + addend[add_row[r]] where add_row[r] >= 0, one pass."""
     rows, D = x.shape
     if dx is None:
         dx = torch.empty_like(x)
+    if add_row is not None:
+        if mod is not None or accum_dx or addend is None or scale is None or dscale is None:
+            raise ValueError("rmsnorm_bwd: add_row goes with scale / dscale and an addend, not with mod or accum_dx")
+        _row_map(add_row, rows, "add_row")
+        _req(addend, torch.bfloat16, "addend")
+        if addend.dim() != 2 or addend.shape[1] != D or not addend.is_contiguous() or not dx.is_contiguous() or dx.shape != x.shape:
+            raise ValueError(f"rmsnorm_bwd: addend {tuple(addend.shape)} / dx {tuple(dx.shape)} do not fit x {tuple(x.shape)}")
+        call("lap_rmsnorm_bwd_rows", _p(x), _p(scale), _p(rstd), _p(dy), _p(dx), _p(dscale), _p(add_row), _p(addend), rows, D)
+        return dx
     call("lap_rmsnorm_bwd", _p(x), _p(scale), _p(mod), _p(rstd), _p(dy), _p(dx), _p(dscale), _p(dmod), rows, D,
          rows_per_sample, mod.stride(0) if mod is not None else 0, dmod.stride(0) if dmod is not None else 0,
          int(accum_dx))
@@ -481,19 +503,32 @@ def layernorm_bwd(x, dy, gamma, mean, rstd, dgamma, dbeta, dx=None, accum_dx=Fal
 
 
 # --------------------------------------------------------------------- elementwise
-def rope_split_fwd(qkv, pos, B, T_seg, T_total, seg_off, NH, HD, q_scale):
+def rope_split_fwd(qkv, pos, B, T_seg, T_total, seg_off, NH, HD, q_scale, q_row=None, q_rows=0):
+    """q_row (int32 [B * T_seg]: the row of q that row r gets, or -1) with q_rows = the height of q: q comes out compact, k / v whole."""
     rows = B * T_seg
-    q = torch.empty((rows, NH * HD), dtype=torch.bfloat16, device=qkv.device)
+    q = torch.empty((rows if q_row is None else q_rows, NH * HD), dtype=torch.bfloat16, device=qkv.device)
     k = torch.empty((rows, HD), dtype=torch.bfloat16, device=qkv.device)
     v = torch.empty((rows, HD), dtype=torch.bfloat16, device=qkv.device)
-    call("lap_rope_split_fwd", _p(qkv), _p(pos), _p(q), _p(k), _p(v), B, T_seg, T_total, seg_off, NH, HD, float(q_scale))
+    if q_row is not None:
+        _row_map(q_row, rows, "q_row")
+        if q_rows <= 0:
+            raise ValueError("rope_split_fwd: q_row needs q_rows, the height of the compact q")
+        call("lap_rope_split_fwd_rows", _p(qkv), _p(pos), _p(q_row), _p(q), _p(k), _p(v), B, T_seg, T_total, seg_off, NH, HD, float(q_scale))
+    else:
+        call("lap_rope_split_fwd", _p(qkv), _p(pos), _p(q), _p(k), _p(v), B, T_seg, T_total, seg_off, NH, HD, float(q_scale))
     return q, k, v
 
 
-def rope_split_bwd(dq, dk, dv, pos, B, T_seg, T_total, seg_off, NH, HD, q_scale):
+def rope_split_bwd(dq, dk, dv, pos, B, T_seg, T_total, seg_off, NH, HD, q_scale, q_row=None):
+    """q_row as in rope_split_fwd: dq is compact, dqkv has all B * T_seg rows, zeros in the q columns of the rows without a dq row."""
     dqkv = torch.empty((B * T_seg, (NH + 2) * HD), dtype=torch.bfloat16, device=dq.device)
-    call("lap_rope_split_bwd", _p(dq), _p(dk), _p(dv), _p(pos), _p(dqkv), B, T_seg, T_total, seg_off, NH, HD,
-         float(q_scale))
+    if q_row is not None:
+        _row_map(q_row, B * T_seg, "q_row")
+        call("lap_rope_split_bwd_rows", _p(dq), _p(dk), _p(dv), _p(pos), _p(q_row), _p(dqkv), B, T_seg, T_total, seg_off, NH, HD,
+             float(q_scale))
+    else:
+        call("lap_rope_split_bwd", _p(dq), _p(dk), _p(dv), _p(pos), _p(dqkv), B, T_seg, T_total, seg_off, NH, HD,
+             float(q_scale))
     return dqkv
 
 
@@ -668,6 +703,18 @@ def copy2d_bf16(src, dst, rows, cols, lds, ldd):
 
 def copy_rows_bf16(src, dst, rows, T, D, src_rps, src_off, dst_rps, dst_off, accumulate=False):
     call("lap_copy_rows_bf16", _p(src), _p(dst), rows, T, D, src_rps, src_off, dst_rps, dst_off, int(accumulate))
+
+
+def gather_rows_bf16(src, idx):
+    """out[r] = src[idx[r]]: bf16 [n, D] from bf16 [rows, D] and int32 [n] (in range: the caller's duty), lap_copy_rows_bf16's kernel."""
+    _req(src, torch.bfloat16, "src")
+    n = idx.numel()
+    _row_map(idx, n, "idx")
+    if src.dim() != 2 or not src.is_contiguous():
+        raise ValueError(f"gather_rows_bf16: src must be a contiguous [rows, D] tensor, got {tuple(src.shape)}")
+    out = torch.empty((n, src.shape[1]), dtype=torch.bfloat16, device=src.device)
+    call("lap_gather_rows_bf16", _p(src), _p(idx), _p(out), n, src.shape[1])
+    return out
 
 
 def im2col_patch(img, P):

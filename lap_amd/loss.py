@@ -51,12 +51,22 @@ class LangHead(NamedTuple):
     logit_chunks: list = None           # f32 logits per chunk (kept for the backward)
     Lt: int = 0
     verbose_metrics: dict = {}
+    compact: bool = False               # `rows` IS the prefix stream's output (the last layer ran on the selected rows only)
 
 
-def lang_head_fwd(model, xf0, obs, observation, B, Pn, *, backward: bool, verbose: bool, collect) -> LangHead:
+class LossRows(NamedTuple):
+    """Which rows the language head reads (`select_loss_rows`): chosen once per step, before the joint layers, so that the last
+    layer's prefix stream can run on these rows alone (LAP._llm_fwd `last_rows`)."""
+    lm: torch.Tensor                    # [B, Lt-1] loss mask, f32
+    cnt: torch.Tensor                   # [B] max(sum(lm), 1)
+    sel: torch.Tensor = None            # [B, Ls] selected rows in 0 .. Lt-2 (masked rows first, stable order, padded), or None: all
+    hint_too_small: torch.Tensor = None  # 0-d bool (with `sel`)
+    cls_masks: list = None              # verbose: the class masks on rows 0 .. Lt-2
+
+
+def select_loss_rows(model, obs, observation, *, verbose: bool) -> LossRows:
     """`obs`: the preprocessed observation; `observation`: the caller's (its row hints win over the derived ones)."""
     dev = model.device
-    Dv, V = model.v.width, model.config.vocab_size
     Lt = obs.tokenized_prompt.shape[1]
     loss_mask = obs.tokenized_langact_mask[:, 1:] & obs.tokenized_prompt_mask[:, 1:]
     if obs.token_loss_mask is not None:
@@ -85,16 +95,30 @@ def lang_head_fwd(model, xf0, obs, observation, B, Pn, *, backward: bool, verbos
             if mk is not None:
                 row_mask = row_mask | mk
         n_sel = observation.metric_rows_max if observation.metric_rows_max is not None else obs.metric_rows_max
-    sel = rowid = None
+    sel = hint_too_small = None
     if n_sel is not None and 0 < n_sel < Lt - 1:
         sel = torch.sort((~row_mask).to(torch.uint8), dim=1, stable=True).indices[:, :n_sel]          # [B, n_sel] in 0 .. Lt-2
         hint_too_small = ((row_mask.sum(-1) if verbose else lm.sum(-1)) > n_sel).any()
-        Ls = n_sel
+    return LossRows(lm, cnt, sel, hint_too_small, cls_masks if verbose else None)
+
+
+def lang_head_fwd(model, xf0, obs, lr: LossRows, B, Pn, *, backward: bool, verbose: bool, collect, compact: bool = False) -> LangHead:
+    """`lr`: select_loss_rows' choice.  `compact`: xf0 holds exactly the selected rows, [B * Ls, Dv] in `lr.sel`'s order (the last
+    layer's row-subset path); else xf0 is the whole prefix stream [B * Pn, Dv] and the rows are gathered from it."""
+    dev = model.device
+    Dv, V = model.v.width, model.config.vocab_size
+    Lt = obs.tokenized_prompt.shape[1]
+    lm, cnt, sel, hint_too_small, cls_masks = lr
+    rowid = None
+    if sel is not None:
+        Ls = sel.shape[1]
         rowid = (torch.arange(B, device=dev) * Pn + (Pn - Lt))[:, None] + sel
-        rows = xf0.index_select(0, rowid.view(-1))
+        rows = xf0 if compact else xf0.index_select(0, rowid.view(-1))
         targets = obs.tokenized_prompt[:, 1:].gather(1, sel).to(torch.int32).contiguous().view(-1)
         lm_s = lm.gather(1, sel)
     else:
+        if compact:
+            raise ValueError("lang_head_fwd: compact rows need a row selection")
         Ls = Lt - 1
         rows = torch.empty((B * Ls, Dv), dtype=torch.bfloat16, device=dev)
         hip.copy_rows_bf16(xf0, rows, B * Ls, Ls, Dv, Pn, Pn - Lt, Ls, 0)
@@ -123,7 +147,8 @@ def lang_head_fwd(model, xf0, obs, observation, B, Pn, *, backward: bool, verbos
         verbose_metrics = _token_metrics(model, amax, targets, nll, lm, sel, cls_masks, obs.tokenized_prompt[:, 1:])
         if collect is not None:
             collect["predictions"], collect["sel"] = amax.view(B, Ls), sel
-    return LangHead(lang_loss, lm, lm_s, cnt, sel, rowid, rows, pl, rstd_pl, targets, m, lsum, chunks, logit_chunks, Lt, verbose_metrics)
+    return LangHead(lang_loss, lm, lm_s, cnt, sel, rowid, rows, pl, rstd_pl, targets, m, lsum, chunks, logit_chunks, Lt, verbose_metrics,
+                    compact)
 
 
 def _token_metrics(model, amax, targets, nll, lm, sel, cls_masks, labels):
@@ -151,7 +176,8 @@ def lang_head_bwd(model, head: LangHead, wl, n_active, B, Pn):
     table = hi + lo -> dh.hi + dl.hi + dh.lo (dl.lo is 2^-16 of the sum) and (dh + dl)^T . pre_logits.
     The planes are stacked along the rows, [dh; dl]: ONE weight-gradient product over 2R rows against [pl; pl] (the f32 [V, D]
     output is written once instead of accumulated onto), ONE data-gradient product [dh; dl] . hi (the table plane is read
-    once), plus dh . lo onto its first half.  Returns dx0 [B*Pn, Dv]: zeros but for the head's rows."""
+    once), plus dh . lo onto its first half.  Returns dx0 [B*Pn, Dv]: zeros but for the head's rows — or, for a `compact` head, the
+    cotangent of its rows alone [B*Ls, Dv]."""
     dev = model.device
     R, Dv = head.pl.shape
     w = (wl[:, None] * head.lm_s / head.cnt[:, None] / n_active).contiguous().view(-1)
@@ -169,6 +195,8 @@ def lang_head_bwd(model, head: LangHead, wl, n_active, B, Pn):
         del dlogits
     dpl = hip.cast_f32_to_bf16(dpl32[:R] + dpl32[R:])
     drows = hip.rmsnorm_bwd(head.rows, dpl, head.rstd_pl, scale=model.F("llm/final_norm"), dscale=model.G("llm/final_norm"))
+    if head.compact:
+        return drows
     dx0 = torch.zeros((B * Pn, Dv), dtype=torch.bfloat16, device=dev)
     if head.sel is not None:
         dx0.index_copy_(0, head.rowid.view(-1), drows)

@@ -31,7 +31,8 @@ import torch
 
 from lap_amd import hip
 from lap_amd.config import LAPConfig, get_gemma_config, get_siglip_config
-from lap_amd.loss import ActionHead, LangHead, action_head_bwd, action_head_fwd, lang_head_bwd, lang_head_fwd, mix_sample_weights
+from lap_amd.loss import (ActionHead, LangHead, action_head_bwd, action_head_fwd, lang_head_bwd, lang_head_fwd, mix_sample_weights,
+                          select_loss_rows)
 from lap_amd.observation import CoTObservation, preprocess_observation
 from lap_amd.params import LORA_PROJ, ParamStore, lora_geometry
 from lap_amd.serve_cache import ServeCache
@@ -56,6 +57,21 @@ def _gen(rng, device):
     g = torch.Generator(device=device)
     g.manual_seed(int(rng) if rng is not None else 0)
     return g
+
+
+class LastRows:
+    """The prefix rows the LAST joint layer keeps in a train step (`LAP._last_layer_rows`): those the language head reads."""
+
+    def __init__(self, sel, qinfo, B, n0, Lt):
+        dev, n_sel = sel.device, sel.shape[1]
+        self.n_sel = n_sel
+        idx = sel + (n0 - Lt)                                                       # [B, n_sel] prefix positions, the head's order
+        self.rowid = (torch.arange(B, device=dev)[:, None] * n0 + idx).to(torch.int32).reshape(-1).contiguous()   # rows of x0
+        self.inv = torch.full((B * n0,), -1, dtype=torch.int32, device=dev)         # row of x0 -> its compact row, or -1
+        self.inv[self.rowid.long()] = torch.arange(B * n_sel, dtype=torch.int32, device=dev)
+        # info words of the kept queries, then the suffix queries': class bits and ar index travel with the row, so every kept
+        # row meets the keys under the mask it had
+        self.qinfo = torch.cat([qinfo[:, :n0].gather(1, idx), qinfo[:, n0:]], 1).to(torch.int32).contiguous()
 
 
 class LAP:
@@ -90,6 +106,10 @@ class LAP:
         self.fuse_geglu_bwd = os.environ.get("LAP_FUSE_GEGLU_BWD", "1") != "0" and gemm_dtype != "fp8"
         self.fuse_geglu_fwd = os.environ.get("LAP_FUSE_GEGLU_FWD", "1") != "0" and gemm_dtype != "fp8"
         self.fuse_gelu = os.environ.get("LAP_FUSE_GELU", "1") != "0"      # SigLIP MLP: GELU forward / backward inside the Dense GEMMs
+        # train step: the last joint layer's prefix stream keeps K / V of every row but runs everything behind them on the rows the
+        # language head reads (`_last_layer_rows`).  LAP_LAST_LAYER_ROWS=0: all rows, as every other layer (A/B runs, tests)
+        self.last_layer_rows = os.environ.get("LAP_LAST_LAYER_ROWS", "1") != "0"
+        self.last_rows_steps = 0      # passes that took the row-subset path (tests read it)
         # first denoise step on a second stream beside the prefill (it needs layer l's K / V only at its layer l).  Measured, hipGraph
         # replay, same box, interleaved: 15.65 -> 16.30 ms per chunk — the step's 110 short kernels take CUs from the prefill's
         # load-bound GEMMs for longer than they save.  Kept as a switch, OFF by default.
@@ -358,7 +378,7 @@ class LAP:
             self._w8[name] = ent
         return ent[1:]
 
-    def _lin0(self, x, name, residual=None, out=None):
+    def _lin0(self, x, name, residual=None, out=None, tile=-1):
         """y = x @ Wt^T (+ residual) for a prefix-stream projection: bf16 MFMA GEMM, or e4m3 x e4m3 when gemm_dtype == 'fp8'."""
         if self.gemm_dtype == "fp8":
             x8, sx = hip.quantize_fp8(x)
@@ -368,7 +388,19 @@ class LAP:
             # measurement switch: the reference rounds the projection to bf16 and then the sum to bf16
             # (gemma.py:285,582-583); the fused epilogue adds in f32 and rounds once
             return hip.add_bf16(residual, hip.linear_fwd(x, self.W(name)))
-        return hip.linear_fwd(x, self.W(name), out, residual=residual)
+        return hip.linear_fwd(x, self.W(name), out, residual=residual, tile=tile)
+
+    def _rows_res_tile(self, x, name):
+        """Tile request for the out / down projection (+ residual) of the last layer's row subset: 14, the assembly residual kernel
+        the other layers' out / down products run on, where the library takes the shape (M a multiple of 256) and no A/B switch has
+        the assembly routes off; else -1, the planner's choice.  Left to itself the planner's fill rule sends the 16 tiles of
+        512 x 2048 to the HIP tiles: the step's out / down products would no longer all be the one kernel."""
+        if os.environ.get("LAP_GEMM_NO_ASM") is not None or os.environ.get("LAP_GEMM_NO_ASM_RES") is not None or \
+                os.environ.get("LAP_UNFUSED_RESIDUAL", "0") == "1":
+            return -1
+        w = self.W(name)
+        ok = hip._lib.lap_gemm_asm_res_ok(0, x.shape[0], w.shape[0], x.shape[1], x.stride(0), w.stride(0), w.shape[0])
+        return 14 if ok and x.stride(1) == 1 else -1
 
     def _dgrad0(self, dy, name):
         """dx = dy @ Wt for a prefix-stream projection (the fp8 route multiplies by the transposed fp8 copy)."""
@@ -780,10 +812,25 @@ class LAP:
         W3 = 3 * self.e.width
         return mod[:, slot * W3:(slot + 1) * W3]
 
+    def _last_layer_rows(self, lr, qinfo, B, n0, Lt, *, save, x1, collect, verbose):
+        """The row subset of the last layer's prefix stream, or None: every row.  Nothing behind the last layer's K / V reads a
+        prefix row but the language head, and it reads `lr.sel`'s rows only (16 of 560 per sample at the benchmark's shapes), so
+        in a train step Q, the attention output, the out projection, the FFN and their backward run on those rows alone.
+        Anything that looks at the layer's other rows (`collect`, the per-layer hooks, eval, serving) or runs products this
+        path has no route for (fp8, LoRA) keeps all rows; so does a step without a row selection or with a frozen prefix."""
+        if not (self.last_layer_rows and save and x1 is not None and collect is None and not verbose and lr is not None
+                and lr.sel is not None and self.gemm_dtype == "bf16" and not self._prefix_frozen()):
+            return None
+        p = f"llm/{self.v.depth - 1}/"
+        if any(self._lora(p + k) is not None for k in ("wqkv0", "wo0", "wgu0", "wd0")):
+            return None
+        return LastRows(lr.sel, qinfo, B, n0, Lt)
+
     def _llm_fwd(self, x0, x1, mod, pos, qinfo, kinfo, B, n0, n1, save: bool, kv_cache=None, cache_out=None, collect=None,
-                 mod_shared: bool = False, layers=None):
+                 mod_shared: bool = False, layers=None, last_rows=None):
         """gemma.Module.__call__ layers (gemma.py:336-387,167-290).  x0 [B*n0, Dv] or None, x1 [B*n1, De] or None.
         kv_cache: per-layer (k, v) of the prefix used as key segment 0 when x0 is None (serving).
+        last_rows (`_last_layer_rows`): the last layer's prefix stream is compact behind K / V, and so is the x0 returned.
         Returns final pre-norm activations and the saved context."""
         v, e = self.v, self.e
         NH, HD, KV = v.num_heads, v.head_dim, v.num_kv_heads
@@ -793,16 +840,23 @@ class LAP:
         sfx = self._suffix_stream(*([x1, mod] if mod is not None else [x1])) if (x0 is not None and x1 is not None) else None
         main = torch.cuda.current_stream() if sfx is not None else None
         on_sfx = (lambda: torch.cuda.stream(sfx)) if sfx is not None else contextlib.nullcontext
+        if last_rows is not None and not (save and x0 is not None and x1 is not None and layers is None and collect is None):
+            raise ValueError("_llm_fwd: last_rows goes with a saved two-stream pass over all layers without `collect`")
         for l in (range(v.depth) if layers is None else layers):    # `layers`: test hook (teacher-forced per-layer parity)
             self.comm.wait_unit(f"llm{l}", also=sfx)
             p = f"llm/{l}/"
+            rows0 = last_rows if l == v.depth - 1 else None
             q = [None, None]; k = [None, None]; vv = [None, None]; h = [None, None]; rstd_a = [None, None]
             lt = [{}, {}]       # LoRA down products t per stream and projection (kept for the backward)
             if x0 is not None:
                 h[0], rstd_a[0] = hip.rmsnorm_fwd(x0, scale=self.F(p + "n_attn"), save_rstd=save)
                 qkv = self._lin0(h[0], p + "wqkv0")
                 lt[0]["wqkv"] = self._lora_fwd(h[0], qkv, p + "wqkv0")
-                q[0], k[0], vv[0] = hip.rope_split_fwd(qkv, pos, B, n0, Ttot, 0, NH, HD, HD ** -0.5)
+                if rows0 is None:
+                    q[0], k[0], vv[0] = hip.rope_split_fwd(qkv, pos, B, n0, Ttot, 0, NH, HD, HD ** -0.5)
+                else:   # K / V of every row, Q of the kept rows
+                    q[0], k[0], vv[0] = hip.rope_split_fwd(qkv, pos, B, n0, Ttot, 0, NH, HD, HD ** -0.5, q_row=rows0.inv,
+                                                           q_rows=B * rows0.n_sel)
                 del qkv
             elif kv_cache is not None:
                 k[0], vv[0] = kv_cache[l]
@@ -821,7 +875,12 @@ class LAP:
                 cache_out.append((k[0], vv[0]))
             qlen = [n0 if x0 is not None else 0, n1 if x1 is not None else 0]
             klen = [k[0].shape[0] // B if k[0] is not None else 0, n1 if x1 is not None else 0]
-            o, lse = hip.attention_fwd(q, k, vv, qlen, klen, B, NH, KV, HD, qinfo, kinfo, need_lse=save)
+            xfull = x0
+            if rows0 is not None:     # a query segment shorter than its key segment, as serving runs it against a cached prefix
+                qlen[0] = rows0.n_sel
+                x0 = hip.gather_rows_bf16(x0, rows0.rowid)      # the residual operand of the out projection, its only other reader
+                self.last_rows_steps += 1
+            o, lse = hip.attention_fwd(q, k, vv, qlen, klen, B, NH, KV, HD, qinfo if rows0 is None else rows0.qinfo, kinfo, need_lse=save)
             self._handoff(main, sfx, o[1])
             xa = [None, None]; y1 = None; hf = [None, None]; rstd_f = [None, None]; gu = [None, None]; act = [None, None]; y1f = None
             xn = [None, None]
@@ -848,7 +907,7 @@ class LAP:
                     lt[1]["wd"] = self._lora_fwd(act[1], y1f, p + "wd1")
                     xn[1] = hip.gated_residual_fwd(xa[1], y1f, self._mod_slot(mod, 2 * l + 1)[:, 2 * e.width:], n1, mld)
             if x0 is not None:
-                xa[0] = self._lin0(o[0], p + "wo0", residual=x0)
+                xa[0] = self._lin0(o[0], p + "wo0", residual=x0, tile=-1 if rows0 is None else self._rows_res_tile(o[0], p + "wo0"))
                 lt[0]["wo"] = self._lora_fwd(o[0], xa[0], p + "wo0")
                 hf[0], rstd_f[0] = hip.rmsnorm_fwd(xa[0], scale=self.F(p + "n_ffw"), save_rstd=save)
                 self.comm.pace(f"llm{l}")     # optimizer units released here start under the longest MFMA-bound GEMM of the layer
@@ -862,10 +921,10 @@ class LAP:
                     gu[0] = self._lin0(hf[0], p + "wgu0", out=gu_out)
                     lt[0]["wgu"] = self._lora_fwd(hf[0], gu[0], p + "wgu0")   # (before the GeGLU: lora.FeedForward's _dot)
                     act[0] = hip.geglu_fwd(gu[0], pad=self.gemm_dtype != "fp8")
-                xn[0] = self._lin0(act[0], p + "wd0", residual=xa[0])
+                xn[0] = self._lin0(act[0], p + "wd0", residual=xa[0], tile=-1 if rows0 is None else self._rows_res_tile(act[0], p + "wd0"))
                 lt[0]["wd"] = self._lora_fwd(act[0], xn[0], p + "wd0")
             if save:
-                ctx.append(dict(x=[x0, x1], h=h, rstd_a=rstd_a, q=q, k=k, v=vv, o=o, lse=lse, xa=xa, y1=y1, hf=hf, rstd_f=rstd_f,
+                ctx.append(dict(x=[xfull, x1], h=h, rstd_a=rstd_a, q=q, k=k, v=vv, o=o, lse=lse, xa=xa, y1=y1, hf=hf, rstd_f=rstd_f,
                                 gu=gu, act=act, y1f=y1f, lt=lt))
             x0, x1 = xn
             if collect is not None:
@@ -925,7 +984,8 @@ class LAP:
                 x0, h = hip.fused_reduce_norm(part, ks, rows, Dv, residual=xa, norm=0)
         return x0
 
-    def _llm_bwd(self, ctx, dx0, dx1, mod, dmod, pos, qinfo, kinfo, B, n0, n1):
+    def _llm_bwd(self, ctx, dx0, dx1, mod, dmod, pos, qinfo, kinfo, B, n0, n1, last_rows=None):
+        """last_rows: as in `_llm_fwd` — dx0 arrives with the kept rows only and leaves the last layer with all of them."""
         v, e = self.v, self.e
         NH, HD, KV = v.num_heads, v.head_dim, v.num_kv_heads
         Ttot = pos.shape[1]
@@ -940,6 +1000,7 @@ class LAP:
             p = f"llm/{l}/"
             c = ctx[l]
             d_o = [None, None]
+            rows0 = last_rows if l == v.depth - 1 else None
             # ---- FFN + attention output, suffix stream: xn = xa + y1f * gate_f  (on the second HIP stream, see the module doc)
             slot_f, slot_a = 2 * l + 1, 2 * l
             if has_sfx and not ada:
@@ -1002,7 +1063,8 @@ class LAP:
                 d_o[0] = zero_do0
             # ---- attention
             self._handoff(sfx, main, d_o[1])
-            dq, dk, dv = hip.attention_bwd(c["q"], c["k"], c["v"], c["o"], d_o, c["lse"], [n0, n1], [n0, n1], B, NH, KV, HD, qinfo, kinfo,
+            dq, dk, dv = hip.attention_bwd(c["q"], c["k"], c["v"], c["o"], d_o, c["lse"], [n0 if rows0 is None else rows0.n_sel, n1], [n0, n1],
+                                           B, NH, KV, HD, qinfo if rows0 is None else rows0.qinfo, kinfo,
                                            stop_q1_to_k0=self.config.stop_action_to_vlm_grad)
             self._handoff(main, sfx, dq[1], dk[1], dv[1])
             if has_sfx:
@@ -1018,12 +1080,17 @@ class LAP:
                         hip.rmsnorm_bwd(c["x"][1], dh, c["rstd_a"][1], scale=self.F(p + "n_attn1"), dx=dx1, dscale=self.G(p + "n_attn1"), accum_dx=True)
                     del dqkv, dh
             if dx0 is not None:
-                dqkv = hip.rope_split_bwd(dq[0], dk[0], dv[0], pos, B, n0, Ttot, 0, NH, HD, HD ** -0.5)
+                dqkv = hip.rope_split_bwd(dq[0], dk[0], dv[0], pos, B, n0, Ttot, 0, NH, HD, HD ** -0.5,
+                                          q_row=None if rows0 is None else rows0.inv)      # (compact dq: zeros in the other rows' q columns)
                 self._wgrad(dqkv, c["h"][0], p + "wqkv0")
                 dh = self._dgrad0(dqkv, p + "wqkv0")
                 self._lora_bwd(dqkv, c["h"][0], c["lt"][0].get("wqkv"), dh, p + "wqkv0")
-                self._wg_join(dx0)   # (the out projection's reads dx0)
-                hip.rmsnorm_bwd(c["x"][0], dh, c["rstd_a"][0], scale=self.F(p + "n_attn"), dx=dx0, dscale=self.G(p + "n_attn"), accum_dx=True)
+                if rows0 is None:
+                    self._wg_join(dx0)   # (the out projection's reads dx0)
+                    hip.rmsnorm_bwd(c["x"][0], dh, c["rstd_a"][0], scale=self.F(p + "n_attn"), dx=dx0, dscale=self.G(p + "n_attn"), accum_dx=True)
+                else:   # all rows from here on: the norm's backward of every row, the compact residual cotangent added at its rows
+                    dx0 = hip.rmsnorm_bwd(c["x"][0], dh, c["rstd_a"][0], scale=self.F(p + "n_attn"), dscale=self.G(p + "n_attn"),
+                                          add_row=rows0.inv, addend=dx0)
                 del dqkv, dh
             ctx[l] = None
             self._unit_done(f"llm{l}", sfx)   # complete once both streams are through: the optimizer's stream waits for both, the
@@ -1124,14 +1191,18 @@ class LAP:
         qinfo, kinfo, pos = self._train_infos(obs, S if act_on else 0)
         if collect is not None:
             collect["x0_in"], collect["x1_in"], collect["pos"], collect["mod"] = x0, x1, pos, mod
-        xf0, xf1, lctx = self._llm_fwd(x0, x1, mod, pos, qinfo, kinfo, B, Pn, Sx, backward, collect=collect)
+        # the language head's rows are chosen here, once: the last layer's prefix stream may run on them alone
+        lrows = select_loss_rows(self, obs, observation, verbose=verbose) if lang_on else None
+        last_rows = self._last_layer_rows(lrows, qinfo, B, Pn, obs.tokenized_prompt.shape[1], save=backward, x1=x1, collect=collect,
+                                          verbose=verbose)
+        xf0, xf1, lctx = self._llm_fwd(x0, x1, mod, pos, qinfo, kinfo, B, Pn, Sx, backward, collect=collect, last_rows=last_rows)
         if collect is not None:
             collect["x0_out"], collect["x1_out"] = xf0, xf1
 
         fb = lambda t: t.to(torch.float32)
         sm = obs.sample_mask if obs.sample_mask is not None else torch.ones(B, dtype=torch.bool, device=dev)
-        head = lang_head_fwd(self, xf0, obs, observation, B, Pn, backward=backward, verbose=verbose, collect=collect) if lang_on else \
-            LangHead(torch.zeros(B, dtype=torch.float32, device=dev))
+        head = lang_head_fwd(self, xf0, obs, lrows, B, Pn, backward=backward, verbose=verbose, collect=collect,
+                             compact=last_rows is not None) if lang_on else LangHead(torch.zeros(B, dtype=torch.float32, device=dev))
         ah = action_head_fwd(self, xf1, mod, B, S, Sx, backward=backward) if act_on else ActionHead()
         lang_loss, v_t = head.lang_loss, ah.v_t
         # the reference's vqa_mask / pred_mask (lap.py:400-409): only where that kind of training is on
@@ -1178,7 +1249,7 @@ class LAP:
             # scatter-add of _embed_prefix_bwd would accumulate onto the previous step's values
             if self.ps.is_trainable("llm/embed"):
                 self.G("llm/embed").zero_()
-        dx0, dx1 = self._llm_bwd(lctx, dx0, dx1, mod, dmod, pos, qinfo, kinfo, B, Pn, Sx)
+        dx0, dx1 = self._llm_bwd(lctx, dx0, dx1, mod, dmod, pos, qinfo, kinfo, B, Pn, Sx, last_rows=last_rows)
         sfx = None
         if act_on and cfg.pi05:
             sfx = self._embed_suffix_bwd(sctx, dx1, dmod)
