@@ -10,7 +10,7 @@ from typing import NamedTuple
 
 import torch
 
-from lap_amd import hip
+from lap_amd import hip, prefill as serving_prefill
 from lap_amd.loss import lm_logits
 from lap_amd.model import LAP, _gen
 from lap_amd.observation import preprocess_observation
@@ -121,7 +121,7 @@ def prefill(model: LAP, observation) -> Prefill:
     model.comm.wait_unit("small")
     obs = preprocess_observation(observation, train=False, image_keys=cfg.image_keys, image_resolution=cfg.image_resolution)
     B = obs.tokenized_prompt.shape[0]
-    x0, Pn, _ = model._embed_prefix(obs, False, serve=True)
+    x0, Pn, _ = model._embed_prefix(obs, False, tower=serving_prefill.siglip_fwd_serve)
     qinfo_p, kinfo_p, ppos = model._serve_infos(obs, 1)[:3]
     prefix_mask, _ = model._prefix_masks(obs)
     ar = torch.arange(Pn, device=dev)
@@ -132,7 +132,7 @@ def prefill(model: LAP, observation) -> Prefill:
     qinfo_d = torch.full((B, 1), (1 << 24) | 0xFFFFFF, dtype=torch.int32, device=dev)
     cache = []
     if model.serve_fusions and model.gemm_dtype == "bf16":
-        xf0 = model._llm_prefill(x0, ppos, qinfo_p, kinfo_p, B, Pn, cache)
+        xf0 = serving_prefill.llm_prefill(model, x0, ppos, qinfo_p, kinfo_p, B, Pn, cache)
     else:
         xf0, _, _ = model._llm_fwd(x0, None, None, ppos, qinfo_p, kinfo_p, B, Pn, 0, False, cache_out=cache)
     last = (torch.arange(B, device=dev) * Pn + seqlen - 1)

@@ -1239,7 +1239,7 @@ def serve_final_euler(x, mod, mod_ld, rps, w_out, b_out, x_t, dt, v_out=None, ep
 
 
 def serve_final_euler_embed(x, mod, mod_ld, rps, w_out, b_out, x_t, dt, v_out=None, eps=1e-6, w_in=None, b_in=None, tokens=None):
-    """serve_final_euler (action_dim 32) and, with `tokens` (a [rows, D] bf16 tensor to fill), the next step's serve_embed_actions in one launch."""
+    """serve_final_euler (action_dim 7 or 8 at width 1024) and, with `tokens` (a [rows, D] bf16 tensor to fill), the next step's serve_embed_actions in one launch."""
     rows, D = x.shape
     call("lap_serve_final_euler_embed", _p(x), _p(mod), mod_ld, rps, _p(w_out), _p(b_out), _p(x_t), _p(v_out), rows, D, w_out.shape[0], float(dt), float(eps),
          _p(w_in), _p(b_in), _p(tokens))

@@ -5,8 +5,8 @@ Keeps the reference's model surface (src/lap/models/lap.py):
     sample_actions(rng, observation, *, num_steps=10, noise=None) -> [b, ah, ad]         lap.py:605-675
 and adds `loss_and_grad(...)`, the fused forward + hand-written backward that the train step uses (the
 reference gets it from nnx.value_and_grad, scripts/train.py:358-361).  `_loss_impl` is the schedule of that step (streams, collectives,
-the order of the passes); the language head, the action head and the sample-weight mixing it calls are in lap_amd/loss.py, token
-decoding is in lap_amd/ar_decode.py.
+the order of the passes); the language head, the action head and the sample-weight mixing it calls are in lap_amd/loss.py.  The serving
+paths are modules of functions on the model: the action sampler in flow_sample.py, token decoding in ar_decode.py, their prefill in prefill.py.
 
 Everything numeric is a call into liblap_hip.so (lap_amd/hip.py); torch only owns device memory, the stream,
 and a few O(batch x tokens) integer tensors (masks -> per-token info words, positions).  There is no autograd
@@ -100,7 +100,7 @@ class LAP:
         self.n_img_tok = (config.image_size // self.s.patch) ** 2
         self.deterministic = True
         self.dual_stream = os.environ.get("LAP_DUAL_STREAM", "1") != "0"
-        # serving prefill on the fused consumers (`_siglip_fwd_serve`, `_llm_prefill`); "0": the generic layer loops (A/B, tests)
+        # serving prefill on the fused consumers (lap_amd/prefill.py); "0": the generic layer loops (A/B, tests)
         self.serve_fusions = os.environ.get("LAP_SERVE_FUSIONS", "1") != "0"
         # prefix stream, bf16: d(act) of the down projection goes straight into the GeGLU backward inside the assembly GEMM's epilogue
         self.fuse_geglu_bwd = os.environ.get("LAP_FUSE_GEGLU_BWD", "1") != "0" and gemm_dtype != "fp8"
@@ -142,9 +142,7 @@ class LAP:
         # ... and every panel launch pulls the NEXT launch's weights into the Infinity Cache with a fifth wave per block (the chain's
         # launches otherwise meet their weights HBM-cold).  LAP_SERVE_PREFETCH=0: off (A/B runs)
         self.serve_prefetch = os.environ.get("LAP_SERVE_PREFETCH", "1") != "0"
-        self._chain_ctr = None
-        self._chain_scratch = None
-        self._den = None
+        self._chain_ctr = self._chain_scratch = self._den = None     # the chain's barrier counters and scratch, the overlap's side stream
         # K splits of the prefill's qkv / out / down projections, down's tile.  Round 5 sweep incl. the consumer (tools/probes/
         # prefill_down_sweep.py, us per GEMM + reduce / residual / norm): 256 x 256 x 8 65.0 | 320 x 128 (tile 19) x 8 60.8 | 320 x 256 x 16 64.5
         ks = os.environ.get("LAP_PREFILL_KS", "4,1,8,19").split(",")
@@ -169,7 +167,7 @@ class LAP:
                 if geo is not None:
                     self._lora_geo[f"{proj}{i}"] = (geo[0], geo[2], geo[3])
         self._merge_depth = 0
-        # every parameter-derived tensor of the serving paths (`_merged`, `_dec_fp8`, `_pw`, `_serve_packed_weights`, `_serve_mods`)
+        # every parameter-derived tensor of the serving paths (`_merged`, `_dec_fp8`, `prefill.panel_weight`, `flow_sample.serve_packed_weights`, `serve_mods`)
         self.serving_cache = ServeCache(self.ps, self.device, lambda unit: self.comm.wait_unit(unit))
         if self._lora_geo and gemm_dtype == "fp8":
             raise ValueError("gemm_dtype='fp8' has no LoRA route: use gemm_dtype='bf16' with the LoRA Gemma variants")
@@ -345,7 +343,7 @@ class LAP:
 
     def _merged(self, name):
         """bf16(W + s B^T A) of a LoRA'd projection from the f32 masters, rounded once (csrc/lora.hip lap_lora_merge): persistent
-        like `_serve_mods` and recomputed in place per parameter version."""
+        like `flow_sample.serve_mods` and recomputed in place per parameter version."""
         def build(old):
             _, l, key = name.split("/")
             self.comm.wait_unit(f"llm{l}")
@@ -455,23 +453,11 @@ class LAP:
                 x = self._siglip_block(l, x, N, T, W, hd, None, False)
             return x, None
         N = images.shape[0]
-        patches = hip.im2col_patch(images.contiguous(), s.patch)
-        # f32 stem (siglip_gemma3.py:398-408) on the MFMA path: x = hi + lo (2 x bf16, 16 mantissa bits), products exact
-        # in the f32 accumulator, the lo.lo term (2^-18 relative) dropped
-        p_hi, p_lo = hip.split_f32_hilo(patches)
-        w_hi, w_lo = hip.split_f32_hilo(self.F("img/stem_w"))
-        del patches
-        stem = torch.empty((p_hi.shape[0], W), dtype=torch.float32, device=p_hi.device)
-        R, Kp = p_hi.shape
-        hip.gemm(p_hi, w_hi, stem, M=R, N=W, K=Kp, lda=Kp, ldb=Kp, ldc=W, bias=self.F("img/stem_b"))
-        hip.gemm(p_hi, w_lo, stem, M=R, N=W, K=Kp, lda=Kp, ldb=Kp, ldc=W, accum=True)
-        hip.gemm(p_lo, w_hi, stem, M=R, N=W, K=Kp, lda=Kp, ldb=Kp, ldc=W, accum=True)
-        x = hip.add_posemb_cast(stem, self.F("img/pos"), T)
-        del stem
+        x, patches = self._siglip_stem(images)
         if collect is not None:
             collect["img/stem"] = x
         if save:
-            ctx["patches"] = (p_hi, p_lo)
+            ctx["patches"] = patches
         for l in range(s.depth):
             x = self._siglip_block(l, x, N, T, W, hd, ctx, save)
             if collect is not None:
@@ -485,61 +471,17 @@ class LAP:
             collect["img/out"] = tok
         return tok, ctx
 
-    def _siglip_fwd_serve(self, images: torch.Tensor):
-        """The tower of `_siglip_fwd` for the serving prefill (nothing is kept for a backward): same operations and rounding
-        points, fewer launches — GELU in fc1's epilogue (after the bf16 rounding of the Dense output), and fc2's split-K reduce,
-        bias, residual add and the NEXT LayerNorm in one consumer pass (`lap_fused_reduce_norm`).  12 -> 10 launches per block,
-        on block tiles sized for 512 rows (lap_gemm_bf16_ex serving rule)."""
-        s, T = self.s, self.n_img_tok
-        W = s.width
-        hd = W // s.num_heads
-        N = images.shape[0]
-        patches = hip.im2col_patch(images.contiguous(), s.patch)
-        p_hi, p_lo = hip.split_f32_hilo(patches)
+    def _siglip_stem(self, images: torch.Tensor):
+        """f32 stem (siglip_gemma3.py:398-408) on the MFMA path -> (x bf16 [N*T, W], the (hi, lo) patches its weight gradient reads):
+        x = hi + lo (2 x bf16, 16 mantissa bits), products exact in the f32 accumulator, the lo.lo term (2^-18 relative) dropped."""
+        p_hi, p_lo = hip.split_f32_hilo(hip.im2col_patch(images.contiguous(), self.s.patch))
         w_hi, w_lo = hip.split_f32_hilo(self.F("img/stem_w"))
-        stem = torch.empty((p_hi.shape[0], W), dtype=torch.float32, device=p_hi.device)
-        R, Kp = p_hi.shape
+        (R, Kp), W = p_hi.shape, self.s.width
+        stem = torch.empty((R, W), dtype=torch.float32, device=p_hi.device)
         hip.gemm(p_hi, w_hi, stem, M=R, N=W, K=Kp, lda=Kp, ldb=Kp, ldc=W, bias=self.F("img/stem_b"))
         hip.gemm(p_hi, w_lo, stem, M=R, N=W, K=Kp, lda=Kp, ldb=Kp, ldc=W, accum=True)
         hip.gemm(p_lo, w_hi, stem, M=R, N=W, K=Kp, lda=Kp, ldb=Kp, ldc=W, accum=True)
-        x = hip.add_posemb_cast(stem, self.F("img/pos"), T)
-        scratch = hip._gemm_scratch(self.device)
-        self.comm.wait_unit("img0")
-        y, _, _ = hip.layernorm_fwd(x, self.F("img/0/ln1_g"), self.F("img/0/ln1_b"))
-        rows = x.shape[0]
-        mlp = self.W("img/0/w1").shape[0]
-        panel = (self.serve_panel and rows <= 640 and hip.panel_gemm_ok(rows, 3 * W, W) and hip.panel_gemm_ok(rows, mlp, W)
-                 and hip.panel_gemm_ok(rows, W, mlp, 4))
-        pf = (lambda name: self._pw(name)) if panel and self.serve_prefetch else (lambda name: None)   # the next launch's weights
-        for l in range(s.depth):
-            p = f"img/{l}/"
-            if panel:    # us per launch at 512 rows, replayed graph (tools/probes/panel_bench.py): 11.6 -> 11.0, 9.0 -> 8.0, 14.5 -> 12.8, 14.9 -> 12.0
-                qkv = hip.panel_linear(y, self._pw(p + "wqkv"), 3 * W, bias=self.F(p + "bqkv"), nt=self._panel_nt[0], prefetch=pf(p + "wo"))
-            else:
-                qkv = hip.linear_fwd(y, self.W(p + "wqkv"), bias=self.F(p + "bqkv"))
-            (o, _), _ = hip.attention_fwd([qkv[:, :W]], [qkv[:, W:2 * W]], [qkv[:, 2 * W:]], [T], [T], N, s.num_heads, s.num_heads, hd,
-                                          scale=hd ** -0.5, q_rs=(3 * W, 0), kv_rs=(3 * W, 0), need_lse=False)
-            if panel:
-                x1 = hip.panel_linear(o, self._pw(p + "wo"), W, bias=self.F(p + "bo"), residual=x, nt=self._panel_nt[1], prefetch=pf(p + "w1"))
-            else:
-                x1 = hip.linear_fwd(o, self.W(p + "wo"), bias=self.F(p + "bo"), residual=x)
-            y2, _, _ = hip.layernorm_fwd(x1, self.F(p + "ln2_g"), self.F(p + "ln2_b"))
-            if panel:
-                a = hip.panel_linear(y2, self._pw(p + "w1"), mlp, bias=self.F(p + "b1"), gelu=self._panel_gelu, nt=self._panel_nt[2], prefetch=pf(p + "w2"))
-                if l + 1 < s.depth:
-                    self.comm.wait_unit(f"img{l + 1}")
-                part, ks = hip.panel_partials(a, self._pw(p + "w2"), W, scratch, 4, nt=self._panel_nt[3], prefetch=pf(f"img/{l + 1}/wqkv") if l + 1 < s.depth else None)
-            else:
-                a = hip.linear_fwd(y2, self.W(p + "w1"), bias=self.F(p + "b1"), gelu="bf16")
-                part, ks = hip.linear_partials(a, self.W(p + "w2"), scratch)
-            if l + 1 < s.depth:
-                self.comm.wait_unit(f"img{l + 1}")
-                g, b = self.F(f"img/{l + 1}/ln1_g"), self.F(f"img/{l + 1}/ln1_b")
-            else:
-                self.comm.wait_unit("img_head")
-                g, b = self.F("img/norm_g"), self.F("img/norm_b")
-            x, y = hip.fused_reduce_norm(part, ks, x1.shape[0], W, bias=self.F(p + "b2"), residual=x1, norm=2, gamma=g, beta=b)
-        return hip.linear_fwd(y, self.W("img/head_w"), bias=self.F("img/head_b"))
+        return hip.add_posemb_cast(stem, self.F("img/pos"), self.n_img_tok), (p_hi, p_lo)
 
     def _siglip_block(self, l, x, N, T, W, hd, ctx, save):
         """One pre-LN encoder block (siglip_gemma3.py:59-167): x + MHA(LN(x)), then + MLP(LN(.))."""
@@ -694,18 +636,14 @@ class LAP:
         return (i32(qinfo_p), i32(kinfo_p), ppos, i32(qinfo_s), i32(torch.cat([kinfo_p, kinfo_s], 1)), i32(torch.cat([ppos, spos], 1)))
 
     # ================================================================== embedding of the two streams
-    def _embed_prefix(self, obs: CoTObservation, save: bool, collect=None, serve: bool = False):
-        """lap.py:118-170 -> x0 bf16 [B*Pn, Dv] with rows (b, [img0 | img1 | prompt])."""
-        cfg = self.config
-        keys = cfg.image_keys
-        B = obs.tokenized_prompt.shape[0]
-        T, Lt, Dv = self.n_img_tok, obs.tokenized_prompt.shape[1], self.v.width
+    def _embed_prefix(self, obs: CoTObservation, save: bool, collect=None, tower=None):
+        """lap.py:118-170 -> x0 bf16 [B*Pn, Dv] with rows (b, [img0 | img1 | prompt]).  tower: the serving callers' (prefill.siglip_fwd_serve)."""
+        B, Lt = obs.tokenized_prompt.shape
+        T, Dv, keys = self.n_img_tok, self.v.width, self.config.image_keys
         Pn = T * len(keys) + Lt
         images = torch.cat([obs.images[k] for k in keys], 0)
-        if save or collect is not None or not (serve and self.serve_fusions):
-            tok, ictx = self._siglip_fwd(images, save, collect)
-        else:
-            tok, ictx = self._siglip_fwd_serve(images), None
+        fused = tower is not None and self.serve_fusions and not save and collect is None
+        tok, ictx = (tower(self, images), None) if fused else self._siglip_fwd(images, save, collect)
         x0 = torch.empty((B * Pn, Dv), dtype=torch.bfloat16, device=self.device)
         for i in range(len(keys)):
             hip.copy_rows_bf16(tok[i * B * T:(i + 1) * B * T], x0, B * T, T, Dv, T, 0, Pn, i * T)
@@ -932,58 +870,6 @@ class LAP:
         self._handoff(sfx, main, x1)
         return x0, x1, ctx
 
-    def _llm_prefill(self, x0, pos, qinfo, kinfo, B, n0, cache_out, kv_events=None):
-        """The prefix-only pass of `_llm_fwd` (x1 = None, nothing saved) for the serving prefill: K / V of every layer go to
-        `cache_out`, the last layer's residual stream is returned.  Same operations and rounding points; the split-K projections
-        leave f32 slabs and their consumers do the rest in one pass each — qkv: reduce + RoPE + head split (sin / cos of the
-        prefix positions from one table for all layers), out / down: reduce + residual + the NEXT RMSNorm — 14 -> 10 launches
-        per layer."""
-        v = self.v
-        NH, HD, KV = v.num_heads, v.head_dim, v.num_kv_heads
-        Ttot = pos.shape[1]
-        Dv = v.width
-        scratch = hip._gemm_scratch(self.device)
-        tab = hip.rope_table(pos, B, n0, Ttot, 0, HD)
-        self.comm.wait_unit("llm0")
-        h, _ = hip.rmsnorm_fwd(x0, scale=self.F("llm/0/n_attn"), save_rstd=False)
-        rows = x0.shape[0]
-        panel = (self.serve_panel and rows <= 640 and hip.panel_gemm_ok(rows, (NH + 2 * KV) * HD, Dv) and hip.panel_gemm_ok(rows, Dv, NH * HD))
-        panel_q, panel_o = panel and "q" in self._panel_llm, panel and "o" in self._panel_llm
-        pf = (lambda name: self._pw(name)) if panel_o and self.serve_prefetch else (lambda name: None)   # the next panel launch's weights
-        for l in range(v.depth):
-            p = f"llm/{l}/"
-            if panel_q:   # one f32 slab, no K split (us, 560 rows: 23.5 -> 16.9 in front of the same consumer)
-                part, ks = hip.panel_partials(h, self._pw(p + "wqkv0"), (NH + 2 * KV) * HD, scratch, 1, nt=2, prefetch=pf(p + "wo0"))
-            else:
-                part, ks = hip.linear_partials(h, self.W(p + "wqkv0"), scratch, ksplit=self._prefill_ks[0])
-            q, k, vv = hip.fused_reduce_rope_split(part, ks, pos, B, n0, Ttot, 0, NH, HD, HD ** -0.5, table=tab)
-            cache_out.append((k, vv))
-            if kv_events is not None:     # layer l's K / V exist from here on: the first denoise step may use them (sample_actions)
-                ev = torch.cuda.Event()
-                ev.record()
-                kv_events.append(ev)
-            o, _ = hip.attention_fwd([q, None], [k, None], [vv, None], [n0, 0], [n0, 0], B, NH, KV, HD, qinfo, kinfo, need_lse=False)
-            if panel_o:   # (16.2 -> 14.6)
-                xa = hip.panel_linear(o[0], self._pw(p + "wo0"), Dv, residual=x0, nt=4)   # (the next panel launch is 200 MB of gate|up and down weights away)
-                hf, _ = hip.rmsnorm_fwd(xa, scale=self.F(p + "n_ffw"), save_rstd=False)
-            elif self._prefill_ks[1] > 1:
-                part, ks = hip.linear_partials(o[0], self.W(p + "wo0"), scratch, ksplit=self._prefill_ks[1])
-                xa, hf = hip.fused_reduce_norm(part, ks, rows, Dv, residual=x0, norm=1, gamma=self.F(p + "n_ffw"))
-            else:   # (measured: the unsplit 64-row tile with the residual epilogue + a norm launch beats split + fused consumer here)
-                xa = hip.linear_fwd(o[0], self.W(p + "wo0"), residual=x0)
-                hf, _ = hip.rmsnorm_fwd(xa, scale=self.F(p + "n_ffw"), save_rstd=False)
-            if rows <= 640 and (v.mlp_dim & 127) == 0:    # gate|up projection + GeGLU in one launch (the 320-row tile's paired epilogue)
-                act = hip.linear_geglu(hf, self.W(p + "wgu0"), exp2=self._panel_gelu == "exp2")
-            else:
-                act = hip.geglu_fwd(hip.linear_fwd(hf, self.W(p + "wgu0")))
-            part, ks = hip.linear_partials(act, self.W(p + "wd0"), scratch, ksplit=self._prefill_ks[2], tile=self._prefill_ks[3])
-            if l + 1 < v.depth:
-                self.comm.wait_unit(f"llm{l + 1}")
-                x0, h = hip.fused_reduce_norm(part, ks, rows, Dv, residual=xa, norm=1, gamma=self.F(f"llm/{l + 1}/n_attn"))
-            else:
-                x0, h = hip.fused_reduce_norm(part, ks, rows, Dv, residual=xa, norm=0)
-        return x0
-
     def _llm_bwd(self, ctx, dx0, dx1, mod, dmod, pos, qinfo, kinfo, B, n0, n1, last_rows=None):
         """last_rows: as in `_llm_fwd` — dx0 arrives with the kept rows only and leaves the last layer with all of them."""
         v, e = self.v, self.e
@@ -1097,58 +983,6 @@ class LAP:
                                              # compute stream goes on (it meets the second stream again at the next attention)
         self._handoff(sfx, main)
         return dx0, dx1
-
-    def _expert_denoise_fwd(self, x1, mod, pos, qinfo, kinfo, B, Pn, S, cache, rope_tab=None):
-        """The 18 action-expert layers of one denoise step (gemma.py:336-387 with xs = [None, suffix], kv_cache given)
-        on the fused serving kernels: every projection is a split-K GEMM that leaves f32 partials, and the reduction
-        happens inside the consumer (RoPE+split / GeGLU / gated residual + next adaptive RMSNorm).  `mod` is the single
-        modulation row of this step (shared by all samples).  Returns the final adaRMS-normed suffix activations."""
-        v, e = self.v, self.e
-        NH, HD, KV = v.num_heads, v.head_dim, v.num_kv_heads
-        Ttot = pos.shape[1]
-        We = e.width
-        scratch = hip._gemm_scratch(self.device)
-        slot = lambda j: self._mod_slot(mod, j)
-        h, _ = hip.rmsnorm_fwd(x1, mod=slot(0), rows_per_sample=S, save_rstd=False, mod_ld=0)
-        x = x1
-        for l in range(v.depth):
-            self.comm.wait_unit(f"llm{l}")
-            p = f"llm/{l}/"
-            part, ks = hip.linear_partials(h, self.W(p + "wqkv1"), scratch)
-            q, k, vv = hip.fused_reduce_rope_split(part, ks, pos, B, S, Ttot, Ttot - S, NH, HD, HD ** -0.5, table=rope_tab)
-            ck, cv = cache[l]
-            o, _ = hip.attention_fwd([None, q], [ck, k], [cv, vv], [0, S], [Pn, S], B, NH, KV, HD, qinfo, kinfo, need_lse=False)
-            part, ks = hip.linear_partials(o[1], self.W(p + "wo1"), scratch)
-            xa, hf = hip.fused_reduce_residual_norm(part, ks, x, slot(2 * l)[:, 2 * We:], 0, slot(2 * l + 1), 0, S)
-            part, ks = hip.linear_partials(hf, self.W(p + "wgu1"), scratch)
-            act = hip.fused_reduce_geglu(part, ks, B * S, e.mlp_dim)
-            part, ks = hip.linear_partials(act, self.W(p + "wd1"), scratch)
-            x, h = hip.fused_reduce_residual_norm(part, ks, xa, slot(2 * l + 1)[:, 2 * We:], 0, slot(2 * l + 2), 0, S)
-        return h   # slot 2L is final_norm_1: h == final adaRMS norm of the last layer's output
-
-    def _expert_denoise_skinny(self, x1, mod, qinfo, kinfo, B, Pn, S, cache, rope_tab, kv_events=None):
-        """The same 18 layers on the skinny-M fused projections (csrc/serve_skinny.hip): five launches per layer —
-        [adaRMS + qkv + RoPE/split] -> attention -> [out-proj + gated residual] -> [adaRMS + gate|up + GeGLU] ->
-        [down-proj + gated residual] — with no f32 partial slabs in between.  Returns the last layer's residual stream
-        (the final adaRMS norm is part of lap_serve_final_euler)."""
-        v, e = self.v, self.e
-        NH, HD, KV = v.num_heads, v.head_dim, v.num_kv_heads
-        We = e.width
-        slot = lambda j: self._mod_slot(mod, j)
-        x = x1
-        for l in range(v.depth):
-            self.comm.wait_unit(f"llm{l}")
-            p = f"llm/{l}/"
-            q, k, vv = hip.serve_qkv_rope(x, slot(2 * l), 0, S, self.W(p + "wqkv1"), rope_tab, NH, HD, HD ** -0.5)
-            ck, cv = cache[l]
-            if kv_events is not None:     # running beside the prefill (first denoise step): layer l's cache is ready at its event
-                torch.cuda.current_stream().wait_event(kv_events[l])
-                ck.record_stream(torch.cuda.current_stream()); cv.record_stream(torch.cuda.current_stream())
-            o, _ = hip.attention_fwd([None, q], [ck, k], [cv, vv], [0, S], [Pn, S], B, NH, KV, HD, qinfo, kinfo, need_lse=False)
-            xa = hip.serve_proj_residual(o[1], self.W(p + "wo1"), x, slot(2 * l)[:, 2 * We:], 0, S)
-            act = hip.serve_gate_up(xa, slot(2 * l + 1), 0, S, self.W(p + "wgu1"))
-            x = hip.serve_proj_residual(act, self.W(p + "wd1"), xa, slot(2 * l + 1)[:, 2 * We:], 0, S)
-        return x
 
     # ================================================================== training forward (+ backward)
     def _loss_impl(self, rng, observation: CoTObservation, actions: torch.Tensor, *, train: bool, noise=None, time=None,
@@ -1289,140 +1123,9 @@ class LAP:
         with self._serving_weights():
             return self._sample_actions(rng, observation, num_steps=num_steps, noise=noise, collect=collect, fused=fused)
 
-    def _sample_actions(self, rng, observation, *, num_steps: int = 10, noise=None, collect=None, fused=True):
-        """`sample_actions` with the weights as `_serving_weights` presents them (merged when the model has adapters)."""
-        cfg = self.config
-        dev = self.device
-        self.comm.wait_unit("small")
-        obs = preprocess_observation(observation, train=False, image_keys=cfg.image_keys, image_resolution=cfg.image_resolution)
-        B = obs.tokenized_prompt.shape[0]
-        S, ad = self.action_horizon, self.action_dim
-        if fused is True:
-            fused = "skinny" if hip.serve_supported(self.e.width, self.v.head_dim, self.e.mlp_dim, self.v.num_heads) else "partials"
-        if fused not in (False, "skinny", "partials"):
-            raise ValueError(f"fused={fused!r}")
-        if noise is None:
-            noise = torch.randn((B, S, ad), generator=_gen(rng, dev), device=dev, dtype=torch.float32)
-        x_t = noise.to(dev, torch.float32).contiguous().clone()
-        x0, Pn, _ = self._embed_prefix(obs, False, serve=True)
-        qinfo_p, kinfo_p, ppos, qinfo_s, kinfo_all, pos_all = self._serve_infos(obs, S)
-        if not cfg.pi05:
-            return self._sample_actions_pi0(obs, x_t, x0, Pn, (qinfo_p, kinfo_p, ppos, qinfo_s, kinfo_all, pos_all), num_steps, collect)
-        dt = -1.0 / num_steps
-        times, t = [], 1.0
-        while t >= -dt / 2:  # lap.py:669-674 loop condition, unrolled on the host (the time grid is data independent)
-            times.append(t)
-            t += dt
-        # the adaRMS condition depends on the denoise time only: all steps' modulations in one pass over the adaRMS bank —
-        # and on nothing else, so they are computed ONCE per (step count, parameter version) and kept: a captured sampler
-        # (serve.GraphedSampler warms up before it captures) holds no time-MLP kernels at all (-0.25 ms per chunk)
-        mods = self._serve_mods(len(times), dt)
-        # ... and so are the action tokens' positions: one sin / cos table serves the 10 x 18 fused RoPE kernels
-        rope_tab = hip.rope_table(pos_all, B, S, pos_all.shape[1], pos_all.shape[1] - S, self.v.head_dim) if fused else None
-        cache = []
-        fast_prefill = self.serve_fusions and collect is None and self.gemm_dtype == "bf16"
-        # The first denoise step needs layer l's K / V only when it reaches layer l: it is issued on a second stream and runs
-        # beside the prefill's layers l+1 .. (whose big GEMMs leave CUs idle at their tails), joined before step 1.
-        overlap = fast_prefill and fused == "skinny" and self.serve_overlap and dev.type == "cuda" and len(times) > 1
-        kv_events = [] if overlap else None
-        if overlap:
-            if self._den is None:
-                self._den = torch.cuda.Stream(dev)
-            start = torch.cuda.Event()
-            start.record()
-        if fast_prefill:
-            self._llm_prefill(x0, ppos, qinfo_p, kinfo_p, B, Pn, cache, kv_events=kv_events)
-        else:
-            self._llm_fwd(x0, None, None, ppos, qinfo_p, kinfo_p, B, Pn, 0, False, cache_out=cache)
-        nslot = 2 * self.v.depth
-        chain = (fused == "skinny" and self.serve_chain and not overlap and dev.type == "cuda" and self.v.depth <= hip.CHAIN_MAX_DEPTH
-                 and hip.serve_chain_ok(B, S, self.e.width, self.e.mlp_dim, self.v.num_heads, self.v.head_dim, self.v.num_kv_heads, Pn))
-        if chain:
-            if self._chain_ctr is None:
-                self._chain_ctr = hip.serve_chain_counters(dev)
-            for l in range(self.v.depth):
-                self.comm.wait_unit(f"llm{l}")
-            tp = (self.serve_packed and self.serve_tp
-                  and hip.serve_chain_tp_ok(B, S, self.e.width, self.e.mlp_dim, self.v.num_heads, self.v.head_dim, self.v.num_kv_heads, Pn))
-            if self.serve_packed:
-                chain_w = self._serve_packed_weights()
-                if self._chain_scratch is None or (tp and "tp_slabs" not in self._chain_scratch):
-                    self._chain_scratch = hip.serve_chain_scratch(dev, self.e.width, self.e.mlp_dim, self.v.num_heads, self.v.head_dim, tp=tp)
-            else:
-                chain_w = [tuple(self.W(f"llm/{l}/{n}") for n in ("wqkv1", "wo1", "wgu1", "wd1")) for l in range(self.v.depth)]
-        for step in range(len(times)):
-            mod = mods[step:step + 1]
-            if chain:
-                fuse_tail = self.serve_euler_embed and ad in (7, 8) and self.e.width == 1024     # the step's tail embeds the next step's tokens in the same launch
-                if not fuse_tail or step == 0:
-                    x1 = hip.serve_embed_actions(x_t.view(B * S, ad), self.F("act/in_w"), self.F("act/in_b"))
-                xf1 = hip.serve_chain(x1, mod, 3 * self.e.width, chain_w, cache, rope_tab, qinfo_s, kinfo_all, B, S, self.v.num_heads,
-                                      self.v.head_dim, self.e.mlp_dim, Pn, self.v.head_dim ** -0.5, self._chain_ctr,
-                                      packed_scratch=self._chain_scratch if self.serve_packed else None, tp=tp)
-                v_t = torch.empty((B * S, ad), dtype=torch.float32, device=dev) if collect is not None else None
-                if fuse_tail:
-                    x1 = torch.empty((B * S, self.e.width), dtype=torch.bfloat16, device=dev) if step + 1 < len(times) else None
-                    hip.serve_final_euler_embed(xf1, self._mod_slot(mod, nslot), 0, S, self.F("act/out_w"), self.F("act/out_b"), x_t.view(B * S, ad), dt, v_t,
-                                                w_in=self.F("act/in_w"), b_in=self.F("act/in_b"), tokens=x1)
-                else:
-                    hip.serve_final_euler(xf1, self._mod_slot(mod, nslot), 0, S, self.F("act/out_w"), self.F("act/out_b"), x_t.view(B * S, ad), dt, v_t)
-                if collect is not None:
-                    collect[f"v_t/{step}"] = v_t.view(B, S, ad)
-                continue
-            if fused == "skinny":
-                side = overlap and step == 0
-                main = torch.cuda.current_stream() if side else None
-                if side:
-                    self._den.wait_event(start)
-                    for tns in (x_t, mods, rope_tab, qinfo_s, kinfo_all):
-                        tns.record_stream(self._den)
-                with (torch.cuda.stream(self._den) if side else contextlib.nullcontext()):
-                    x1 = hip.serve_embed_actions(x_t.view(B * S, ad), self.F("act/in_w"), self.F("act/in_b"))
-                    xf1 = self._expert_denoise_skinny(x1, mod, qinfo_s, kinfo_all, B, Pn, S, cache, rope_tab, kv_events=kv_events if side else None)
-                    v_t = torch.empty((B * S, ad), dtype=torch.float32, device=dev) if collect is not None else None
-                    hip.serve_final_euler(xf1, self._mod_slot(mod, nslot), 0, S, self.F("act/out_w"), self.F("act/out_b"), x_t.view(B * S, ad), dt, v_t)
-                if side:
-                    main.wait_stream(self._den)
-                if collect is not None:
-                    collect[f"v_t/{step}"] = v_t.view(B, S, ad)
-                continue
-            x1, _ = self._embed_actions(x_t)
-            if fused == "partials":
-                pre1 = self._expert_denoise_fwd(x1, mod, pos_all, qinfo_s, kinfo_all, B, Pn, S, cache, rope_tab)
-            else:  # generic path (same numerics; kept for A/B tests)
-                _, xf1, _ = self._llm_fwd(None, x1, mod, pos_all, qinfo_s, kinfo_all, B, Pn, S, False, kv_cache=cache, mod_shared=True)
-                pre1, _ = hip.rmsnorm_fwd(xf1, mod=self._mod_slot(mod, nslot), rows_per_sample=S, save_rstd=False, mod_ld=0)
-            v_t = self._lin32(hip.cast_bf16_to_f32(pre1), "act/out_w", "act/out_b")
-            if collect is not None:
-                collect[f"v_t/{step}"] = v_t.view(B, S, ad).clone()
-            hip.axpy_f32(x_t, v_t, dt)
-        return x_t
-
-    def _sample_actions_pi0(self, obs, x_t, x0, Pn, infos, num_steps, collect):
-        """`sample_actions` for pi0 (`pi05=False`): the suffix is [state token | action tokens mixed with the time embedding], embedded anew
-        at every Euler step; the expert's layers run on the generic layer loop (plain norms and residuals) against the prefix cache.
-        Functional path: no fused serving kernels, no hipGraph chain (no registry config of the reference is pi0)."""
-        if obs.state is None:
-            raise ValueError("pi05=False feeds the continuous state through state_proj: the observation has no `state`")
-        qinfo_p, kinfo_p, ppos, qinfo_s, kinfo_all, pos_all = infos
-        B, S, ad = x_t.shape
-        Sx, We = S + 1, self.e.width
-        cache = []
-        self._llm_fwd(x0, None, None, ppos, qinfo_p, kinfo_p, B, Pn, 0, False, cache_out=cache)
-        dt = -1.0 / num_steps
-        t, step = 1.0, 0
-        while t >= -dt / 2:      # lap.py:669-674
-            x1, _ = self._embed_suffix_pi0(x_t, torch.full((B,), t, dtype=torch.float32, device=self.device), obs.state, False)
-            _, xf1, _ = self._llm_fwd(None, x1, None, pos_all, qinfo_s, kinfo_all, B, Pn, Sx, False, kv_cache=cache)
-            pre_all, _ = hip.rmsnorm_fwd(xf1, scale=self.F("llm/final_norm1"), save_rstd=False)
-            pre1 = pre_all.view(B, Sx, We)[:, 1:].reshape(B * S, We).contiguous()
-            v_t = self._lin32(hip.cast_bf16_to_f32(pre1), "act/out_w", "act/out_b")
-            if collect is not None:
-                collect[f"v_t/{step}"] = v_t.view(B, S, ad).clone()
-            hip.axpy_f32(x_t, v_t, dt)
-            t += dt
-            step += 1
-        return x_t
+    def _sample_actions(self, rng, observation, **kw):      # on the weights as they are (outside `_serving_weights`: base + adapters)
+        from lap_amd import flow_sample     # (it imports this module)
+        return flow_sample.sample_actions(self, rng, observation, **kw)
 
     def serve_chain_failed(self) -> bool:
         """True if a launch of the one-launch denoise step gave up at a grid barrier since the last check (synchronises)."""
@@ -1439,42 +1142,9 @@ class LAP:
             torch.cuda.synchronize(self.device)
             self._chain_ctr.zero_()
 
-    def _serve_mods(self, nsteps: int, dt: float):
-        """adaRMS modulations of the denoise time grid t_k = 1 + k dt (lap.py:655-660 through `_time_mod`), one PERSISTENT tensor
-        per (nsteps, dt), refreshed IN PLACE when the parameters change: a captured sampler holds its address (ADVICE r3 — a
-        cache that dropped the tensor on a version change left a replayed graph reading freed memory and stale modulations).
-        `GraphedSampler.__call__` calls `refresh_serve_caches` before every replay; never refreshed during stream capture."""
-        def build(old):
-            tvec = 1.0 + dt * torch.arange(nsteps, dtype=torch.float32, device=self.device)
-            new = self._time_mod(tvec, False)[0]
-            return new if old is None else old.copy_(new)
-        return self.serving_cache.get(("mods", nsteps, float(dt)), "ada", build)
-
-    def _serve_packed_weights(self):
-        """Fragment-packed images of the action expert's projections for the packed chain (csrc/serve_skinny_body.hpp PK),
-        persistent like `_serve_mods` and re-packed in place per parameter version (+0.62 GB for LAP-3B)."""
-        def build(old):
-            kinds = (("wqkv1", hip.PACK_QKV), ("wo1", hip.PACK_PLAIN), ("wgu1", hip.PACK_GATE_UP), ("wd1", hip.PACK_PLAIN))
-            out = []
-            for l in range(self.v.depth):
-                self.comm.wait_unit(f"llm{l}")
-                out.append(tuple(hip.serve_pack_weight(self.W(f"llm/{l}/{n}"), kind, self.v.head_dim, out=None if old is None else old[l][j])
-                                 for j, (n, kind) in enumerate(kinds)))
-            return out
-        return self.serving_cache.get(("chain",), None, build)
-
-    def _pw(self, name):
-        """Fragment-packed image (lap_serve_pack_weight kind 3) of a prefill projection for the row-panel kernel, persistent like
-        `_serve_packed_weights` and re-packed in place per parameter version."""
-        def build(old):
-            kind, l = name.split("/")[:2]
-            self.comm.wait_unit(f"{kind}{l}")
-            return hip.serve_pack_weight(self.W(name), hip.PACK_PLAIN, out=old)
-        return self.serving_cache.get(("panel", name), None, build)
-
     def _dec_fp8(self, name):
         """(e4m3 codes [N, K], f32 row scales [N]) of a weight of the fused decoder in the format of lap_amd/fp8.py: persistent
-        like `_serve_packed_weights`, built on first use and re-quantised IN PLACE per parameter version (a captured decoder
+        like `flow_sample.serve_packed_weights`, built on first use and re-quantised IN PLACE per parameter version (a captured decoder
         holds both addresses).  The layer projections are quantised from the bf16 weight `W(name)` the bf16 decoder reads (the
         merged one under `_serving_weights`), the LM head from the f32 embedding table.  +1 byte per weight on top of the bf16
         copies the prefill keeps: 2.0 GB for LAP-3B's 18 layers, 0.53 GB for the table."""

@@ -187,6 +187,76 @@ def test_full_width_sample_actions_matches_oracle(hip, monkeypatch):
     assert rel(out, generic) < max(FREE_RUN_RATIO * base, 5e-3)    # same rounding points, different K summation order
 
 
+def _serve_launch_traces(hip, monkeypatch):
+    """The library entry points that take a stream, in the order ONE fresh model issues them, for `sample_actions` (3 Euler steps)
+    on each denoise route and for `sample_tokens(decode="eager")`, run-length encoded as [[name, count], ...].  `_full_width_cfg`
+    with action_dim 7: at the LAP-3B widths the skinny projections, the one-launch chain and the panel prefill are live, and with
+    7 action dimensions so is the chain's fused Euler / embed tail (it takes 7 or 8), whose first, middle and last step differ.
+    The routes run in a fixed order on one model: what a call finds cached (packed weight images, modulations) is part of the trace."""
+    import ctypes
+
+    cfg = _full_width_cfg(monkeypatch, action_dim=7)
+    P = O.init_params(oracle_cfg(cfg), seed=5)
+    obs, _, noise, _ = make_inputs(cfg, B=1, ragged=False)
+    o = to_observation({k: v for k, v in obs.items() if k != "tokenized_langact_mask"} | {"tokenized_langact_mask": None}, DEV)
+    model = _engine(cfg, P)
+    trace = []
+
+    def traced(name, fn):
+        def call(*a):
+            trace.append(name)
+            return fn(*a)
+        return call
+    for name, fn in list(hip._fn.items()):
+        sig = hip.SIGNATURES[name]
+        if sig and sig[-1] is ctypes.c_void_p:      # (include/lap_hip.h: the stream is the last argument, a void*)
+            monkeypatch.setitem(hip._fn, name, traced(name, fn))
+
+    def record(run):
+        del trace[:]
+        run()
+        torch.cuda.synchronize()
+        rle = []
+        for name in trace:
+            if rle and rle[-1][0] == name:
+                rle[-1][1] += 1
+            else:
+                rle.append([name, 1])
+        return rle
+    sample = lambda **kw: model.sample_actions(0, o, num_steps=3, noise=noise.to(DEV), **kw)
+    out = {"chain": record(sample)}
+    monkeypatch.setattr(model, "serve_euler_embed", False)
+    out["chain_plain_tail"] = record(sample)
+    monkeypatch.setattr(model, "serve_euler_embed", True)
+    monkeypatch.setattr(model, "serve_chain", False)
+    out["skinny"] = record(sample)
+    out["partials"] = record(lambda: sample(fused="partials"))
+    out["generic"] = record(lambda: sample(fused=False))
+    out["tokens_eager"] = record(lambda: model.sample_tokens(0, o, max_decoding_steps=2, decode="eager"))
+    assert not model.serve_chain_failed()
+    return out
+
+
+def test_serving_launch_trace_matches_fixture(hip, monkeypatch):
+    """What a tolerance cannot see: a dropped, duplicated or reordered launch in the serving paths.  The ordered entry points of
+    every denoise route and of the shared prefill equal tests/golden/serve_launch_trace.json, recorded with `_serve_launch_traces`
+    on the commit before the sampler and the prefill moved out of model.py (a change that alters the launches on purpose records
+    the fixture anew, with the reason)."""
+    import json
+
+    with open(os.path.join(os.path.dirname(__file__), "golden", "serve_launch_trace.json")) as f:
+        want = json.load(f)
+    got = _serve_launch_traces(hip, monkeypatch)
+    assert set(got) == set(want)
+    for route in want:
+        assert got[route] == want[route], route
+    names = lambda route: {n for n, _ in want[route]}
+    assert "lap_serve_chain" in names("chain") and "lap_serve_final_euler_embed" in names("chain")      # the fixture holds the routes it names
+    assert "lap_serve_final_euler" in names("chain_plain_tail") and "lap_serve_qkv_rope" in names("skinny")
+    assert "lap_fused_reduce_geglu" in names("partials") and "lap_gated_residual_fwd" in names("generic")
+    assert "lap_panel_gemm_pf" in names("tokens_eager") | names("chain")
+
+
 def _check_loss_activations_and_grads(cfg, B, ragged):
     oc = oracle_cfg(cfg)
     P = O.init_params(oc, seed=7)
