@@ -11,6 +11,7 @@ from typing import NamedTuple
 import torch
 
 from lap_amd import hip, prefill as serving_prefill
+from lap_amd.joint_layers import llm_fwd
 from lap_amd.loss import lm_logits
 from lap_amd.model import LAP, _gen
 from lap_amd.observation import preprocess_observation
@@ -134,7 +135,7 @@ def prefill(model: LAP, observation) -> Prefill:
     if model.serve_fusions and model.gemm_dtype == "bf16":
         xf0 = serving_prefill.llm_prefill(model, x0, ppos, qinfo_p, kinfo_p, B, Pn, cache)
     else:
-        xf0, _, _ = model._llm_fwd(x0, None, None, ppos, qinfo_p, kinfo_p, B, Pn, 0, False, cache_out=cache)
+        xf0, _, _ = llm_fwd(model, x0, None, None, ppos, qinfo_p, kinfo_p, B, Pn, 0, False, cache_out=cache)
     last = (torch.arange(B, device=dev) * Pn + seqlen - 1)
     return Prefill(B, Pn, cache, kinfo_prefix, qinfo_d, plen, xf0.index_select(0, last).contiguous())
 

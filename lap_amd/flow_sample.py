@@ -13,6 +13,7 @@ from typing import NamedTuple
 import torch
 
 from lap_amd import hip, prefill
+from lap_amd.joint_layers import llm_fwd, mod_slot
 from lap_amd.model import LAP, _gen
 from lap_amd.observation import preprocess_observation
 
@@ -78,7 +79,7 @@ def sample_actions(model: LAP, rng, observation, *, num_steps: int = 10, noise=N
     if fast_prefill:
         prefill.llm_prefill(model, x0, ppos, qinfo_p, kinfo_p, B, Pn, cache, kv_events=kv_events)
     else:
-        model._llm_fwd(x0, None, None, ppos, qinfo_p, kinfo_p, B, Pn, 0, False, cache_out=cache)
+        llm_fwd(model, x0, None, None, ppos, qinfo_p, kinfo_p, B, Pn, 0, False, cache_out=cache)
     d = Denoise(x_t, mods, dt, B, S, Pn, cache, rope_tab, qinfo_s, kinfo_all, pos_all, collect)
     chain = (fused == "skinny" and model.serve_chain and not overlap and dev.type == "cuda" and model.v.depth <= hip.CHAIN_MAX_DEPTH
              and hip.serve_chain_ok(B, S, model.e.width, model.e.mlp_dim, model.v.num_heads, model.v.head_dim, model.v.num_kv_heads, Pn))
@@ -124,7 +125,7 @@ def _step_chain(model: LAP, d: Denoise, step, x1, *, chain):
     xf1 = hip.serve_chain(x1, mod, 3 * e.width, weights, d.cache, d.rope_tab, d.qinfo, d.kinfo, B, S, v.num_heads, v.head_dim, e.mlp_dim,
                           d.Pn, v.head_dim ** -0.5, model._chain_ctr, packed_scratch=model._chain_scratch if model.serve_packed else None, tp=tp)
     v_t = torch.empty((B * S, ad), dtype=torch.float32, device=model.device) if d.collect is not None else None
-    final = (xf1, model._mod_slot(mod, 2 * v.depth), 0, S, model.F("act/out_w"), model.F("act/out_b"), d.x_t.view(B * S, ad), d.dt, v_t)
+    final = (xf1, mod_slot(model, mod, 2 * v.depth), 0, S, model.F("act/out_w"), model.F("act/out_b"), d.x_t.view(B * S, ad), d.dt, v_t)
     if fuse_tail:
         x1 = torch.empty((B * S, e.width), dtype=torch.bfloat16, device=model.device) if step + 1 < d.mods.shape[0] else None
         hip.serve_final_euler_embed(*final, w_in=model.F("act/in_w"), b_in=model.F("act/in_b"), tokens=x1)
@@ -150,7 +151,7 @@ def _step_skinny(model: LAP, d: Denoise, step, _x1, *, start, kv_events):
         x1 = hip.serve_embed_actions(d.x_t.view(B * S, ad), model.F("act/in_w"), model.F("act/in_b"))
         xf1 = expert_denoise_skinny(model, x1, mod, d.qinfo, d.kinfo, B, d.Pn, S, d.cache, d.rope_tab, kv_events=kv_events if side else None)
         v_t = torch.empty((B * S, ad), dtype=torch.float32, device=model.device) if d.collect is not None else None
-        hip.serve_final_euler(xf1, model._mod_slot(mod, 2 * model.v.depth), 0, S, model.F("act/out_w"), model.F("act/out_b"),
+        hip.serve_final_euler(xf1, mod_slot(model, mod, 2 * model.v.depth), 0, S, model.F("act/out_w"), model.F("act/out_b"),
                               d.x_t.view(B * S, ad), d.dt, v_t)
     if side:
         main.wait_stream(model._den)
@@ -168,8 +169,8 @@ def _step_generic(model: LAP, d: Denoise, step, _x1):
     """The layer loop of the train step against the prefix cache (same numerics as the partials; kept for A/B tests)."""
     mod = d.mods[step:step + 1]
     x1, _ = model._embed_actions(d.x_t)
-    _, xf1, _ = model._llm_fwd(None, x1, mod, d.pos, d.qinfo, d.kinfo, d.B, d.Pn, d.S, False, kv_cache=d.cache, mod_shared=True)
-    pre1, _ = hip.rmsnorm_fwd(xf1, mod=model._mod_slot(mod, 2 * model.v.depth), rows_per_sample=d.S, save_rstd=False, mod_ld=0)
+    _, xf1, _ = llm_fwd(model, None, x1, mod, d.pos, d.qinfo, d.kinfo, d.B, d.Pn, d.S, False, kv_cache=d.cache, mod_shared=True)
+    pre1, _ = hip.rmsnorm_fwd(xf1, mod=mod_slot(model, mod, 2 * model.v.depth), rows_per_sample=d.S, save_rstd=False, mod_ld=0)
     _euler_f32(model, d, step, pre1)
 
 
@@ -191,12 +192,12 @@ def _sample_actions_pi0(model: LAP, obs, x_t, x0, Pn, infos, num_steps, collect)
     B, S, ad = x_t.shape
     Sx, We = S + 1, model.e.width
     cache = []
-    model._llm_fwd(x0, None, None, ppos, qinfo_p, kinfo_p, B, Pn, 0, False, cache_out=cache)
+    llm_fwd(model, x0, None, None, ppos, qinfo_p, kinfo_p, B, Pn, 0, False, cache_out=cache)
     dt = -1.0 / num_steps
     t, step = 1.0, 0
     while t >= -dt / 2:      # lap.py:669-674
         x1, _ = model._embed_suffix_pi0(x_t, torch.full((B,), t, dtype=torch.float32, device=model.device), obs.state, False)
-        _, xf1, _ = model._llm_fwd(None, x1, None, pos_all, qinfo_s, kinfo_all, B, Pn, Sx, False, kv_cache=cache)
+        _, xf1, _ = llm_fwd(model, None, x1, None, pos_all, qinfo_s, kinfo_all, B, Pn, Sx, False, kv_cache=cache)
         pre_all, _ = hip.rmsnorm_fwd(xf1, scale=model.F("llm/final_norm1"), save_rstd=False)
         pre1 = pre_all.view(B, Sx, We)[:, 1:].reshape(B * S, We).contiguous()
         v_t = model._lin32(hip.cast_bf16_to_f32(pre1), "act/out_w", "act/out_b")
@@ -218,7 +219,7 @@ def expert_denoise_partials(model: LAP, x1, mod, pos, qinfo, kinfo, B, Pn, S, ca
     Ttot = pos.shape[1]
     We = e.width
     scratch = hip._gemm_scratch(model.device)
-    slot = lambda j: model._mod_slot(mod, j)
+    slot = lambda j: mod_slot(model, mod, j)
     h, _ = hip.rmsnorm_fwd(x1, mod=slot(0), rows_per_sample=S, save_rstd=False, mod_ld=0)
     x = x1
     for l in range(v.depth):
@@ -245,7 +246,7 @@ def expert_denoise_skinny(model: LAP, x1, mod, qinfo, kinfo, B, Pn, S, cache, ro
     v, e = model.v, model.e
     NH, HD, KV = v.num_heads, v.head_dim, v.num_kv_heads
     We = e.width
-    slot = lambda j: model._mod_slot(mod, j)
+    slot = lambda j: mod_slot(model, mod, j)
     x = x1
     for l in range(v.depth):
         model.comm.wait_unit(f"llm{l}")

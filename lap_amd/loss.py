@@ -1,6 +1,6 @@
 """The loss heads of `LAP._loss_impl` (lap.py:209-301, 472-566): the language head (row selection, final norm, chunked cross
 entropy over the f32 table as two bf16 planes, and its backward), the action head, and the per-sample weight mixing of VQA /
-prediction / language-action samples.  `_loss_impl` keeps the schedule: streams, collectives and the hand-off to `_llm_bwd`.
+prediction / language-action samples.  `_loss_impl` keeps the schedule: streams, collectives and the hand-off to `joint_layers.llm_bwd`.
 The weights are read through the model (`W`, `F`, `G`, `ps`); `mix_sample_weights` is plain torch and runs on any device.
 """
 from __future__ import annotations
@@ -11,6 +11,7 @@ import torch
 
 from lap_amd import hip
 from lap_amd.config import VQA_DATASET_ID_MAP
+from lap_amd.joint_layers import mod_slot
 
 
 def vocab_chunks(R: int, V: int, cap_cols: int | None = None) -> list[tuple[int, int]]:
@@ -56,7 +57,7 @@ class LangHead(NamedTuple):
 
 class LossRows(NamedTuple):
     """Which rows the language head reads (`select_loss_rows`): chosen once per step, before the joint layers, so that the last
-    layer's prefix stream can run on these rows alone (LAP._llm_fwd `last_rows`)."""
+    layer's prefix stream can run on these rows alone (joint_layers.llm_fwd `last_rows`)."""
     lm: torch.Tensor                    # [B, Lt-1] loss mask, f32
     cnt: torch.Tensor                   # [B] max(sum(lm), 1)
     sel: torch.Tensor = None            # [B, Ls] selected rows in 0 .. Lt-2 (masked rows first, stable order, padded), or None: all
@@ -216,7 +217,7 @@ class ActionHead(NamedTuple):
 def action_head_fwd(model, xf1, mod, B, S, Sx, *, backward: bool) -> ActionHead:
     We = model.e.width
     if model.config.pi05:
-        pre1, rstd_p1 = hip.rmsnorm_fwd(xf1, mod=model._mod_slot(mod, 2 * model.v.depth), rows_per_sample=S, save_rstd=backward)
+        pre1, rstd_p1 = hip.rmsnorm_fwd(xf1, mod=mod_slot(model, mod, 2 * model.v.depth), rows_per_sample=S, save_rstd=backward)
     else:       # plain final norm; the action head reads the last S rows of each sample (`suffix_out[:, -ah:]`, lap.py:298)
         pre1_all, rstd_p1 = hip.rmsnorm_fwd(xf1, scale=model.F("llm/final_norm1"), save_rstd=backward)
         pre1 = pre1_all.view(B, Sx, We)[:, 1:].reshape(B * S, We).contiguous()
@@ -230,8 +231,8 @@ def action_head_bwd(model, head: ActionHead, xf1, mod, dv, B, S, Sx):
     dpre1f = model._lin32_bwd(head.pre1f, dv.view(B * S, -1), "act/out_w", "act/out_b")
     if model.config.pi05:
         dmod = torch.zeros(mod.shape, dtype=torch.float32, device=dev)
-        dx1 = hip.rmsnorm_bwd(xf1, hip.cast_f32_to_bf16(dpre1f), head.rstd_p1, mod=model._mod_slot(mod, 2 * model.v.depth), rows_per_sample=S,
-                              dmod=model._mod_slot(dmod, 2 * model.v.depth))
+        dx1 = hip.rmsnorm_bwd(xf1, hip.cast_f32_to_bf16(dpre1f), head.rstd_p1, mod=mod_slot(model, mod, 2 * model.v.depth), rows_per_sample=S,
+                              dmod=mod_slot(model, dmod, 2 * model.v.depth))
         return dx1, dmod
     dall = torch.zeros((B, Sx, We), dtype=torch.bfloat16, device=dev)      # (the state token's row of the final norm has no consumer)
     dall[:, 1:] = hip.cast_f32_to_bf16(dpre1f).view(B, S, We)

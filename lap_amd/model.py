@@ -4,9 +4,7 @@ Keeps the reference's model surface (src/lap/models/lap.py):
     compute_loss(rng, observation, actions, *, train=False, ...) -> (loss, metrics)      lap.py:380-602
     sample_actions(rng, observation, *, num_steps=10, noise=None) -> [b, ah, ad]         lap.py:605-675
 and adds `loss_and_grad(...)`, the fused forward + hand-written backward that the train step uses (the
-reference gets it from nnx.value_and_grad, scripts/train.py:358-361).  `_loss_impl` is the schedule of that step (streams, collectives,
-the order of the passes); the language head, the action head and the sample-weight mixing it calls are in lap_amd/loss.py.  The serving
-paths are modules of functions on the model: the action sampler in flow_sample.py, token decoding in ar_decode.py, their prefill in prefill.py.
+reference gets it from nnx.value_and_grad, scripts/train.py:358-361).
 
 Everything numeric is a call into liblap_hip.so (lap_amd/hip.py); torch only owns device memory, the stream,
 and a few O(batch x tokens) integer tensors (masks -> per-token info words, positions).  There is no autograd
@@ -14,16 +12,19 @@ and no fallback path.  Activations needed by the backward are kept in HBM (288 G
 recomputed — the reference rematerialises every block (gemma.py:418-423 nothing_saveable), which costs a
 fourth forward pass.
 
-Joint two-expert transformer (gemma.py:455-531): the prefix stream (SigLIP tokens + prompt, width of the VLM)
-and the suffix stream (action tokens, width of the action expert) keep separate activations and weights and
-meet only inside the attention kernel, which takes both as segments.  In the train step the suffix stream's kernels (1,600 rows:
-poorly filled grids, launch-latency bound) are issued on a second HIP stream and run under the prefix stream's GEMMs; the two
-streams synchronise before and after each layer's attention (`LAP_DUAL_STREAM=0`: everything on one stream).
+What is here: the switches (`LAP_*`, read in `__init__`), how the model reads a parameter and routes a product (`W` / `F` / `G`,
+`_wgrad` / `_bgrad`, the fp8 and LoRA routes, merged serving weights), the per-token info words, the two streams' embeddings with
+their backward, and `_loss_impl`, the schedule of the train step (streams, collectives, the order of the passes).  What it calls
+are modules of functions on the model:
+    joint_layers.py     the joint Gemma layers, forward and backward (both experts; the last layer's row subset)
+    siglip.py           the SigLIP training tower
+    streams.py          the suffix stream and its hand-offs, the weight-gradient stream (`model.wg`)
+    loss.py             the language head, the action head, the sample-weight mixing
+    flow_sample.py, ar_decode.py, prefill.py    the serving paths: action sampler, token decoding, their prefill
 """
 from __future__ import annotations
 
 import contextlib
-import dataclasses
 import math
 import os
 
@@ -31,11 +32,14 @@ import torch
 
 from lap_amd import hip
 from lap_amd.config import LAPConfig, get_gemma_config, get_siglip_config
+from lap_amd.joint_layers import last_layer_rows, llm_bwd, llm_fwd
 from lap_amd.loss import (ActionHead, LangHead, action_head_bwd, action_head_fwd, lang_head_bwd, lang_head_fwd, mix_sample_weights,
                           select_loss_rows)
 from lap_amd.observation import CoTObservation, preprocess_observation
 from lap_amd.params import LORA_PROJ, ParamStore, lora_geometry
 from lap_amd.serve_cache import ServeCache
+from lap_amd.siglip import siglip_bwd, siglip_fwd
+from lap_amd.streams import OffPathStream, handoff, suffix_stream
 
 SUFFIX_IDX_BASE = 0x800000  # suffix ar-indices live above every prefix index (see _train_infos)
 
@@ -57,21 +61,6 @@ def _gen(rng, device):
     g = torch.Generator(device=device)
     g.manual_seed(int(rng) if rng is not None else 0)
     return g
-
-
-class LastRows:
-    """The prefix rows the LAST joint layer keeps in a train step (`LAP._last_layer_rows`): those the language head reads."""
-
-    def __init__(self, sel, qinfo, B, n0, Lt):
-        dev, n_sel = sel.device, sel.shape[1]
-        self.n_sel = n_sel
-        idx = sel + (n0 - Lt)                                                       # [B, n_sel] prefix positions, the head's order
-        self.rowid = (torch.arange(B, device=dev)[:, None] * n0 + idx).to(torch.int32).reshape(-1).contiguous()   # rows of x0
-        self.inv = torch.full((B * n0,), -1, dtype=torch.int32, device=dev)         # row of x0 -> its compact row, or -1
-        self.inv[self.rowid.long()] = torch.arange(B * n_sel, dtype=torch.int32, device=dev)
-        # info words of the kept queries, then the suffix queries': class bits and ar index travel with the row, so every kept
-        # row meets the keys under the mask it had
-        self.qinfo = torch.cat([qinfo[:, :n0].gather(1, idx), qinfo[:, n0:]], 1).to(torch.int32).contiguous()
 
 
 class LAP:
@@ -107,7 +96,7 @@ class LAP:
         self.fuse_geglu_fwd = os.environ.get("LAP_FUSE_GEGLU_FWD", "1") != "0" and gemm_dtype != "fp8"
         self.fuse_gelu = os.environ.get("LAP_FUSE_GELU", "1") != "0"      # SigLIP MLP: GELU forward / backward inside the Dense GEMMs
         # train step: the last joint layer's prefix stream keeps K / V of every row but runs everything behind them on the rows the
-        # language head reads (`_last_layer_rows`).  LAP_LAST_LAYER_ROWS=0: all rows, as every other layer (A/B runs, tests)
+        # language head reads (`joint_layers.last_layer_rows`).  LAP_LAST_LAYER_ROWS=0: all rows, as every other layer (A/B runs, tests)
         self.last_layer_rows = os.environ.get("LAP_LAST_LAYER_ROWS", "1") != "0"
         self.last_rows_steps = 0      # passes that took the row-subset path (tests read it)
         # first denoise step on a second stream beside the prefill (it needs layer l's K / V only at its layer l).  Measured, hipGraph
@@ -147,17 +136,15 @@ class LAP:
         # prefill_down_sweep.py, us per GEMM + reduce / residual / norm): 256 x 256 x 8 65.0 | 320 x 128 (tile 19) x 8 60.8 | 320 x 256 x 16 64.5
         ks = os.environ.get("LAP_PREFILL_KS", "4,1,8,19").split(",")
         self._prefill_ks = tuple(int(k) for k in ks)
-        self._sfx = None        # the suffix stream's HIP stream (created on first use)
-        # which gradients leave the data-gradient path for a third stream (see _off_path): s SigLIP weights, b biases, q / g the
+        self.sfx = None         # the suffix stream's HIP stream (created on first use: streams.suffix_stream)
+        # which gradients leave the data-gradient path for a third stream (lap_amd/streams.py): s SigLIP weights, b biases, q / g the
         # prefix stream's attention / MLP projections; "1" all, "0" none.  Measured (tools/ab3.sh, interleaved on one box): sb
         # -2.1 .. -3.3 ms per step in round 2 and -2.6 ms in round 3 (310.0 -> 307.4), s -1.3, q 0, all +12.6.  Default "sb":
         # step time is the decision variable (the compute stream's GEMMs then share the chip, so their EVENT-timed rate drops
         # by 4 % — bench.py's roofline figure is computed from isolated per-shape times for that reason).
         mode = os.environ.get("LAP_WGRAD_STREAM", "sb")
         self.wgrad_stream = "" if mode == "0" else mode
-        self._wg = self._wg_obj = self._wg_main = None
-        self._wg_dirty = False
-        self._wg_ev: dict = {}
+        self.wg = OffPathStream(self.device)
         # LoRA adapters (config.GemmaConfig.lora_attn / lora_ffn): projection key ("wgu0", ...) -> (G, nsum, s), see params.lora_geometry.
         # Training keeps base and adapters apart (csrc/lora.hip); the serving paths run on merged weights (`_serving_weights`)
         self._lora_geo = {}
@@ -177,28 +164,6 @@ class LAP:
                 raise ValueError(f"gemm_dtype='fp8' needs projection dimensions that are multiples of 128, got {dims}")
 
     # ------------------------------------------------------------------ small helpers
-    def _suffix_stream(self, *tensors):
-        """The second HIP stream for the suffix (action-expert) side of a joint layer loop, or None when both streams of
-        activations go down the current one (one of them absent, CPU tensors, stream capture, LAP_DUAL_STREAM=0).  It starts
-        behind everything the current stream has been given so far; `tensors` are marked as used on it."""
-        if not self.dual_stream or any(t is None or not t.is_cuda for t in tensors) or torch.cuda.is_current_stream_capturing():
-            return None
-        if self._sfx is None:
-            self._sfx = torch.cuda.Stream(self.device, priority=-1)   # short kernels: never let them queue behind a full grid
-        self._sfx.wait_stream(torch.cuda.current_stream())
-        for t in tensors:
-            t.record_stream(self._sfx)
-        return self._sfx
-
-    @staticmethod
-    def _handoff(src, dst, *tensors):
-        """`dst` waits for what `src` has been given so far; `tensors` (allocated on src) are about to be used on dst."""
-        if src is not None and dst is not None:
-            dst.wait_stream(src)
-            for t in tensors:
-                if t is not None:
-                    t.record_stream(dst)
-
     def W(self, name):
         if self._merge_depth and name.rsplit("/", 1)[-1] in self._lora_geo:
             return self._merged(name)
@@ -225,7 +190,7 @@ class LAP:
                 else:
                     hip.linear_wgrad(dy, x, self.G(name), **kw)
             if mode == "1" or kind in mode:
-                with self._off_path(dy, x):
+                with self.wg.run(dy, x):
                     run()
             else:
                 run()
@@ -234,62 +199,10 @@ class LAP:
         """Bias gradient = column sums of dy, next to the weight gradient."""
         mode = self.wgrad_stream
         if mode == "1" or "b" in mode:
-            with self._off_path(dy):
+            with self.wg.run(dy):
                 hip.colsum(dy, self.G(name))
         else:
             hip.colsum(dy, self.G(name))
-
-    # Nothing in the backward waits for a weight / bias gradient except the optimizer, so the prefix stream's and SigLIP's are
-    # issued on a third HIP stream: the data-gradient chain (the critical path) keeps the compute stream, and the weight-gradient
-    # GEMMs fill the CUs its poorly filled last rounds leave idle.  The compute stream joins before it updates a dy in place and
-    # before a unit's gradients are declared complete.  (LAP_WGRAD_STREAM=0: inline.)
-    @contextlib.contextmanager
-    def _off_path(self, *tensors):
-        wg = self._wg
-        cur = torch.cuda.current_stream()
-        if wg is None or cur != self._wg_main:
-            yield
-            return
-        wg.wait_stream(self._wg_main)
-        for t in tensors:
-            t.record_stream(wg)
-        with torch.cuda.stream(wg):
-            yield
-        ev = torch.cuda.Event()
-        ev.record(wg)
-        self._wg_ev.setdefault(tensors[0].data_ptr(), []).append(ev)     # keyed by dy: the tensor the path may rewrite
-        self._wg_dirty = True
-
-    def _wg_join(self, dy=None):
-        """The compute stream waits for the off-path readers of `dy` (about to be updated in place), or for all of them."""
-        if self._wg is None or not self._wg_dirty or torch.cuda.current_stream() != self._wg_main:
-            return
-        if dy is not None:
-            for ev in self._wg_ev.pop(dy.data_ptr(), ()):
-                self._wg_main.wait_event(ev)
-        else:
-            self._wg_main.wait_stream(self._wg)
-            self._wg_ev.clear()
-            self._wg_dirty = False
-
-    def _unit_done(self, name, sfx=None):
-        """comm.grads_ready for a unit whose gradients may still be in flight on the second (`sfx`) or third stream: the
-        communication / optimizer stream waits for those too, the compute stream does not."""
-        also = [sfx] if sfx is not None else []
-        if self._wg is not None and self._wg_dirty and torch.cuda.current_stream() == self._wg_main:
-            also.append(self._wg)
-        self.comm.grads_ready(name, also=also or None)
-
-    def _wg_begin(self):
-        """Start of a backward pass on the current stream: weight gradients go off the path from here on."""
-        if self.wgrad_stream and self.device.type == "cuda" and not torch.cuda.is_current_stream_capturing():
-            if self._wg_obj is None:
-                self._wg_obj = torch.cuda.Stream(self.device)
-            self._wg, self._wg_main, self._wg_dirty = self._wg_obj, torch.cuda.current_stream(), False
-
-    def _wg_end(self):
-        self._wg_join()
-        self._wg = None
 
     # ---- LoRA adapters (lora.Einsum / lora.FeedForward, gemma.py:180-200,279-285,366-372; csrc/lora.hip)
     def _lora(self, name):
@@ -334,7 +247,7 @@ class LAP:
                 hip.lora_wgrad(t, dy, self.G(nb), G=G, bg=Ng if G > 1 else 0, ncopy=nsum, s=s)
         mode = self.wgrad_stream
         if mode == "1" or ("q" if key in ("wqkv0", "wo0") else "g") in mode:
-            with self._off_path(dy, x, t, dt):
+            with self.wg.run(dy, x, t, dt):
                 run()
         else:
             run()
@@ -388,18 +301,6 @@ class LAP:
             return hip.add_bf16(residual, hip.linear_fwd(x, self.W(name)))
         return hip.linear_fwd(x, self.W(name), out, residual=residual, tile=tile)
 
-    def _rows_res_tile(self, x, name):
-        """Tile request for the out / down projection (+ residual) of the last layer's row subset: 14, the assembly residual kernel
-        the other layers' out / down products run on, where the library takes the shape (M a multiple of 256) and no A/B switch has
-        the assembly routes off; else -1, the planner's choice.  Left to itself the planner's fill rule sends the 16 tiles of
-        512 x 2048 to the HIP tiles: the step's out / down products would no longer all be the one kernel."""
-        if os.environ.get("LAP_GEMM_NO_ASM") is not None or os.environ.get("LAP_GEMM_NO_ASM_RES") is not None or \
-                os.environ.get("LAP_UNFUSED_RESIDUAL", "0") == "1":
-            return -1
-        w = self.W(name)
-        ok = hip._lib.lap_gemm_asm_res_ok(0, x.shape[0], w.shape[0], x.shape[1], x.stride(0), w.stride(0), w.shape[0])
-        return 14 if ok and x.stride(1) == 1 else -1
-
     def _dgrad0(self, dy, name):
         """dx = dy @ Wt for a prefix-stream projection (the fp8 route multiplies by the transposed fp8 copy)."""
         if self.gemm_dtype == "fp8":
@@ -436,138 +337,6 @@ class LAP:
         dx = torch.empty_like(x)
         return hip.gemm_f32(dy, w, dx, M=x.shape[0], N=w.shape[1], K=w.shape[0], lda=dy.stride(0), ldb=w.stride(0), ldc=w.shape[1],
                             a_kc=True, b_kc=False)
-
-    # ================================================================== SigLIP
-    def _siglip_fwd(self, images: torch.Tensor, save: bool, collect=None, x_in=None, blocks=None):
-        """images f32 [N,H,W,3] -> tokens bf16 [N*T, Dv].  openpi siglip (missing) restated in
-        siglip_gemma3.py:382-545 minus :432, plus head bias.
-        Test hook (teacher-forced per-block parity): with `x_in` (bf16 [N*T, W]) the stem is skipped, only `blocks` run
-        and the block output is returned instead of the projected tokens."""
-        s, T = self.s, self.n_img_tok
-        W = s.width
-        hd = W // s.num_heads
-        ctx = {"blocks": []} if save else None
-        if x_in is not None:
-            x, N = x_in, x_in.shape[0] // T
-            for l in blocks:
-                x = self._siglip_block(l, x, N, T, W, hd, None, False)
-            return x, None
-        N = images.shape[0]
-        x, patches = self._siglip_stem(images)
-        if collect is not None:
-            collect["img/stem"] = x
-        if save:
-            ctx["patches"] = patches
-        for l in range(s.depth):
-            x = self._siglip_block(l, x, N, T, W, hd, ctx, save)
-            if collect is not None:
-                collect[f"img/block{l:02d}"] = x
-        self.comm.wait_unit("img_head")
-        enc, mean, rstd = hip.layernorm_fwd(x, self.F("img/norm_g"), self.F("img/norm_b"))
-        tok = hip.linear_fwd(enc, self.W("img/head_w"), bias=self.F("img/head_b"))
-        if save:
-            ctx["final"] = (x, enc, mean, rstd)
-        if collect is not None:
-            collect["img/out"] = tok
-        return tok, ctx
-
-    def _siglip_stem(self, images: torch.Tensor):
-        """f32 stem (siglip_gemma3.py:398-408) on the MFMA path -> (x bf16 [N*T, W], the (hi, lo) patches its weight gradient reads):
-        x = hi + lo (2 x bf16, 16 mantissa bits), products exact in the f32 accumulator, the lo.lo term (2^-18 relative) dropped."""
-        p_hi, p_lo = hip.split_f32_hilo(hip.im2col_patch(images.contiguous(), self.s.patch))
-        w_hi, w_lo = hip.split_f32_hilo(self.F("img/stem_w"))
-        (R, Kp), W = p_hi.shape, self.s.width
-        stem = torch.empty((R, W), dtype=torch.float32, device=p_hi.device)
-        hip.gemm(p_hi, w_hi, stem, M=R, N=W, K=Kp, lda=Kp, ldb=Kp, ldc=W, bias=self.F("img/stem_b"))
-        hip.gemm(p_hi, w_lo, stem, M=R, N=W, K=Kp, lda=Kp, ldb=Kp, ldc=W, accum=True)
-        hip.gemm(p_lo, w_hi, stem, M=R, N=W, K=Kp, lda=Kp, ldb=Kp, ldc=W, accum=True)
-        return hip.add_posemb_cast(stem, self.F("img/pos"), self.n_img_tok), (p_hi, p_lo)
-
-    def _siglip_block(self, l, x, N, T, W, hd, ctx, save):
-        """One pre-LN encoder block (siglip_gemma3.py:59-167): x + MHA(LN(x)), then + MLP(LN(.))."""
-        s = self.s
-        self.comm.wait_unit(f"img{l}")
-        p = f"img/{l}/"
-        y, mean1, rstd1 = hip.layernorm_fwd(x, self.F(p + "ln1_g"), self.F(p + "ln1_b"))
-        qkv = hip.linear_fwd(y, self.W(p + "wqkv"), bias=self.F(p + "bqkv"))
-        (o, _), lse = hip.attention_fwd([qkv[:, :W]], [qkv[:, W:2 * W]], [qkv[:, 2 * W:]], [T], [T], N, s.num_heads, s.num_heads, hd,
-                                        scale=hd ** -0.5, q_rs=(3 * W, 0), kv_rs=(3 * W, 0), need_lse=save)
-        x1 = hip.linear_fwd(o, self.W(p + "wo"), bias=self.F(p + "bo"), residual=x)
-        y2, mean2, rstd2 = hip.layernorm_fwd(x1, self.F(p + "ln2_g"), self.F(p + "ln2_b"))
-        self.comm.pace(f"img{l}")
-        if save:
-            if self.fuse_gelu and hip.linear_bias_gelu_train_ok(y2, self.W(p + "w1"), self.F(p + "b1")):
-                h, a = hip.linear_bias_gelu_train(y2, self.W(p + "w1"), self.F(p + "b1"))     # fc1 + bias with the GELU in its epilogue
-            else:
-                h = hip.linear_fwd(y2, self.W(p + "w1"), bias=self.F(p + "b1"))
-                a = hip.gelu_fwd(h)
-        else:   # nothing keeps the pre-activation: GELU in the GEMM epilogue, after the bf16 rounding of the Dense output (same bits)
-            h, a = None, hip.linear_fwd(y2, self.W(p + "w1"), bias=self.F(p + "b1"), gelu="bf16")
-        x2 = hip.linear_fwd(a, self.W(p + "w2"), bias=self.F(p + "b2"), residual=x1)
-        if save:
-            ctx["blocks"].append((x, y, mean1, rstd1, qkv, o, lse, x1, y2, mean2, rstd2, h, a))
-        return x2
-
-    def _siglip_bwd(self, ctx, dtok: torch.Tensor):
-        s, T = self.s, self.n_img_tok
-        W = s.width
-        hd = W // s.num_heads
-        x, enc, mean, rstd = ctx["final"]
-        N = x.shape[0] // T
-        self._bgrad(dtok, "img/head_b")
-        self._wgrad(dtok, enc, "img/head_w")
-        denc = hip.linear_dgrad(dtok, self.W("img/head_w"))
-        self._unit_done("img_head")
-        # Bias gradients = column sums of a dy.  Two of a block's four (fc2's and the out projection's) come out of the LayerNorm
-        # backward that PRODUCES that dy instead of a pass of their own over 38 MB (+1.8 us in that kernel against a 15.5 us
-        # column-sum launch; a GELU backward that sums its columns was 2.3 x slower than the two kernels it replaced).
-        fuse_b = os.environ.get("LAP_FUSE_BGRAD", "1") != "0"
-        last = s.depth - 1
-        dx = hip.layernorm_bwd(x, denc, self.F("img/norm_g"), mean, rstd, self.G("img/norm_g"), self.G("img/norm_b"),
-                               dxsum=self.G(f"img/{last}/b2") if fuse_b else None)
-        for l in reversed(range(s.depth)):
-            p = f"img/{l}/"
-            x, y, mean1, rstd1, qkv, o, lse, x1, y2, mean2, rstd2, h, a = ctx["blocks"][l]
-            if not fuse_b:
-                self._bgrad(dx, p + "b2")
-            self._wgrad(dx, a, p + "w2")
-            if self.fuse_gelu and hip.dgrad_gelu_bwd_ok(dx, self.W(p + "w2"), h):
-                dh = hip.linear_dgrad_gelu_bwd(dx, self.W(p + "w2"), h)      # fc2's data gradient with the GELU backward as its epilogue
-            else:
-                da = hip.linear_dgrad(dx, self.W(p + "w2"))
-                dh = hip.gelu_bwd(h, da)
-                del da
-            self._bgrad(dh, p + "b1")
-            self._wgrad(dh, y2, p + "w1")
-            dy2 = hip.linear_dgrad(dh, self.W(p + "w1"))
-            del dh
-            self._wg_join(dx)    # (the fc2 weight / bias gradients read dx)
-            hip.layernorm_bwd(x1, dy2, self.F(p + "ln2_g"), mean2, rstd2, self.G(p + "ln2_g"), self.G(p + "ln2_b"), dx=dx, accum_dx=True,
-                              dxsum=self.G(p + "bo") if fuse_b else None)
-            if not fuse_b:
-                self._bgrad(dx, p + "bo")
-            self._wgrad(dx, o, p + "wo")
-            do = hip.linear_dgrad(dx, self.W(p + "wo"))
-            dqkv = torch.empty_like(qkv)
-            hip.attention_bwd([qkv[:, :W]], [qkv[:, W:2 * W]], [qkv[:, 2 * W:]], [o], [do], lse, [T], [T], N, s.num_heads, s.num_heads, hd,
-                              scale=hd ** -0.5, q_rs=(3 * W, 0), kv_rs=(3 * W, 0),
-                              dq_out=[dqkv[:, :W]], dk_out=[dqkv[:, W:2 * W]], dv_out=[dqkv[:, 2 * W:]])
-            self._bgrad(dqkv, p + "bqkv")
-            self._wgrad(dqkv, y, p + "wqkv")
-            dy = hip.linear_dgrad(dqkv, self.W(p + "wqkv"))
-            self._wg_join(dx)    # (the out-projection's read dx)
-            hip.layernorm_bwd(x, dy, self.F(p + "ln1_g"), mean1, rstd1, self.G(p + "ln1_g"), self.G(p + "ln1_b"), dx=dx, accum_dx=True,
-                              dxsum=self.G(f"img/{l - 1}/b2") if (fuse_b and l > 0) else None)
-            ctx["blocks"][l] = None
-            self._unit_done(f"img{l}")
-        dstem = hip.add_posemb_cast_bwd(dx, self.G("img/pos"), T)     # f32 copy of a bf16 gradient: exact in bf16
-        p_hi, p_lo = ctx["patches"]
-        gw = self.G("img/stem_w")
-        tmp = torch.empty((gw.shape[0], p_hi.shape[1]), dtype=torch.float32, device=gw.device)   # [W, 592]
-        hip.linear_wgrad(dx, p_hi, tmp)
-        hip.linear_wgrad(dx, p_lo, tmp, accum=True)
-        gw.add_(tmp[:, :gw.shape[1]])
-        hip.colsum(dstem, self.G("img/stem_b"))
 
     # ================================================================== token info words / positions
     def _prefix_masks(self, obs: CoTObservation):
@@ -643,7 +412,7 @@ class LAP:
         Pn = T * len(keys) + Lt
         images = torch.cat([obs.images[k] for k in keys], 0)
         fused = tower is not None and self.serve_fusions and not save and collect is None
-        tok, ictx = (tower(self, images), None) if fused else self._siglip_fwd(images, save, collect)
+        tok, ictx = (tower(self, images), None) if fused else siglip_fwd(self, images, save, collect)
         x0 = torch.empty((B * Pn, Dv), dtype=torch.bfloat16, device=self.device)
         for i in range(len(keys)):
             hip.copy_rows_bf16(tok[i * B * T:(i + 1) * B * T], x0, B * T, T, Dv, T, 0, Pn, i * T)
@@ -665,7 +434,7 @@ class LAP:
         dtok = torch.empty((len(keys) * B * T, Dv), dtype=torch.bfloat16, device=self.device)
         for i in range(len(keys)):
             hip.copy_rows_bf16(dx0, dtok[i * B * T:(i + 1) * B * T], B * T, T, Dv, Pn, i * T, T, 0)
-        self._siglip_bwd(ictx, dtok)
+        siglip_bwd(self, ictx, dtok)
 
     def _time_mod(self, time: torch.Tensor, save: bool):
         """[UPSTREAM-RECALL] openpi Pi0.embed_suffix (pi05), time branch: posemb_sincos -> time_mlp_in -> swish ->
@@ -717,8 +486,8 @@ class LAP:
 
     def _embed_suffix(self, x_t: torch.Tensor, time: torch.Tensor, save: bool, overlap: bool = False):
         """overlap (train step): the dozen small kernels go to the second HIP stream and run under whatever the current stream was
-        given before (the SigLIP tower); their results are next touched by `_llm_fwd`, which joins the streams."""
-        sfx = self._suffix_stream(x_t, time) if overlap else None
+        given before (the SigLIP tower); their results are next touched by `joint_layers.llm_fwd`, which joins the streams."""
+        sfx = suffix_stream(self, x_t, time) if overlap else None
         self.comm.wait_unit("ada", also=sfx)
         with (torch.cuda.stream(sfx) if sfx is not None else contextlib.nullcontext()):
             x1, xt2 = self._embed_actions(x_t)
@@ -731,7 +500,7 @@ class LAP:
         """On the second HIP stream when there is one: it runs under the SigLIP backward that the caller issues next.  The
         caller joins the streams before it declares the "small" unit's gradients complete."""
         xt2, temb, h1, s1, h2, cond16 = sctx
-        sfx = self._suffix_stream(dx1, dmod)
+        sfx = suffix_stream(self, dx1, dmod)
         with (torch.cuda.stream(sfx) if sfx is not None else contextlib.nullcontext()):
             dmod16 = hip.cast_f32_to_bf16(dmod)
             hip.colsum(dmod, self.G("ada/b"))
@@ -744,245 +513,6 @@ class LAP:
             self._lin32_bwd(temb, dh1, "act/time_in_w", "act/time_in_b", need_dx=False)
             self._lin32_bwd(xt2, hip.cast_bf16_to_f32(dx1), "act/in_w", "act/in_b", need_dx=False)
         return sfx
-
-    # ================================================================== joint Gemma layers
-    def _mod_slot(self, mod, slot):
-        W3 = 3 * self.e.width
-        return mod[:, slot * W3:(slot + 1) * W3]
-
-    def _last_layer_rows(self, lr, qinfo, B, n0, Lt, *, save, x1, collect, verbose):
-        """The row subset of the last layer's prefix stream, or None: every row.  Nothing behind the last layer's K / V reads a
-        prefix row but the language head, and it reads `lr.sel`'s rows only (16 of 560 per sample at the benchmark's shapes), so
-        in a train step Q, the attention output, the out projection, the FFN and their backward run on those rows alone.
-        Anything that looks at the layer's other rows (`collect`, the per-layer hooks, eval, serving) or runs products this
-        path has no route for (fp8, LoRA) keeps all rows; so does a step without a row selection or with a frozen prefix."""
-        if not (self.last_layer_rows and save and x1 is not None and collect is None and not verbose and lr is not None
-                and lr.sel is not None and self.gemm_dtype == "bf16" and not self._prefix_frozen()):
-            return None
-        p = f"llm/{self.v.depth - 1}/"
-        if any(self._lora(p + k) is not None for k in ("wqkv0", "wo0", "wgu0", "wd0")):
-            return None
-        return LastRows(lr.sel, qinfo, B, n0, Lt)
-
-    def _llm_fwd(self, x0, x1, mod, pos, qinfo, kinfo, B, n0, n1, save: bool, kv_cache=None, cache_out=None, collect=None,
-                 mod_shared: bool = False, layers=None, last_rows=None):
-        """gemma.Module.__call__ layers (gemma.py:336-387,167-290).  x0 [B*n0, Dv] or None, x1 [B*n1, De] or None.
-        kv_cache: per-layer (k, v) of the prefix used as key segment 0 when x0 is None (serving).
-        last_rows (`_last_layer_rows`): the last layer's prefix stream is compact behind K / V, and so is the x0 returned.
-        Returns final pre-norm activations and the saved context."""
-        v, e = self.v, self.e
-        NH, HD, KV = v.num_heads, v.head_dim, v.num_kv_heads
-        Ttot = pos.shape[1]
-        ctx = [] if save else None
-        mld = 0 if mod_shared else (mod.stride(0) if mod is not None else 0)  # 0: one modulation row for every sample
-        sfx = self._suffix_stream(*([x1, mod] if mod is not None else [x1])) if (x0 is not None and x1 is not None) else None
-        main = torch.cuda.current_stream() if sfx is not None else None
-        on_sfx = (lambda: torch.cuda.stream(sfx)) if sfx is not None else contextlib.nullcontext
-        if last_rows is not None and not (save and x0 is not None and x1 is not None and layers is None and collect is None):
-            raise ValueError("_llm_fwd: last_rows goes with a saved two-stream pass over all layers without `collect`")
-        for l in (range(v.depth) if layers is None else layers):    # `layers`: test hook (teacher-forced per-layer parity)
-            self.comm.wait_unit(f"llm{l}", also=sfx)
-            p = f"llm/{l}/"
-            rows0 = last_rows if l == v.depth - 1 else None
-            q = [None, None]; k = [None, None]; vv = [None, None]; h = [None, None]; rstd_a = [None, None]
-            lt = [{}, {}]       # LoRA down products t per stream and projection (kept for the backward)
-            if x0 is not None:
-                h[0], rstd_a[0] = hip.rmsnorm_fwd(x0, scale=self.F(p + "n_attn"), save_rstd=save)
-                qkv = self._lin0(h[0], p + "wqkv0")
-                lt[0]["wqkv"] = self._lora_fwd(h[0], qkv, p + "wqkv0")
-                if rows0 is None:
-                    q[0], k[0], vv[0] = hip.rope_split_fwd(qkv, pos, B, n0, Ttot, 0, NH, HD, HD ** -0.5)
-                else:   # K / V of every row, Q of the kept rows
-                    q[0], k[0], vv[0] = hip.rope_split_fwd(qkv, pos, B, n0, Ttot, 0, NH, HD, HD ** -0.5, q_row=rows0.inv,
-                                                           q_rows=B * rows0.n_sel)
-                del qkv
-            elif kv_cache is not None:
-                k[0], vv[0] = kv_cache[l]
-            if x1 is not None:
-                with on_sfx():
-                    if mod is None:     # pi0: plain RMSNorm in the expert (`use_adarms=[False, False]`, lap.py:51)
-                        h[1], rstd_a[1] = hip.rmsnorm_fwd(x1, scale=self.F(p + "n_attn1"), save_rstd=save)
-                    else:
-                        h[1], rstd_a[1] = hip.rmsnorm_fwd(x1, mod=self._mod_slot(mod, 2 * l), rows_per_sample=n1, save_rstd=save, mod_ld=mld)
-                    qkv = hip.linear_fwd(h[1], self.W(p + "wqkv1"))
-                    lt[1]["wqkv"] = self._lora_fwd(h[1], qkv, p + "wqkv1")
-                    q[1], k[1], vv[1] = hip.rope_split_fwd(qkv, pos, B, n1, Ttot, Ttot - n1, NH, HD, HD ** -0.5)
-                    del qkv
-                self._handoff(sfx, main, q[1], k[1], vv[1])
-            if cache_out is not None:
-                cache_out.append((k[0], vv[0]))
-            qlen = [n0 if x0 is not None else 0, n1 if x1 is not None else 0]
-            klen = [k[0].shape[0] // B if k[0] is not None else 0, n1 if x1 is not None else 0]
-            xfull = x0
-            if rows0 is not None:     # a query segment shorter than its key segment, as serving runs it against a cached prefix
-                qlen[0] = rows0.n_sel
-                x0 = hip.gather_rows_bf16(x0, rows0.rowid)      # the residual operand of the out projection, its only other reader
-                self.last_rows_steps += 1
-            o, lse = hip.attention_fwd(q, k, vv, qlen, klen, B, NH, KV, HD, qinfo if rows0 is None else rows0.qinfo, kinfo, need_lse=save)
-            self._handoff(main, sfx, o[1])
-            xa = [None, None]; y1 = None; hf = [None, None]; rstd_f = [None, None]; gu = [None, None]; act = [None, None]; y1f = None
-            xn = [None, None]
-            if x1 is not None and mod is None:       # pi0: plain residuals (gemma.py:577-583 with gate None)
-                with on_sfx():
-                    xa[1] = hip.linear_fwd(o[1], self.W(p + "wo1"), residual=x1)
-                    lt[1]["wo"] = self._lora_fwd(o[1], xa[1], p + "wo1")
-                    hf[1], rstd_f[1] = hip.rmsnorm_fwd(xa[1], scale=self.F(p + "n_ffw1"), save_rstd=save)
-                    gu[1] = hip.linear_fwd(hf[1], self.W(p + "wgu1"))
-                    lt[1]["wgu"] = self._lora_fwd(hf[1], gu[1], p + "wgu1")
-                    act[1] = hip.geglu_fwd(gu[1])
-                    xn[1] = hip.linear_fwd(act[1], self.W(p + "wd1"), residual=xa[1])
-                    lt[1]["wd"] = self._lora_fwd(act[1], xn[1], p + "wd1")
-            elif x1 is not None:     # (issued first: 8 short kernels that then run under the prefix stream's GEMMs)
-                with on_sfx():
-                    y1 = hip.linear_fwd(o[1], self.W(p + "wo1"))
-                    lt[1]["wo"] = self._lora_fwd(o[1], y1, p + "wo1")
-                    xa[1] = hip.gated_residual_fwd(x1, y1, self._mod_slot(mod, 2 * l)[:, 2 * e.width:], n1, mld)
-                    hf[1], rstd_f[1] = hip.rmsnorm_fwd(xa[1], mod=self._mod_slot(mod, 2 * l + 1), rows_per_sample=n1, save_rstd=save, mod_ld=mld)
-                    gu[1] = hip.linear_fwd(hf[1], self.W(p + "wgu1"))
-                    lt[1]["wgu"] = self._lora_fwd(hf[1], gu[1], p + "wgu1")
-                    act[1] = hip.geglu_fwd(gu[1])
-                    y1f = hip.linear_fwd(act[1], self.W(p + "wd1"))
-                    lt[1]["wd"] = self._lora_fwd(act[1], y1f, p + "wd1")
-                    xn[1] = hip.gated_residual_fwd(xa[1], y1f, self._mod_slot(mod, 2 * l + 1)[:, 2 * e.width:], n1, mld)
-            if x0 is not None:
-                xa[0] = self._lin0(o[0], p + "wo0", residual=x0, tile=-1 if rows0 is None else self._rows_res_tile(o[0], p + "wo0"))
-                lt[0]["wo"] = self._lora_fwd(o[0], xa[0], p + "wo0")
-                hf[0], rstd_f[0] = hip.rmsnorm_fwd(xa[0], scale=self.F(p + "n_ffw"), save_rstd=save)
-                self.comm.pace(f"llm{l}")     # optimizer units released here start under the longest MFMA-bound GEMM of the layer
-                if save and self.fuse_geglu_fwd and self._lora(p + "wgu0") is None and hip.linear_geglu_train_ok(hf[0], self.W(p + "wgu0")):
-                    # gate | up projection with the GeGLU in its epilogue: gu (kept for the backward pass) and act leave one launch
-                    gu[0], act[0] = hip.linear_geglu_train(hf[0], self.W(p + "wgu0"))
-                else:
-                    gu_out = None
-                    if save and self.fuse_geglu_bwd:    # rows padded like d(gate | up): the fused backward kernel shares one row stride
-                        gu_out = hip._padded_rows(hf[0].shape[0], 2 * v.mlp_dim, hf[0].device, hip._row_pad(2 * v.mlp_dim))
-                    gu[0] = self._lin0(hf[0], p + "wgu0", out=gu_out)
-                    lt[0]["wgu"] = self._lora_fwd(hf[0], gu[0], p + "wgu0")   # (before the GeGLU: lora.FeedForward's _dot)
-                    act[0] = hip.geglu_fwd(gu[0], pad=self.gemm_dtype != "fp8")
-                xn[0] = self._lin0(act[0], p + "wd0", residual=xa[0], tile=-1 if rows0 is None else self._rows_res_tile(act[0], p + "wd0"))
-                lt[0]["wd"] = self._lora_fwd(act[0], xn[0], p + "wd0")
-            if save:
-                ctx.append(dict(x=[xfull, x1], h=h, rstd_a=rstd_a, q=q, k=k, v=vv, o=o, lse=lse, xa=xa, y1=y1, hf=hf, rstd_f=rstd_f,
-                                gu=gu, act=act, y1f=y1f, lt=lt))
-            x0, x1 = xn
-            if collect is not None:
-                collect[f"llm/layer{l:02d}/x0"], collect[f"llm/layer{l:02d}/x1"] = x0, x1
-        self._handoff(sfx, main, x1)
-        return x0, x1, ctx
-
-    def _llm_bwd(self, ctx, dx0, dx1, mod, dmod, pos, qinfo, kinfo, B, n0, n1, last_rows=None):
-        """last_rows: as in `_llm_fwd` — dx0 arrives with the kept rows only and leaves the last layer with all of them."""
-        v, e = self.v, self.e
-        NH, HD, KV = v.num_heads, v.head_dim, v.num_kv_heads
-        Ttot = pos.shape[1]
-        has_sfx = dx1 is not None         # False: prefix-only backward (enable_action_training=False, lap.py:449-455)
-        ada = has_sfx and mod is not None  # False with a suffix stream: pi0 (plain norms and residuals in the expert)
-        ldm = mod.stride(0) if ada else 0
-        zero_do0 = None
-        sfx = self._suffix_stream(*([dx1, dmod, mod] if ada else [dx1]))
-        main = torch.cuda.current_stream() if sfx is not None else None
-        on_sfx = (lambda: torch.cuda.stream(sfx)) if sfx is not None else contextlib.nullcontext
-        for l in reversed(range(v.depth)):
-            p = f"llm/{l}/"
-            c = ctx[l]
-            d_o = [None, None]
-            rows0 = last_rows if l == v.depth - 1 else None
-            # ---- FFN + attention output, suffix stream: xn = xa + y1f * gate_f  (on the second HIP stream, see the module doc)
-            slot_f, slot_a = 2 * l + 1, 2 * l
-            if has_sfx and not ada:
-                with on_sfx():      # xn = xa + act wd^T, xa = x + o wo^T: the residuals pass dx1 through, the norms add onto it in place
-                    self._wgrad(dx1, c["act"][1], p + "wd1")
-                    dact = hip.linear_dgrad(dx1, self.W(p + "wd1"))
-                    self._lora_bwd(dx1, c["act"][1], c["lt"][1].get("wd"), dact, p + "wd1")
-                    dgu = hip.geglu_bwd(c["gu"][1], dact)
-                    self._wgrad(dgu, c["hf"][1], p + "wgu1")
-                    dhf = hip.linear_dgrad(dgu, self.W(p + "wgu1"))
-                    self._lora_bwd(dgu, c["hf"][1], c["lt"][1].get("wgu"), dhf, p + "wgu1")
-                    hip.rmsnorm_bwd(c["xa"][1], dhf, c["rstd_f"][1], scale=self.F(p + "n_ffw1"), dx=dx1, dscale=self.G(p + "n_ffw1"), accum_dx=True)
-                    self._wgrad(dx1, c["o"][1], p + "wo1")
-                    d_o[1] = hip.linear_dgrad(dx1, self.W(p + "wo1"))
-                    self._lora_bwd(dx1, c["o"][1], c["lt"][1].get("wo"), d_o[1], p + "wo1")
-                    del dact, dgu, dhf
-            elif has_sfx:
-                with on_sfx():
-                    gate_f = self._mod_slot(mod, slot_f)[:, 2 * e.width:]
-                    dy1f = hip.gated_residual_bwd(dx1, c["y1f"], gate_f, n1, ldm, self._mod_slot(dmod, slot_f)[:, 2 * e.width:], dmod.stride(0))
-                    self._wgrad(dy1f, c["act"][1], p + "wd1")
-                    dact = hip.linear_dgrad(dy1f, self.W(p + "wd1"))
-                    self._lora_bwd(dy1f, c["act"][1], c["lt"][1].get("wd"), dact, p + "wd1")
-                    dgu = hip.geglu_bwd(c["gu"][1], dact)
-                    self._wgrad(dgu, c["hf"][1], p + "wgu1")
-                    dhf = hip.linear_dgrad(dgu, self.W(p + "wgu1"))
-                    self._lora_bwd(dgu, c["hf"][1], c["lt"][1].get("wgu"), dhf, p + "wgu1")
-                    hip.rmsnorm_bwd(c["xa"][1], dhf, c["rstd_f"][1], mod=self._mod_slot(mod, slot_f), rows_per_sample=n1, dx=dx1,
-                                    dmod=self._mod_slot(dmod, slot_f), accum_dx=True)
-                    gate_a = self._mod_slot(mod, slot_a)[:, 2 * e.width:]
-                    dy1 = hip.gated_residual_bwd(dx1, c["y1"], gate_a, n1, ldm, self._mod_slot(dmod, slot_a)[:, 2 * e.width:], dmod.stride(0))
-                    self._wgrad(dy1, c["o"][1], p + "wo1")
-                    d_o[1] = hip.linear_dgrad(dy1, self.W(p + "wo1"))
-                    self._lora_bwd(dy1, c["o"][1], c["lt"][1].get("wo"), d_o[1], p + "wo1")
-                    del dy1f, dact, dgu, dhf, dy1
-            # ---- FFN, prefix stream: xn = xa + act @ wd^T   (dx0 is None: the whole prefix side is frozen)
-            if dx0 is not None:
-                self._wgrad(dx0, c["act"][0], p + "wd0")
-                if self.fuse_geglu_bwd and self._lora(p + "wd0") is None and hip.dgrad_geglu_bwd_ok(dx0, self.W(p + "wd0"), c["gu"][0]):
-                    # the down projection's data gradient with the GeGLU backward as its epilogue: d(act) never reaches memory
-                    dgu = hip.linear_dgrad_geglu_bwd(dx0, self.W(p + "wd0"), c["gu"][0])
-                else:
-                    dact = self._dgrad0(dx0, p + "wd0")
-                    self._lora_bwd(dx0, c["act"][0], c["lt"][0].get("wd"), dact, p + "wd0")
-                    dgu = hip.geglu_bwd(c["gu"][0], dact, pad=self.gemm_dtype != "fp8")
-                    del dact
-                self._wgrad(dgu, c["hf"][0], p + "wgu0")
-                dhf = self._dgrad0(dgu, p + "wgu0")
-                self._lora_bwd(dgu, c["hf"][0], c["lt"][0].get("wgu"), dhf, p + "wgu0")
-                del dgu
-                self._wg_join(dx0)   # (the down projection's weight gradient reads dx0)
-                hip.rmsnorm_bwd(c["xa"][0], dhf, c["rstd_f"][0], scale=self.F(p + "n_ffw"), dx=dx0, dscale=self.G(p + "n_ffw"), accum_dx=True)
-                del dhf
-                self._wgrad(dx0, c["o"][0], p + "wo0")
-                d_o[0] = self._dgrad0(dx0, p + "wo0")
-                self._lora_bwd(dx0, c["o"][0], c["lt"][0].get("wo"), d_o[0], p + "wo0")
-            else:   # the attention backward still needs a dO for the prefix queries: zero (their dq / dk / dv are discarded)
-                if zero_do0 is None:
-                    zero_do0 = torch.zeros_like(c["o"][0])
-                d_o[0] = zero_do0
-            # ---- attention
-            self._handoff(sfx, main, d_o[1])
-            dq, dk, dv = hip.attention_bwd(c["q"], c["k"], c["v"], c["o"], d_o, c["lse"], [n0 if rows0 is None else rows0.n_sel, n1], [n0, n1],
-                                           B, NH, KV, HD, qinfo if rows0 is None else rows0.qinfo, kinfo,
-                                           stop_q1_to_k0=self.config.stop_action_to_vlm_grad)
-            self._handoff(main, sfx, dq[1], dk[1], dv[1])
-            if has_sfx:
-                with on_sfx():
-                    dqkv = hip.rope_split_bwd(dq[1], dk[1], dv[1], pos, B, n1, Ttot, Ttot - n1, NH, HD, HD ** -0.5)
-                    self._wgrad(dqkv, c["h"][1], p + "wqkv1")
-                    dh = hip.linear_dgrad(dqkv, self.W(p + "wqkv1"))
-                    self._lora_bwd(dqkv, c["h"][1], c["lt"][1].get("wqkv"), dh, p + "wqkv1")
-                    if ada:
-                        hip.rmsnorm_bwd(c["x"][1], dh, c["rstd_a"][1], mod=self._mod_slot(mod, slot_a), rows_per_sample=n1, dx=dx1,
-                                        dmod=self._mod_slot(dmod, slot_a), accum_dx=True)
-                    else:
-                        hip.rmsnorm_bwd(c["x"][1], dh, c["rstd_a"][1], scale=self.F(p + "n_attn1"), dx=dx1, dscale=self.G(p + "n_attn1"), accum_dx=True)
-                    del dqkv, dh
-            if dx0 is not None:
-                dqkv = hip.rope_split_bwd(dq[0], dk[0], dv[0], pos, B, n0, Ttot, 0, NH, HD, HD ** -0.5,
-                                          q_row=None if rows0 is None else rows0.inv)      # (compact dq: zeros in the other rows' q columns)
-                self._wgrad(dqkv, c["h"][0], p + "wqkv0")
-                dh = self._dgrad0(dqkv, p + "wqkv0")
-                self._lora_bwd(dqkv, c["h"][0], c["lt"][0].get("wqkv"), dh, p + "wqkv0")
-                if rows0 is None:
-                    self._wg_join(dx0)   # (the out projection's reads dx0)
-                    hip.rmsnorm_bwd(c["x"][0], dh, c["rstd_a"][0], scale=self.F(p + "n_attn"), dx=dx0, dscale=self.G(p + "n_attn"), accum_dx=True)
-                else:   # all rows from here on: the norm's backward of every row, the compact residual cotangent added at its rows
-                    dx0 = hip.rmsnorm_bwd(c["x"][0], dh, c["rstd_a"][0], scale=self.F(p + "n_attn"), dscale=self.G(p + "n_attn"),
-                                          add_row=rows0.inv, addend=dx0)
-                del dqkv, dh
-            ctx[l] = None
-            self._unit_done(f"llm{l}", sfx)   # complete once both streams are through: the optimizer's stream waits for both, the
-                                             # compute stream goes on (it meets the second stream again at the next attention)
-        self._handoff(sfx, main)
-        return dx0, dx1
 
     # ================================================================== training forward (+ backward)
     def _loss_impl(self, rng, observation: CoTObservation, actions: torch.Tensor, *, train: bool, noise=None, time=None,
@@ -1027,9 +557,9 @@ class LAP:
             collect["x0_in"], collect["x1_in"], collect["pos"], collect["mod"] = x0, x1, pos, mod
         # the language head's rows are chosen here, once: the last layer's prefix stream may run on them alone
         lrows = select_loss_rows(self, obs, observation, verbose=verbose) if lang_on else None
-        last_rows = self._last_layer_rows(lrows, qinfo, B, Pn, obs.tokenized_prompt.shape[1], save=backward, x1=x1, collect=collect,
-                                          verbose=verbose)
-        xf0, xf1, lctx = self._llm_fwd(x0, x1, mod, pos, qinfo, kinfo, B, Pn, Sx, backward, collect=collect, last_rows=last_rows)
+        last_rows = last_layer_rows(self, lrows, qinfo, B, Pn, obs.tokenized_prompt.shape[1], save=backward, x1=x1, collect=collect,
+                                    verbose=verbose)
+        xf0, xf1, lctx = llm_fwd(self, x0, x1, mod, pos, qinfo, kinfo, B, Pn, Sx, backward, collect=collect, last_rows=last_rows)
         if collect is not None:
             collect["x0_out"], collect["x1_out"] = xf0, xf1
 
@@ -1070,7 +600,7 @@ class LAP:
 
         # =============================== backward ===============================
         self.comm.before_backward()
-        self._wg_begin()
+        self.wg.begin(self.wgrad_stream)
         dx1, dmod = action_head_bwd(self, ah, xf1, mod, dv, B, S, Sx) if act_on else (None, None)
         skip_prefix = self._prefix_frozen()
         dx0 = None
@@ -1083,7 +613,7 @@ class LAP:
             # scatter-add of _embed_prefix_bwd would accumulate onto the previous step's values
             if self.ps.is_trainable("llm/embed"):
                 self.G("llm/embed").zero_()
-        dx0, dx1 = self._llm_bwd(lctx, dx0, dx1, mod, dmod, pos, qinfo, kinfo, B, Pn, Sx, last_rows=last_rows)
+        dx0, dx1 = llm_bwd(self, lctx, dx0, dx1, mod, dmod, pos, qinfo, kinfo, B, Pn, Sx, last_rows=last_rows)
         sfx = None
         if act_on and cfg.pi05:
             sfx = self._embed_suffix_bwd(sctx, dx1, dmod)
@@ -1093,8 +623,8 @@ class LAP:
             self.comm.grads_ready("ada")
         if not skip_prefix:
             self._embed_prefix_bwd(pctx, dx0, B, Pn)
-        self._handoff(sfx, torch.cuda.current_stream() if sfx is not None else None)
-        self._wg_end()
+        handoff(sfx, torch.cuda.current_stream() if sfx is not None else None)
+        self.wg.end()
         self.comm.grads_ready("small")
         return loss, metrics
 

@@ -8,6 +8,7 @@ import torch
 
 from lap_amd import hip
 from lap_amd.model import LAP
+from lap_amd.siglip import siglip_stem
 
 
 def panel_weight(model: LAP, name):
@@ -21,7 +22,7 @@ def panel_weight(model: LAP, name):
 
 
 def siglip_fwd_serve(model: LAP, images: torch.Tensor):
-    """The tower of `LAP._siglip_fwd` for the serving prefill: same operations and rounding points, fewer launches — GELU in fc1's
+    """The tower of `siglip.siglip_fwd` for the serving prefill: same operations and rounding points, fewer launches — GELU in fc1's
     epilogue (after the bf16 rounding of the Dense output), and fc2's split-K reduce, bias, residual add and the NEXT LayerNorm in
     one consumer pass (`lap_fused_reduce_norm`).  12 -> 10 launches per block, on block tiles sized for 512 rows
     (lap_gemm_bf16_ex serving rule)."""
@@ -30,7 +31,7 @@ def siglip_fwd_serve(model: LAP, images: torch.Tensor):
     hd = W // s.num_heads
     N = images.shape[0]
     pw = lambda name: panel_weight(model, name)
-    x, _ = model._siglip_stem(images)
+    x, _ = siglip_stem(model, images)
     scratch = hip._gemm_scratch(model.device)
     model.comm.wait_unit("img0")
     y, _, _ = hip.layernorm_fwd(x, model.F("img/0/ln1_g"), model.F("img/0/ln1_b"))
@@ -71,7 +72,7 @@ def siglip_fwd_serve(model: LAP, images: torch.Tensor):
 
 
 def llm_prefill(model: LAP, x0, pos, qinfo, kinfo, B, n0, cache_out, kv_events=None):
-    """The prefix-only pass of `LAP._llm_fwd` (x1 = None, nothing saved) for the serving prefill: K / V of every layer go to
+    """The prefix-only pass of `joint_layers.llm_fwd` (x1 = None, nothing saved) for the serving prefill: K / V of every layer go to
     `cache_out`, the last layer's residual stream is returned.  Same operations and rounding points; the split-K projections
     leave f32 slabs and their consumers do the rest in one pass each — qkv: reduce + RoPE + head split (sin / cos of the
     prefix positions from one table for all layers), out / down: reduce + residual + the NEXT RMSNorm — 14 -> 10 launches

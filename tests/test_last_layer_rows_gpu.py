@@ -1,4 +1,4 @@
-"""The last joint layer's row-subset path (LAP._last_layer_rows, LAP_LAST_LAYER_ROWS): in a train step the prefix stream of the last
+"""The last joint layer's row-subset path (joint_layers.last_layer_rows, LAP_LAST_LAYER_ROWS): in a train step the prefix stream of the last
 layer keeps K / V of every row and runs Q, attention, out projection, FFN and their backward on the language head's rows only.
 
 Kernel level: the indexed kernels against float64 references computed here from the same bf16 inputs (tests/train_reference.py

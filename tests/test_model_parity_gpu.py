@@ -257,6 +257,118 @@ def test_serving_launch_trace_matches_fixture(hip, monkeypatch):
     assert "lap_panel_gemm_pf" in names("tokens_eager") | names("chain")
 
 
+def _train_launch_traces(hip, monkeypatch):
+    """One `loss_and_grad` per route of the train step on a fresh model (`_full_width_cfg`, B = 2, ragged prompts, fixed noise and
+    time, the loaders' `loss_rows_max` hint): every library entry point that takes a stream as [name, stream number, run length]
+    (streams numbered by first appearance within the run: normally 0 the compute stream, 1 the suffix stream, 2 the weight-gradient
+    stream; consecutive equal (name, stream) pairs run-length encoded) and, between them in issue order, the collective hooks as
+    ["comm.<hook>", unit, streams in `also`].  Uses the public surface only (LAP(...), loss_and_grad, model.comm, model.ps, hip._fn):
+    the recorder runs unchanged on the commit the fixture was recorded on."""
+    import ctypes
+
+    from lap_amd import config as C
+    from lap_amd.model import LAP, _NullComm
+
+    trace = []
+
+    class RecordingComm(_NullComm):
+        @staticmethod
+        def _n(also):
+            return 0 if also is None else (len(also) if isinstance(also, (list, tuple)) else 1)
+
+        def wait_unit(self, name, also=None): trace.append(("comm.wait_unit", name, self._n(also)))
+        def pace(self, name): trace.append(("comm.pace", name, 0))
+        def grads_ready(self, name, also=None): trace.append(("comm.grads_ready", name, self._n(also)))
+        def before_backward(self): trace.append(("comm.before_backward", "", 0))
+
+    def traced(name, fn):
+        def call(*a):
+            s = a[-1]
+            trace.append((name, int(getattr(s, "value", s) or 0)))
+            return fn(*a)
+        return call
+    for name, fn in list(hip._fn.items()):
+        sig = hip.SIGNATURES[name]
+        if sig and sig[-1] is ctypes.c_void_p:      # (include/lap_hip.h: the stream is the last argument, a void*)
+            monkeypatch.setitem(hip._fn, name, traced(name, fn))
+
+    cfg = _full_width_cfg(monkeypatch)
+    obs, actions, noise, time = make_inputs(cfg, B=2, ragged=True)
+    # (the host-side hint the data loaders attach: with it the language head, and the last layer's prefix stream, run on the loss rows)
+    o = dataclasses.replace(to_observation(obs, DEV), loss_rows_max=int(obs["tokenized_langact_mask"][:, 1:].sum(-1).max()))
+
+    def record(cfg, setup=None, **kw):
+        model = LAP(cfg, seed=5, device=DEV, comm=RecordingComm(), **kw)
+        if setup is not None:
+            setup(model)
+        torch.cuda.synchronize()
+        del trace[:]
+        model.loss_and_grad(0, o, actions.to(DEV), noise=noise.to(DEV), time=time.to(DEV))
+        torch.cuda.synchronize()
+        streams, rle = {}, []
+        for ent in trace:
+            if len(ent) == 3:
+                rle.append(list(ent))
+                continue
+            sid = streams.setdefault(ent[1], len(streams))
+            if rle and rle[-1][0] == ent[0] and rle[-1][1] == sid and not rle[-1][0].startswith("comm."):
+                rle[-1][2] += 1
+            else:
+                rle.append([ent[0], sid, 1])
+        return model, rle
+
+    def one_stream(m):
+        m.dual_stream, m.wgrad_stream = False, ""
+
+    def all_rows(m):
+        m.last_layer_rows = False
+
+    record(cfg)     # the process-wide warm-up step (not recorded)
+    out = {}
+    model, out["pi05"] = record(cfg)
+    assert model.last_rows_steps > 0      # the row-subset path is in the trace
+    _, out["pi05_one_stream"] = record(cfg, one_stream)
+    _, out["pi05_all_rows"] = record(cfg, all_rows)
+    _, out["pi0"] = record(dataclasses.replace(cfg, pi05=False))
+    model, out["prefix_frozen"] = record(cfg, lambda m: m.ps.set_frozen(cfg.get_vlm_freeze_filter()))
+    assert model._prefix_frozen()
+    _, out["lang_off"] = record(dataclasses.replace(cfg, enable_langact_training=False))
+    _, out["action_off"] = record(dataclasses.replace(cfg, enable_action_training=False))
+    monkeypatch.setitem(C._GEMMA, "gemma_2b_lora_x2", C.GemmaConfig(2048, 2, 16384, 8, 1, 256, lora_attn=(16, 16.0), lora_ffn=(16, 16.0)))
+    monkeypatch.setitem(C._GEMMA, "gemma_300m_lora_x2", C.GemmaConfig(1024, 2, 4096, 8, 1, 256, lora_attn=(32, 32.0), lora_ffn=(32, 32.0)))
+    _, out["lora"] = record(dataclasses.replace(cfg, paligemma_variant="gemma_2b_lora_x2", action_expert_variant="gemma_300m_lora_x2"))
+    _, out["fp8"] = record(cfg, gemm_dtype="fp8")
+    del model
+    return out
+
+
+def test_train_launch_trace_matches_fixture(hip, monkeypatch):
+    """What a tolerance cannot see in the train step: a dropped join with the weight-gradient stream, a `comm.pace` that moved behind
+    a GEMM, a weight gradient that left its stream.  The launches of one step, the stream of each and the collective hooks between
+    them equal tests/golden/train_launch_trace.json on every route, recorded with `_train_launch_traces` on the commit before the
+    joint layers, the SigLIP tower and the side streams moved out of model.py (a change that alters the launches on purpose records
+    the fixture anew, with the reason)."""
+    import json
+
+    with open(os.path.join(os.path.dirname(__file__), "golden", "train_launch_trace.json")) as f:
+        want = json.load(f)
+    got = _train_launch_traces(hip, monkeypatch)
+    assert set(got) == set(want)
+    for route in want:
+        assert got[route] == want[route], route
+    launches = lambda route: [e for e in want[route] if not e[0].startswith("comm.")]
+    names = lambda route: {e[0] for e in launches(route)}
+    streams = lambda route: {e[1] for e in launches(route)}
+    assert streams("pi05") == {0, 1, 2} and "lap_rope_split_fwd_rows" in names("pi05")      # the fixture holds the routes it names
+    assert "lap_rope_split_fwd_rows" not in names("pi05_all_rows") and streams("pi05_one_stream") == {0}
+    assert "lap_gated_residual_fwd" not in names("pi0") and "lap_gated_residual_fwd" in names("pi05")
+    assert "lap_lora_down" in names("lora") and "lap_gemm_fp8" in names("fp8")
+    ln_bwd = lambda route: {n for n in names(route) if n.startswith("lap_layernorm_bwd")}      # (SigLIP's: hip.layernorm_bwd)
+    assert not ln_bwd("prefix_frozen") and ln_bwd("pi05")
+    hooks = {e[0] for e in want["pi05"]} - names("pi05")
+    assert hooks == {"comm.wait_unit", "comm.pace", "comm.grads_ready", "comm.before_backward"}
+
+
 def _check_loss_activations_and_grads(cfg, B, ragged):
     oc = oracle_cfg(cfg)
     P = O.init_params(oc, seed=7)
@@ -480,6 +592,9 @@ def _per_layer_sweep(cfg, oc, col, col32, col16, B, pm, report=None):
 def _teacher_forced_sweep(model, cfg, oc, obs, col, col16, B, pm, report=None):
     """Layer by layer: engine(layer l)(bf16 oracle's input of layer l) vs the bf16 oracle's output of layer l, for every
     SigLIP block (first image key) and every joint Gemma layer (both streams), at valid positions."""
+    from lap_amd.joint_layers import llm_fwd
+    from lap_amd.siglip import siglip_fwd
+
     T = (cfg.image_size // oc.img.patch) ** 2
     S = cfg.action_horizon
     Pn = pm.shape[1]
@@ -500,7 +615,7 @@ def _teacher_forced_sweep(model, cfg, oc, obs, col, col16, B, pm, report=None):
 
     prev = col16["img/stem"]
     for l in range(oc.img.depth):
-        out, _ = model._siglip_fwd(None, False, x_in=bf(prev).view(B * T, -1), blocks=[l])
+        out, _ = siglip_fwd(model, None, False, x_in=bf(prev).view(B * T, -1), blocks=[l])
         want = col16[f"img/block{l:02d}"]
         check(f"img/block{l:02d}", out.float().cpu().view(B, T, -1), want)
         prev = want
@@ -508,7 +623,7 @@ def _teacher_forced_sweep(model, cfg, oc, obs, col, col16, B, pm, report=None):
     mod = col["mod"]
     x0p, x1p = col16["llm/in0"], col16["llm/in1"]
     for l in range(oc.vlm.depth):
-        x0, x1, _ = model._llm_fwd(bf(x0p).view(B * Pn, -1), bf(x1p).view(B * S, -1), mod, pos, qinfo, kinfo, B, Pn, S, False, layers=[l])
+        x0, x1, _ = llm_fwd(model, bf(x0p).view(B * Pn, -1), bf(x1p).view(B * S, -1), mod, pos, qinfo, kinfo, B, Pn, S, False, layers=[l])
         w0, w1 = col16[f"llm/layer{l:02d}/x0"], col16[f"llm/layer{l:02d}/x1"]
         check(f"llm/layer{l:02d}/x0", x0.float().cpu().view(B, Pn, -1)[pm], w0[pm])
         check(f"llm/layer{l:02d}/x1", x1.float().cpu().view(B, S, -1), w1)
@@ -974,7 +1089,7 @@ def test_compute_loss_is_forward_of_loss_and_grad(hip):
 
 
 def test_two_stream_schedule_equals_one_stream(hip, monkeypatch):
-    """The action expert's kernels on a second HIP stream (model.py: _suffix_stream) against everything on one stream, LAP-3B
+    """The action expert's kernels on a second HIP stream (streams.py: suffix_stream) against everything on one stream, LAP-3B
     widths: same loss bits, same activations, and gradients equal up to the order of the f32 atomics that the norm / modulation
     backward kernels add with (free in both schedules; what follows them inherits the last-bit noise: 1e-5 relative, and no more
     tensors affected than between two one-stream runs + 2).  Run five times: a missing join between the streams would show up
@@ -995,12 +1110,12 @@ def test_two_stream_schedule_equals_one_stream(hip, monkeypatch):
         return loss.item(), {k: col[k].clone() for k in ("x0_out", "x1_out", "v_t")}, {n: model.ps.g(n).detach().clone() for n in model.ps.names()}
 
     l1, a1, g1 = run(False)
-    assert model._sfx is None
+    assert model.sfx is None
     _, _, g1b = run(False)
     noisy = sum(not torch.equal(g1[n], g1b[n]) for n in g1)
     for _ in range(5):
         l2, a2, g2 = run(True)
-        assert model._sfx is not None and model._wg_obj is not None
+        assert model.sfx is not None and model.wg.stream is not None
         assert l1 == l2
         for k in a1:
             assert torch.equal(a1[k], a2[k]), k
