@@ -1,7 +1,10 @@
-// Shared pieces of the bf16 (gemm.hip) and fp8 (gemm_fp8.hip) MFMA GEMM kernels: launch parameters, the logical tile
-// order, and the epilogues (direct 4-wide stores, LDS-staged full-row stores of the 256x256 kernels).
+// Shared pieces of the bf16 (gemm.hip, gemm_probes.hpp) and fp8 (gemm_fp8.hip) MFMA GEMM kernels: launch parameters, the logical
+// tile order, the operand descriptors of the prologues, the epilogues (bias / GELU / residual and the final
+// store as one function each; direct 4-wide stores, LDS-staged full-row stores of the 256x256 kernels) and the launcher of the
+// 256 x 256 family.
 #pragma once
 #include "common.hpp"
+#include <stdlib.h>
 #include "../../include/lap_hip.h"
 
 namespace {
@@ -53,6 +56,53 @@ __device__ __forceinline__ bf16x8 kc32_frag(const char* tile, int row0, int lane
   return *reinterpret_cast<const bf16x8*>(tile + kc32_tile_off(row0 + i, g));
 }
 
+// Buffer descriptor of an operand of `rows` rows of ld elements (ESZ bytes each; rows = M or N when it is K-contiguous, else K):
+// 31-bit range, reads past it (and at the offset OOB) return zeros.
+template <int ESZ = 2>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t operand_rsrc(const void* ptr, int rows, int ld) {
+  return __builtin_amdgcn_make_buffer_rsrc((void*)ptr, 0, (int)min((long long)rows * ld * ESZ, 0x7fffffffLL), 0x00020000);
+}
+
+// Epilogue arithmetic for 4 consecutive outputs at (m, n), v = alpha * product: bias (bf16 or f32), GELU (2: the pre-activation is
+// rounded to bf16 first = a bf16 Dense output followed by a GELU kernel), residual, in this order.  Used by the direct stores of
+// every kernel (store_tile4) and by both reduce passes.  The bf16 branch of staged_epilogue below states the same chain a second
+// time: calling this function there moved instructions in the 16-wave kernel's compiled code, and the main-loop kernels are held
+// to their instruction text (docs/EXPERIMENTS.md W).  A change to the chain is made in both places.
+__device__ __forceinline__ f32x4 epilogue4(const GemmParams& p, int m, int n, f32x4 v) {
+  if (p.bias_kind == 1) {
+    bf16x4 b = *reinterpret_cast<const bf16x4*>((const bf16*)p.bias + n);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] += (float)b[e];
+  } else if (p.bias_kind == 2) {
+    v += *reinterpret_cast<const f32x4*>((const float*)p.bias + n);
+  }
+  if (p.gelu) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = gelu_tanh_f(p.gelu == 2 ? round_bf16(v[e]) : v[e]);
+  }
+  if (p.R) {
+    bf16x4 r = *reinterpret_cast<const bf16x4*>(p.R + (long long)m * p.ldr + n);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] += (float)r[e];
+  }
+  return v;
+}
+
+// ... and the final store: f32 (onto the old values when accumulating) or bf16.
+template <bool OUT_F32>
+__device__ __forceinline__ void store4(const GemmParams& p, int m, int n, f32x4 v) {
+  if (OUT_F32) {
+    float* c = (float*)p.C + (long long)m * p.ldc + n;
+    if (p.accum) v += *reinterpret_cast<const f32x4*>(c);
+    *reinterpret_cast<f32x4*>(c) = v;
+  } else {
+    bf16x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = f2bf(v[e]);
+    *reinterpret_cast<bf16x4*>((bf16*)p.C + (long long)m * p.ldc + n) = o;
+  }
+}
+
 // Epilogue for 4 consecutive outputs C[m][n..n+3] held by one lane (shared by every kernel shape).
 template <bool OUT_F32>
 __device__ __forceinline__ void store_tile4(const GemmParams& p, int m, int n, f32x4 a) {
@@ -65,38 +115,14 @@ __device__ __forceinline__ void store_tile4(const GemmParams& p, int m, int n, f
     }
     return;
   }
-  f32x4 v = a * p.alpha;
-  if (p.bias_kind == 1) {
-    bf16x4 b = *reinterpret_cast<const bf16x4*>((const bf16*)p.bias + n);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] += (float)b[e];
-  } else if (p.bias_kind == 2) {
-    v += *reinterpret_cast<const f32x4*>((const float*)p.bias + n);
-  }
-  if (p.gelu) {   // 2: the pre-activation is rounded to bf16 first (= a bf16 Dense output followed by a GELU kernel)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = gelu_tanh_f(p.gelu == 2 ? round_bf16(v[e]) : v[e]);
-  }
-  if (p.R) {
-    bf16x4 r = *reinterpret_cast<const bf16x4*>(p.R + (long long)m * p.ldr + n);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] += (float)r[e];
-  }
-  if (OUT_F32) {
+  const f32x4 v = epilogue4(p, m, n, a * p.alpha);
+  if (OUT_F32 && p.ksplit > 1) {   // atomic split-K
     float* c = (float*)p.C + (long long)m * p.ldc + n;
-    if (p.ksplit > 1) {
 #pragma unroll
-      for (int e = 0; e < 4; ++e) atomicAdd(c + e, v[e]);
-    } else {
-      if (p.accum) v += *reinterpret_cast<const f32x4*>(c);
-      *reinterpret_cast<f32x4*>(c) = v;
-    }
-  } else {
-    bf16x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = f2bf(v[e]);
-    *reinterpret_cast<bf16x4*>((bf16*)p.C + (long long)m * p.ldc + n) = o;
+    for (int e = 0; e < 4; ++e) atomicAdd(c + e, v[e]);
+    return;
   }
+  store4<OUT_F32>(p, m, n, v);
 }
 
 // Epilogue of the 256x256 kernels through LDS (set by the host: p.epi_lds).  bf16: straight from the accumulators a lane
@@ -207,5 +233,46 @@ __device__ __forceinline__ void staged_epilogue(const GemmParams& p, char* smem,
 }
 
 template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+
+// ---- host side ----
+// The staged epilogue's full-row stores go out nontemporal (C is written once and read from HBM by its consumer anyway; the
+// operand panels keep the L2): -0.3 .. -1.0 ms per train step in three A/B pairs, serving unchanged.  LAP_GEMM_NT_STORE=0: plain.
+inline int epi_lds_mode() {
+  static const int mode = (getenv("LAP_GEMM_NT_STORE") && atoi(getenv("LAP_GEMM_NT_STORE")) == 0) ? 1 : 2;
+  return mode;
+}
+
+// GemmParams::epi_lds of a launch: the staged epilogue needs an unsplit product straight to C, whole 16-byte pieces per row and no
+// residual on an f32 output.
+inline int staged_epilogue_mode(const GemmParams& p, bool out_f32) {
+  return (!p.part && p.ksplit == 1 && !(out_f32 && p.R) && !(p.N & 7) && !(p.ldc & 7) && !((uintptr_t)p.C & 15)) ? epi_lds_mode() : 0;
+}
+
+// LDS of the staged epilogue: a bf16 tile (528-byte rows) or half an f32 tile (128 rows of 1040 bytes); >= 128 KiB of operand stages
+constexpr int staged_epilogue_lds(bool out_f32) { return out_f32 ? 128 * (256 * 4 + 16) : 256 * (256 * 2 + 16); }
+
+// Launcher of every kernel with a 256 x 256 block tile and 64-deep k-tiles: THREADS threads, LDS bytes of dynamic shared memory,
+// K & KMASK must be 0, STAGED: the kernel takes the staged epilogue where staged_epilogue_mode allows it (else p.epi_lds stays the
+// caller's).  The kernel arrives as a captureless lambda that returns it, [] { return some_kernel<...>; }: every such lambda has a
+// type of its own, so `done` (the attribute is set once; benign race, it is idempotent) is one flag per kernel instantiation.
+template <int THREADS, int LDS, int KMASK, bool STAGED, bool OUT_F32, typename KernelOf>
+int launch_256(KernelOf kernel_of, GemmParams p, hipStream_t s) {
+  const auto kern = kernel_of();
+  if (p.K & KMASK) return LAP_ERR_ARG;
+  if (STAGED) p.epi_lds = staged_epilogue_mode(p, OUT_F32);
+  static bool done = false;
+  if (!done) {
+    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    if (e != hipSuccess) return (int)e;
+    done = true;
+  }
+  p.tiles_m = (p.M + 255) / 256;
+  p.tiles_n = (p.N + 255) / 256;
+  p.ktiles_per_split = ((p.K + 63) / 64 + p.ksplit - 1) / p.ksplit;
+  const int count = p.tile_count > 0 ? p.tile_count : p.tiles_m * p.tiles_n - p.tile_base;
+  hipLaunchKernelGGL(kern, dim3(count, p.ksplit), dim3(THREADS), LDS, s, p);
+  LAP_CHECK_LAUNCH();
+  return LAP_OK;
+}
 
 }  // namespace

@@ -48,8 +48,8 @@ __global__ __launch_bounds__(512) void gemm_f8_kernel(GemmParams p) {
   const int m0 = tm * BM, n0 = tn * BN;
   const char* A8 = reinterpret_cast<const char*>(p.A);
   const char* B8 = reinterpret_cast<const char*>(p.B);
-  auto rsA = __builtin_amdgcn_make_buffer_rsrc((void*)A8, 0, (int)min((long long)p.M * p.lda, 0x7fffffffLL), 0x00020000);
-  auto rsB = __builtin_amdgcn_make_buffer_rsrc((void*)B8, 0, (int)min((long long)p.N * p.ldb, 0x7fffffffLL), 0x00020000);
+  auto rsA = operand_rsrc<1>(A8, p.M, p.lda);
+  auto rsB = operand_rsrc<1>(B8, p.N, p.ldb);
   unsigned offA[PC], offB[PC];
 #pragma unroll
   for (int j = 0; j < PC; ++j) {
@@ -275,22 +275,10 @@ extern "C" int lap_gemm_fp8(const void* A8, const void* B8, void* C, const void*
   p.accum = (flags & LAP_GEMM_ACCUM) ? 1 : 0;
   p.ksplit = 1;
   p.qscale_a = scale_a; p.qscale_b = scale_b;
-  p.tiles_m = (M + 255) / 256; p.tiles_n = (N + 255) / 256;
   p.epi_lds = (!(f32 && p.R) && !(N & 7) && !(ldc & 7)) ? 1 : 0;
-  const int LDS = f32 ? 128 * (256 * 4 + 16) : 256 * (256 * 2 + 16);   // >= the two operand stages (128 KiB)
-  auto launch = [&](auto kern) -> int {
-    static bool done_f32 = false, done_b16 = false;
-    bool& done = f32 ? done_f32 : done_b16;
-    if (!done) {
-      hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-      if (e != hipSuccess) return (int)e;
-      done = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(p.tiles_m * p.tiles_n), dim3(512), LDS, S_, p);
-    LAP_CHECK_LAUNCH();
-    return LAP_OK;
-  };
-  return f32 ? launch(gemm_f8_kernel<true>) : launch(gemm_f8_kernel<false>);
+  // (the two operand stages are 128 KiB; the staged epilogue's image is larger)
+  return f32 ? launch_256<512, staged_epilogue_lds(true), 127, false, true>([] { return gemm_f8_kernel<true>; }, p, S_)
+             : launch_256<512, staged_epilogue_lds(false), 127, false, false>([] { return gemm_f8_kernel<false>; }, p, S_);
 }
 
 extern "C" int lap_amax_bf16(const void* x, long long rows, int cols, long long ld, float* amax, void* stream) {

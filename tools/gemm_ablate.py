@@ -1,5 +1,6 @@
 """Where does a k-tile of the production GEMM kernel (tile 10) go?  Normal vs no in-loop LDS-DMA vs no MFMA, on the
-LAP-3B shapes.  Needs a LAP_GEMM_EXPERIMENTAL=1 build (python -m lap_amd.build --force with the env set)."""
+LAP-3B shapes.  The ablation bits (lap_gemm_set_debug) sit inside gemm_sp_kernel / gemm_pq_kernel / gemm_kernel in csrc/gemm.hip and are
+compiled in a LAP_GEMM_EXPERIMENTAL build only: python -m lap_amd.build --variant=exp, then LAP_HIP_LIB_VARIANT=exp."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
