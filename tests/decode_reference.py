@@ -93,28 +93,29 @@ def gelu_tanh64(x):
     return 0.5 * x * (1.0 + torch.tanh(0.7978845608028654 * (x + 0.044715 * x ** 3)))
 
 
-def ref_residual(a, w, res, rounded=True):
-    """proj_res: y = bf16(a W^T + res).  One rounding point (n = 1).  Returns (R16, bound) or R64."""
+def ref_residual(a, w, res, rounded=True, depth=DEPTH):
+    """proj_res: y = bf16(a W^T + res).  One rounding point (n = 1).  Returns (R16, bound) or R64.  depth: the summation depth of
+    the kernel under test (the decode kernels': DEPTH), here and in ref_gate_up / ref_qkv."""
     dot, sens = dot_and_sens(a, w)
     y = dot + res.double()
-    return _rnd(y, DEPTH * U24 * sens) if rounded else y
+    return _rnd(y, depth * U24 * sens) if rounded else y
 
 
-def ref_gate_up(h, w, H, rounded=True):
+def ref_gate_up(h, w, H, rounded=True, depth=DEPTH):
     """gate_up on the normalised rows h [B, D] (float64): act = bf16(bf16(gelu(bf16 g)) * bf16 u), g | u = h W^T.  Four rounding
     points (n = 4: g, u, gelu, the stored product), each entering with its gain: gelu's slope is at most 1.13, and the float32
     form 0.5 x (1 + tanh(.)) carries an absolute error of up to 2^-23 |g| from the cancellation in its negative tail."""
     dot, sens = dot_and_sens(h, w)
     if not rounded:
         return gelu_tanh64(dot[:, :H]) * dot[:, H:]
-    d0 = DEPTH * U24 * sens
+    d0 = depth * U24 * sens
     g, dg = _rnd(dot[:, :H], d0[:, :H])
     u, du = _rnd(dot[:, H:], d0[:, H:])
     ge, dge = _rnd(gelu_tanh64(g), 1.13 * dg + g.abs() * 2.0 ** -23)
     return _rnd(ge * u, dge * u.abs() + ge.abs() * du + dge * du)
 
 
-def ref_qkv(h, w, pos, NH, HD, q_scale, rounded=True):
+def ref_qkv(h, w, pos, NH, HD, q_scale, rounded=True, depth=DEPTH):
     """qkv on the normalised rows h [B, D] (float64), positions pos [B]: x = bf16(h W^T); q and k heads r = bf16(RoPE(x)), q
     scaled by q_scale (a power of two here: exact, and so is the store); v = x.  Rounding points: projection and rotation for q / k
     (n = 2 with gains |cos| and |sin|; the store the header lists is exact), projection alone for v (n = 1).  The float32 angle
@@ -122,7 +123,7 @@ def ref_qkv(h, w, pos, NH, HD, q_scale, rounded=True):
     Returns (q [B, NH HD], k [B, HD], v [B, HD]), each (R16, bound), or the three R64."""
     B, half = h.shape[0], HD // 2
     dot, sens = dot_and_sens(h, w)
-    dot, d0 = dot.view(B, NH + 2, HD), (DEPTH * U24 * sens).view(B, NH + 2, HD)
+    dot, d0 = dot.view(B, NH + 2, HD), (depth * U24 * sens).view(B, NH + 2, HD)
     ang = pos.double().view(B, 1, 1) / (10000.0 ** (2.0 * torch.arange(half, dtype=torch.float64) / HD)).view(1, 1, half)
     sn, cs = torch.sin(ang), torch.cos(ang)
 
