@@ -73,8 +73,30 @@ def allowed_set(model: LAP, allowed_tokens) -> AllowedSet:
     return AllowedSet(check_allowed_tokens(allowed_tokens, V, eos).to(model.device), V, eos)
 
 
+MAX_NUM_SAMPLES = 8     # best-of-N decodes its candidates as the rows of one fused batch (B <= 8)
+
+
+def check_num_samples(num_samples, batch: int, *, decode: str, sampler: str, temperature: float) -> int:
+    """`num_samples` of a best-of-N request as an int; ValueError naming the condition it breaks."""
+    if isinstance(num_samples, bool) or int(num_samples) != num_samples:
+        raise ValueError(f"num_samples must be an integer, got {num_samples!r}")
+    N = int(num_samples)
+    if not 1 <= N <= MAX_NUM_SAMPLES:
+        raise ValueError(f"num_samples must lie in [1, {MAX_NUM_SAMPLES}] (the candidates are the rows of one fused batch), got {N}")
+    if batch != 1:
+        raise ValueError(f"num_samples needs an observation of batch 1 (its prefix is prefilled once), got batch {batch}")
+    if decode != "fused":
+        raise ValueError(f"num_samples needs decode=\"fused\" (the candidates decode as one fused batch), got decode={decode!r}")
+    if sampler != "device":
+        raise ValueError(f"num_samples needs sampler=\"device\" (row b draws with Philox row index b), got sampler={sampler!r}")
+    if not temperature > 0.0:
+        raise ValueError(f"num_samples needs temperature > 0 (greedy candidates are all the same), got {temperature!r}")
+    return N
+
+
 def sample_tokens(model: LAP, rng, observation, *, max_decoding_steps: int = 390, temperature: float = 0.0, collect=None,
-                  decode: str = "eager", sampler: str = "host", decode_weights: str = "bf16", allowed_tokens=None):
+                  decode: str = "eager", sampler: str = "host", decode_weights: str = "bf16", allowed_tokens=None,
+                  return_logprobs: bool = False, num_samples=None):
     """`LAP.sample_tokens` (documented there): every argument is checked before any device work."""
     if decode not in ("eager", "fused"):
         raise ValueError(f"sample_tokens: decode must be 'eager' or 'fused', got {decode!r}")
@@ -83,8 +105,11 @@ def sample_tokens(model: LAP, rng, observation, *, max_decoding_steps: int = 390
         raise ValueError(f"sample_tokens: decode_weights={decode_weights!r} runs on the fused decode kernels only: pass decode=\"fused\"")
     if sampler not in ("host", "device"):
         raise ValueError(f"sample_tokens: sampler must be 'host' or 'device', got {sampler!r}")
+    N = None
+    if num_samples is not None:
+        N = check_num_samples(num_samples, observation.tokenized_prompt.shape[0], decode=decode, sampler=sampler, temperature=temperature)
     if decode == "fused":
-        check_fused_decode(model, observation.tokenized_prompt.shape[0])
+        check_fused_decode(model, N or observation.tokenized_prompt.shape[0])
     if sampler == "device":
         hip.sampling_words(rng, temperature)        # (rejects a temperature whose inverse is not finite before any work)
     allowed = None
@@ -94,12 +119,12 @@ def sample_tokens(model: LAP, rng, observation, *, max_decoding_steps: int = 390
         if decode == "fused" and (sampler == "device" or temperature <= 0.0):   # (the host sampler's noise cannot run on the device state)
             return _sample_fused(model, observation, max_decoding_steps=max_decoding_steps, collect=collect,
                                  sampling=(rng, temperature) if sampler == "device" else None, weights=decode_weights,
-                                 allowed=allowed)
+                                 allowed=allowed, logprobs=return_logprobs or N is not None, num_samples=N)
         if decode_weights != "bf16":
             raise ValueError("sample_tokens: decode_weights other than 'bf16' with temperature > 0 needs sampler='device' (the "
                              "host sampler keeps the eager loop)")
         return _sample_eager(model, rng, observation, max_decoding_steps=max_decoding_steps, temperature=temperature, collect=collect,
-                             device_sampler=sampler == "device", allowed=allowed)
+                             device_sampler=sampler == "device", allowed=allowed, logprobs=return_logprobs)
 
 
 class Prefill(NamedTuple):
@@ -138,6 +163,19 @@ def prefill(model: LAP, observation) -> Prefill:
         xf0, _, _ = llm_fwd(model, x0, None, None, ppos, qinfo_p, kinfo_p, B, Pn, 0, False, cache_out=cache)
     last = (torch.arange(B, device=dev) * Pn + seqlen - 1)
     return Prefill(B, Pn, cache, kinfo_prefix, qinfo_d, plen, xf0.index_select(0, last).contiguous())
+
+
+def replicate_prefill(pre: Prefill, N: int) -> Prefill:
+    """The batch-1 prefill `pre` as N identical rows (best-of-N): plain copies of the prefix K / V of every layer, the key-info
+    words, the prefill length and the last residual row, from which the LM head forms every row's first-token logits."""
+    if pre.B != 1:
+        raise ValueError(f"replicate_prefill: a prefill of batch 1, got {pre.B}")
+
+    def rep(t):
+        return t.repeat((N,) + (1,) * (t.dim() - 1))
+
+    return Prefill(N, pre.Pn, [(rep(k), rep(v)) for k, v in pre.cache], rep(pre.kinfo_prefix), rep(pre.qinfo_d), rep(pre.plen),
+                   rep(pre.x_last))
 
 
 # ---- the eager step: generic launches
@@ -179,13 +217,16 @@ def _lm_logits(model: LAP, rows):
 
 
 def _sample_eager(model: LAP, rng, observation, *, max_decoding_steps: int, temperature: float, collect, device_sampler: bool,
-                  allowed=None):
-    """allowed: int32 device ids; the logits outside the set are -inf before the argmax or the noise."""
+                  allowed=None, logprobs: bool = False):
+    """allowed: int32 device ids; the logits outside the set are -inf before the argmax or the noise.  logprobs: also the f32
+    log_softmax of logits * inv_t (over the allowed set) at every token, returned beside the tokens."""
     dev = model.device
     B, Pn, cache, kinfo_prefix, qinfo_d, plen, x_last = prefill(model, observation)
     logits = _lm_logits(model, x_last)                                      # decodes the first token (lap.py:716)
     out = torch.zeros((B, max_decoding_steps), dtype=torch.int32, device=dev)
     eos = torch.zeros((B,), dtype=torch.bool, device=dev)
+    logp = torch.zeros((B, max_decoding_steps), dtype=torch.float32, device=dev) if logprobs else None
+    inv_t = float(hip.sampling_words(0, temperature)[2]) if logprobs else 0.0      # float32(1 / temperature); 0: greedy, scored at tau = 1
     gen = [(None, None)] * model.v.depth
     g = _gen(rng, dev) if temperature > 0.0 and not device_sampler else None
     outside = None
@@ -196,6 +237,7 @@ def _sample_eager(model: LAP, rng, observation, *, max_decoding_steps: int, temp
     while step < max_decoding_steps:
         if outside is not None:
             logits = logits.masked_fill(outside, float("-inf"))
+        raw = logits
         if device_sampler and temperature > 0.0:      # one pass over the raw logits, no [B, V] temporaries
             token = hip.gumbel_argmax_rows(logits, temperature, rng, step)
         else:
@@ -206,22 +248,28 @@ def _sample_eager(model: LAP, rng, observation, *, max_decoding_steps: int, temp
         if collect is not None:
             collect[f"logit/{step}"] = logits.clone()
         out[:, step] = token
+        if logp is not None:
+            z = raw * inv_t if inv_t != 0.0 else raw
+            logp[:, step] = torch.log_softmax(z, dim=-1).gather(1, token.view(B, 1).long()).view(B)
         eos |= token == model.EOS_TOKEN
         step += 1
         if step >= max_decoding_steps or bool(eos.all()):   # lap.py:754-756 loop condition (the unused last decode is skipped)
             break
         pos = (plen + (step - 1)).to(torch.int32).view(B, 1).contiguous()
         logits = _vlm_decode_step(model, token, pos, step - 1, cache, gen, qinfo_d, kinfo_prefix, B, Pn)
-    return out
+    return (out, logp) if logprobs else out
 
 
 # ---- the fused step: single-token kernels, state on the device (csrc/decode.hip)
 def _sample_fused(model: LAP, observation, *, max_decoding_steps: int, collect=None, sampling=None, weights: str = "bf16",
-                  allowed=None):
+                  allowed=None, logprobs: bool = False, num_samples=None):
     """sampling: None (the greedy LM head) or (seed, temperature) for the sampling LM head.  weights: `decode_weights`.
-    allowed: None or the int32 device ids of `check_allowed_tokens`."""
+    allowed: None or the int32 device ids of `check_allowed_tokens`.  logprobs: the context keeps the token log-probabilities
+    and (tokens, logprobs) is returned.  num_samples: the batch-1 prefill is replicated to that many rows."""
     pre = prefill(model, observation)
-    ctx = DecodeCtx(model, pre.B, pre.Pn, max_decoding_steps, sampling is not None, weights, allowed=allowed)
+    if num_samples is not None:
+        pre = replicate_prefill(pre, num_samples)
+    ctx = DecodeCtx(model, pre.B, pre.Pn, max_decoding_steps, sampling is not None, weights, allowed=allowed, logprobs=logprobs)
     if sampling is not None:
         ctx.set_sampling(*sampling)
     lg = None
@@ -235,14 +283,14 @@ def _sample_fused(model: LAP, observation, *, max_decoding_steps: int, collect=N
         while not bool(ctx.state[1].item()):
             ctx.step(lg)
             collect[f"logit/{int(ctx.state[0].item()) - 1}"] = lg.clone()
-        return ctx.out
+        return (ctx.out, ctx.logp) if logprobs else ctx.out
     n = DECODE_STEPS_PER_CHECK
     for _ in range((max_decoding_steps - 1 + n - 1) // n):
         if bool(ctx.state[1].item()):
             break
         for _ in range(n):
             ctx.step()
-    return ctx.out
+    return (ctx.out, ctx.logp) if logprobs else ctx.out
 
 
 class DecodeCtx:
@@ -250,7 +298,8 @@ class DecodeCtx:
     the fixed-capacity generated K/V cache of every layer ([depth, 2, B, cap, head_dim] bf16, 7.2 MB per sample at 390 steps
     for LAP-3B) and the step's activations.  The prefix K/V cache and kinfo come from the prefill (`first_token` -> `bind`)."""
 
-    def __init__(self, model: LAP, B: int, Pn: int, cap: int, sampling: bool = False, weights: str = "bf16", allowed=None):
+    def __init__(self, model: LAP, B: int, Pn: int, cap: int, sampling: bool = False, weights: str = "bf16", allowed=None,
+                 logprobs: bool = False):
         check_decode_weights(weights)
         if allowed is not None and (allowed.dtype != torch.int32 or not allowed.is_cuda or allowed.dim() != 1):
             raise ValueError("DecodeCtx: allowed must be the int32 device ids of check_allowed_tokens")
@@ -275,6 +324,10 @@ class DecodeCtx:
         # the sampling words {seed low, seed high, bits of 1 / temperature, 0} of the sampling LM head (zeros: greedy); None:
         # the context decodes on the greedy LM head
         self.sampling = hip.decode_sampling(dev) if sampling else None
+        # logprobs: the log-probability of every token of `out` beside it (f32 [B, cap], zeros where nothing was written) and the
+        # LM head's log-sum-exp partials; None: the context launches the heads without them
+        self.logp = torch.zeros((B, cap), dtype=torch.float32, device=dev) if logprobs else None
+        self.plp = hip.decode_lm_logp_partials(B, dev) if logprobs else None
         self.prefix = None
         self.kinfo = None
 
@@ -295,6 +348,8 @@ class DecodeCtx:
         self.bind(pre.cache, pre.kinfo_prefix)
         self.plen.copy_(pre.plen)
         hip.decode_init(self.state, self.plen, self.out)
+        if self.logp is not None:
+            self.logp.zero_()
         self._token(pre.x_last, logits)
 
     def _w(self, name):
@@ -315,6 +370,10 @@ class DecodeCtx:
             hi, lo, kw = m.W("llm/embed"), m.ps.w16lo("llm/embed"), {}
         if self.allowed is not None:      # the LM head streams the allowed rows only
             kw["ids"] = self.allowed
+        if self.logp is not None:         # the same head with the log-sum-exp partials, and the finish that turns them into logp[:, t]
+            hip.decode_lm_head_lp(self.state, self.sampling, x, m.F("llm/final_norm"), hi, lo, self.pval, self.pidx, self.plp, logits, **kw)
+            hip.decode_finish_lp(self.state, self.pval, self.pidx, self.plp, self.out, self.logp, m.EOS_TOKEN)
+            return
         if self.sampling is not None:
             hip.decode_lm_head_sample(self.state, self.sampling, x, m.F("llm/final_norm"), hi, lo, self.pval, self.pidx, logits, **kw)
         else:

@@ -28,6 +28,8 @@
 //               head differs only in which two rows a unit is, which wave takes it and which noise call it makes.  So the
 //               logit of vocabulary row j is the same bits in every head by construction, and tests/test_decode_bits_gpu.py
 //               pins those bits (and the projections') to a recorded fixture: a change to the arithmetic shows there.
+//   lm_head_lp / finish_lp   any of the LM heads above with the LOGP parameter: the log-sum-exp of z = logit * tau rides along in
+//               the same pass (per block {m, s, z of the best candidate}), and the finish also writes logp[:, t] = z_tok - lse
 //   finish      one block: argmax over the partials with the lowest index among ties, out[:, t] = token, EOS mask, t += 1,
 //               done                                                                         (lap_argmax_rows_f32)
 // Rounding points are those of the eager step; only the summation order of the dot products differs.
@@ -454,6 +456,12 @@ struct LmP8 : LmP {
   const float* wscale;                 // [V] 2^e per vocabulary row
 };
 
+// P = LmLogP<LmP> / LmLogP<LmP8>: the LOGP instances' arguments (the instances without LOGP keep theirs as they are)
+template <class Base>
+struct LmLogP : Base {
+  float* plp;                          // partials [gridDim.x][B][3] = {m, s, z of the block's best candidate}
+};
+
 // The row dot product of the LM head.  Every head (full or subset, greedy or sampling, bf16 or fp8) runs this one statement of
 // it, so the logit of vocabulary row j is the same bits in all of them by construction; tests/test_decode_bits_gpu.py pins
 // those bits to a recorded fixture.  The logits of rows f0 and f1 (f1 == f0: one row) for all B rows of `sx` are wave-uniform
@@ -465,7 +473,7 @@ struct LmP8 : LmP {
 template <int B, bool SAMPLE, class P>
 __device__ __forceinline__ void lm_row_pair(const P& p, const bf16* sx, int lane, int f0, int f1, float (&bv)[B], int (&bi)[B],
                                             float& y0, float& y1) {
-  constexpr bool F8 = std::is_same<P, LmP8>::value;
+  constexpr bool F8 = std::is_base_of<LmP8, P>::value;
   float h0[B], h1[B], l0[B], l1[B];
 #pragma unroll
   for (int b = 0; b < B; ++b) { h0[b] = 0.f; h1[b] = 0.f; l0[b] = 0.f; l1[b] = 0.f; }
@@ -544,6 +552,44 @@ __device__ __forceinline__ void lm_block_partials(const P& p, int lane, int w, c
   }
 }
 
+// LOGP: the log-sum-exp of z = float32(logit * tau) (tau = inv_t under sampling, else 1) rides along as a running pair (m, s),
+// m = max z so far, s = sum exp(z - m); the pair of nothing is (-inf, 0).  Every expf argument is <= 0, and m == -inf is tested
+// before a difference is formed, so neither a large logit nor two empty pairs make an inf - inf.  Accurate expf, like the
+// sampler's logarithms.  The order of the additions is fixed: a lane's units in its wave's order (row f0, then f1), the four waves
+// in order (lm_block_logp), the blocks in index order (dec_finish_kernel<true>), so a replay reproduces the bits.
+__device__ __forceinline__ void lse_push(float z, float& m, float& s) {
+  const float e = (m == -INFINITY || z == -INFINITY) ? 0.f : expf(-fabsf(z - m));
+  if (z > m) { s = __fadd_rn(__fmul_rn(s, e), 1.0f); m = z; }
+  else s = __fadd_rn(s, e);
+}
+__device__ __forceinline__ void lse_merge(float m2, float s2, float& m, float& s) {
+  const float M = fmaxf(m, m2);
+  if (M == -INFINITY) return;          // both empty: (m, s) stays (-inf, 0)
+  s = __fadd_rn(__fmul_rn(s, expf(m - M)), __fmul_rn(s2, expf(m2 - M)));
+  m = M;
+}
+
+// LOGP, after lm_block_partials (which leaves the waves' bests in sv / si): the block's (m, s) of every row from its four
+// waves' pairs in wave order, and the noise-free z of the candidate that lm_block_partials chose.
+template <int B, class P>
+__device__ __forceinline__ void lm_block_logp(const P& p, int lane, int w, float lm, float ls, float lz, const float (*sv)[B],
+                                              const int (*si)[B]) {
+  __shared__ float slp[4][B][3];
+  if (lane < B) { slp[w][lane][0] = lm; slp[w][lane][1] = ls; slp[w][lane][2] = lz; }
+  __syncthreads();
+  if (threadIdx.x < B) {
+    const int b = threadIdx.x;
+    float v = sv[0][b], m = slp[0][b][0], s = slp[0][b][1], z = slp[0][b][2];
+    int i = si[0][b];
+    for (int k = 1; k < 4; ++k) {
+      if (better(sv[k][b], si[k][b], v, i)) { v = sv[k][b]; i = si[k][b]; z = slp[k][b][2]; }
+      lse_merge(slp[k][b][0], slp[k][b][1], m, s);
+    }
+    float* o = p.plp + ((long long)blockIdx.x * B + b) * 3;
+    o[0] = m; o[1] = s; o[2] = z;
+  }
+}
+
 // The LM heads.  A unit is two vocabulary rows run through lm_row_pair by one wave; the heads differ only in which rows a unit
 // is and which wave takes it.
 // Full: unit u is rows 2u, 2u + 1 (the last unit of an odd V is one row), unit u = 4 blockIdx.x + w.  SAMPLE: the rows share the
@@ -554,8 +600,12 @@ __device__ __forceinline__ void lm_block_partials(const P& p, int lane, int w, c
 // without a unit writes the neutral partial and skips the norm.  An id outside [0, V) (a broken caller) is never used as an
 // address: its row is left out.  SAMPLE: row j takes word j & 1 of the Philox block (j >> 1, b, t, 0), as everywhere; the two
 // rows of a unit share a block only when they are 2m and 2m + 1.
-template <int B, bool SAMPLE, bool SUBSET, class P>
+// LOGP (SAMPLE instances only; p.samp may then be NULL: greedy): lane b also keeps row b's running (m, s) over z and the z of
+// its best candidate, and the block writes them to p.plp (lm_block_logp); pval / pidx / logits are those of the instance without
+// it, bit for bit.  A row whose id is outside [0, V) enters neither; the single row of an odd last unit enters once.
+template <int B, bool SAMPLE, bool SUBSET, class P, bool LOGP = false>
 __global__ __launch_bounds__(256) void dec_lm_head_kernel(P p) {
+  static_assert(SAMPLE || !LOGP, "LOGP: the lane-b-owns-row-b form only");
   __shared__ __attribute__((aligned(16))) bf16 sx[B * DEC_D];
   __shared__ float red[4];
   __shared__ float sv[4][B];
@@ -566,6 +616,10 @@ __global__ __launch_bounds__(256) void dec_lm_head_kernel(P p) {
     if (threadIdx.x < B) {
       p.pval[(long long)blockIdx.x * B + threadIdx.x] = -INFINITY;
       p.pidx[(long long)blockIdx.x * B + threadIdx.x] = 0x7fffffff;
+      if constexpr (LOGP) {
+        float* o = p.plp + ((long long)blockIdx.x * B + threadIdx.x) * 3;
+        o[0] = -INFINITY; o[1] = 0.f; o[2] = -INFINITY;
+      }
     }
     return;
   }
@@ -579,10 +633,11 @@ __global__ __launch_bounds__(256) void dec_lm_head_kernel(P p) {
   int lbi = 0x7fffffff;
   uint32_t seed_lo = 0, seed_hi = 0, step = 0;
   float inv_t = 0.f;
-  if (SAMPLE) {
+  if (SAMPLE && (!LOGP || p.samp)) {
     seed_lo = (uint32_t)p.samp[0]; seed_hi = (uint32_t)p.samp[1]; inv_t = __int_as_float(p.samp[2]);
     step = (uint32_t)p.state[0];
   }
+  float lm = -INFINITY, ls = 0.f, lz = -INFINITY;      // LOGP: lane b's (m, s) of row b and the z of its best candidate
   for (int u = SUBSET ? blockIdx.x + w * gridDim.x : blockIdx.x * 4 + w; u < units; u += gridDim.x * 4) {
     int f0, f1;
     if (SUBSET) {
@@ -597,45 +652,90 @@ __global__ __launch_bounds__(256) void dec_lm_head_kernel(P p) {
     float y0 = 0.f, y1 = 0.f;
     lm_row_pair<B, SAMPLE>(p, sx, lane, f0, f1, bv, bi, y0, y1);
     if (SAMPLE) {
+      float z0 = y0, z1 = y1;
+      if constexpr (LOGP) {
+        // z = float(logit * inv_t): fmaf(., ., 0) rounds once, like the product.  It is not written as the product the sampler
+        // forms, so that the sampler's product keeps its single use and the score compiles to what it compiles to in the
+        // instances without LOGP (there the compiler contracts product and sum into one fma): pval stays theirs bit for bit.
+        if (inv_t != 0.f) { z0 = __builtin_fmaf(y0, inv_t, 0.0f); z1 = __builtin_fmaf(y1, inv_t, 0.0f); }
+        lse_push(z0, lm, ls);
+        if (f1 != f0) lse_push(z1, lm, ls);
+      }
       if (inv_t != 0.f) {
         if (SUBSET) lap_sampling::gumbel_scores_at(y0, y1, inv_t, seed_lo, seed_hi, step, (uint32_t)lane, (uint32_t)f0, (uint32_t)f1, y0, y1);
         else lap_sampling::gumbel_scores(y0, y1, inv_t, seed_lo, seed_hi, step, (uint32_t)lane, (uint32_t)u, y0, y1);
       }
-      if (better(y0, f0, lbv, lbi)) { lbv = y0; lbi = f0; }
-      if (f1 != f0 && better(y1, f1, lbv, lbi)) { lbv = y1; lbi = f1; }
+      if (better(y0, f0, lbv, lbi)) { lbv = y0; lbi = f0; if constexpr (LOGP) lz = z0; }
+      if (f1 != f0 && better(y1, f1, lbv, lbi)) { lbv = y1; lbi = f1; if constexpr (LOGP) lz = z1; }
     }
   }
   lm_block_partials<B, SAMPLE>(p, lane, w, bv, bi, lbv, lbi, sv, si);
+  if constexpr (LOGP) lm_block_logp<B>(p, lane, w, lm, ls, lz, sv, si);
 }
 
 // one block: per sample, the best of the partials (lowest index among ties); then out[:, t], EOS mask, t + 1, done.
+// LOGP (nblk <= LM_BLOCKS): also logp[b][t] = z_tok - (M + logf(S)) from the LM head's plp partials {m, s, z of the block's best}.
+// The reduction carries the block index k of the best partial (a payload: the choice is unchanged), z_tok is that block's z.  M =
+// max of the blocks' m (exact in any order); the terms s_k expf(m_k - M) (an empty block's is 0) are formed by all threads and
+// added by lane b for row b in block index order.
+template <bool LOGP>
 __global__ __launch_bounds__(256) void dec_finish_kernel(int* state, const float* pval, const int* pidx, int nblk, int* out, int cap,
-                                                         int B, int eos_token) {
+                                                         int B, int eos_token, const float* plp, float* logp) {
   __shared__ float sv[4];
   __shared__ int si[4];
   __shared__ int tok[DEC_MAXB];
+  __shared__ float sm[LOGP ? 4 : 1], term[LOGP ? DEC_MAXB : 1][LOGP ? LM_BLOCKS + 1 : 1], lpv[LOGP ? DEC_MAXB : 1][2];
+  __shared__ int sk[LOGP ? 4 : 1];
   if (state[1]) return;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   for (int b = 0; b < B; ++b) {
     float v = -INFINITY;
     int i = 0x7fffffff;
+    int kb = 0;
+    float M = -INFINITY;
     for (int k = threadIdx.x; k < nblk; k += 256) {
       const float pv = pval[(long long)k * B + b];
       const int pi = pidx[(long long)k * B + b];
-      if (better(pv, pi, v, i)) { v = pv; i = pi; }
+      if (better(pv, pi, v, i)) { v = pv; i = pi; if constexpr (LOGP) kb = k; }
+      if constexpr (LOGP) M = fmaxf(M, plp[((long long)k * B + b) * 3]);
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
       const float ov = __shfl_xor(v, o, 64);
       const int oi = __shfl_xor(i, o, 64);
+      if constexpr (LOGP) {
+        const int ok = __shfl_xor(kb, o, 64);
+        if (better(ov, oi, v, i)) kb = ok;
+        M = fmaxf(M, __shfl_xor(M, o, 64));
+      }
       if (better(ov, oi, v, i)) { v = ov; i = oi; }
     }
-    if (lane == 0) { sv[w] = v; si[w] = i; }
+    if (lane == 0) {
+      sv[w] = v; si[w] = i;
+      if constexpr (LOGP) { sk[w] = kb; sm[w] = M; }
+    }
     __syncthreads();
+    if constexpr (LOGP) {
+      M = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
+      for (int k = threadIdx.x; k < nblk; k += 256) {
+        const float* q = plp + ((long long)k * B + b) * 3;
+        term[b][k] = q[0] == -INFINITY ? 0.f : __fmul_rn(q[1], expf(q[0] - M));
+      }
+    }
     if (threadIdx.x == 0) {
       for (int k = 1; k < 4; ++k)
-        if (better(sv[k], si[k], v, i)) { v = sv[k]; i = si[k]; }
+        if (better(sv[k], si[k], v, i)) { v = sv[k]; i = si[k]; if constexpr (LOGP) kb = sk[k]; }
       tok[b] = i;
+      if constexpr (LOGP) { lpv[b][0] = M; lpv[b][1] = plp[((long long)kb * B + b) * 3 + 2]; }
+    }
+    __syncthreads();
+  }
+  if constexpr (LOGP) {
+    if (threadIdx.x < B) {
+      const int b = threadIdx.x;
+      float S = 0.f;
+      for (int k = 0; k < nblk; ++k) S = __fadd_rn(S, term[b][k]);
+      lpv[b][1] = lpv[b][1] - (lpv[b][0] + logf(S));
     }
     __syncthreads();
   }
@@ -644,6 +744,7 @@ __global__ __launch_bounds__(256) void dec_finish_kernel(int* state, const float
     if (t >= cap) { state[1] = 1; return; }
     int all = 1;
     for (int b = 0; b < B; ++b) {
+      if constexpr (LOGP) logp[(long long)b * cap + t] = lpv[b][1];
       out[(long long)b * cap + t] = tok[b];
       const int e = state[8 + b] | (tok[b] == eos_token ? 1 : 0);
       state[8 + b] = e;
@@ -765,17 +866,18 @@ int proj_residual_impl(const int* state, const void* a, const void* w, const flo
   return kwaves == 4 ? launch_proj<EPI_RES, false, 4>(p, f8, B, grid, stream) : launch_proj<EPI_RES, false, 1>(p, f8, B, grid, stream);
 }
 
-template <bool SAMPLE, bool SUBSET, class P>
+template <bool SAMPLE, bool SUBSET, class P, bool LOGP = false>
 int launch_lm_head(const P& p, int B, void* stream) {
-  DISPATCH_B(B, hipLaunchKernelGGL((dec_lm_head_kernel<BB, SAMPLE, SUBSET, P>), dim3(LM_BLOCKS), dim3(256), 0, S_, p));
+  DISPATCH_B(B, hipLaunchKernelGGL((dec_lm_head_kernel<BB, SAMPLE, SUBSET, P, LOGP>), dim3(LM_BLOCKS), dim3(256), 0, S_, p));
   LAP_CHECK_LAUNCH();
   return LAP_OK;
 }
 
 // sampling == NULL: the greedy head.  f8: `hi` holds the code plane, `lo` is not used.  subset: the head over ids[0 .. n).
+// plp != NULL: the LOGP instances (the sampling form of the kernel, which is the greedy head while sampling is NULL or inv_t == 0).
 int lm_head_impl(const int* state, const int* sampling, bool sample, const void* x, const float* gamma, const void* hi, const void* lo,
                  const float* wscale, bool f8, int B, int D, int V, float eps, float* logits, float* pval, int* pidx, void* stream,
-                 bool subset = false, const int* ids = nullptr, int n = 0) {
+                 bool subset = false, const int* ids = nullptr, int n = 0, float* plp = nullptr) {
   if (!state || (sample && !sampling) || !gamma || !hi || !pval || !pidx || B < 1 || B > DEC_MAXB || D != DEC_D || V < 2 ||
       !aligned16(x) || !aligned16(hi) || (lo && !aligned16(lo)) || (f8 && (!wscale || !f8_k_ok(D, 1))) ||
       (subset && (!ids || n < 1 || n > V))) return LAP_ERR_ARG;
@@ -783,6 +885,18 @@ int lm_head_impl(const int* state, const int* sampling, bool sample, const void*
   p.state = state; p.x = (const bf16*)x; p.gamma = gamma; p.eps = eps; p.hi = (const bf16*)hi; p.lo = f8 ? nullptr : (const bf16*)lo;
   p.V = V; p.D = D; p.logits = logits; p.pval = pval; p.pidx = pidx; p.samp = sampling; p.ids = ids; p.n = n;
   p.wscale = wscale;
+  if (plp) {
+    LmLogP<LmP> q{};
+    LmLogP<LmP8> q8{};
+    static_cast<LmP&>(q) = p; static_cast<LmP8&>(q8) = p;
+    q.plp = q8.plp = plp;
+    switch ((f8 ? 2 : 0) | (subset ? 1 : 0)) {
+      case 0: return launch_lm_head<true, false, LmLogP<LmP>, true>(q, B, stream);
+      case 1: return launch_lm_head<true, true, LmLogP<LmP>, true>(q, B, stream);
+      case 2: return launch_lm_head<true, false, LmLogP<LmP8>, true>(q8, B, stream);
+      default: return launch_lm_head<true, true, LmLogP<LmP8>, true>(q8, B, stream);
+    }
+  }
   switch ((sample ? 4 : 0) | (f8 ? 2 : 0) | (subset ? 1 : 0)) {
     case 0: return launch_lm_head<false, false, LmP>(p, B, stream);
     case 1: return launch_lm_head<false, true, LmP>(p, B, stream);
@@ -878,7 +992,8 @@ extern "C" int lap_decode_lm_head_sample(const int* state, const int* sampling, 
 extern "C" int lap_decode_finish(int* state, const float* pval, const int* pidx, int* out, int B, int cap, int eos_token,
                                  void* stream) {
   if (!state || !pval || !pidx || !out || B < 1 || B > DEC_MAXB || cap < 1) return LAP_ERR_ARG;
-  hipLaunchKernelGGL(dec_finish_kernel, dim3(1), dim3(256), 0, S_, state, pval, pidx, LM_BLOCKS, out, cap, B, eos_token);
+  hipLaunchKernelGGL(dec_finish_kernel<false>, dim3(1), dim3(256), 0, S_, state, pval, pidx, LM_BLOCKS, out, cap, B, eos_token,
+                     (const float*)nullptr, (float*)nullptr);
   LAP_CHECK_LAUNCH();
   return LAP_OK;
 }
@@ -943,4 +1058,21 @@ extern "C" int lap_decode_lm_head_subset_sample_fp8(const int* state, const int*
                                                     const void* w8, const float* wscale, const int* ids, int n, int B, int D, int V,
                                                     float eps, float* logits, float* pval, int* pidx, void* stream) {
   return lm_head_impl(state, sampling, true, x, gamma, w8, nullptr, wscale, true, B, D, V, eps, logits, pval, pidx, stream, true, ids, n);
+}
+
+// ---- token log-probabilities: one LM head for every form that also leaves the log-sum-exp partials, and the finish that reads them
+extern "C" int lap_decode_lm_head_lp(const int* state, const int* sampling, const void* x, const float* gamma, const void* hi,
+                                     const void* lo, const float* wscale, const int* ids, int n, int B, int D, int V, float eps,
+                                     float* logits, float* pval, int* pidx, float* plp, void* stream) {
+  if (!plp || (wscale && lo)) return LAP_ERR_ARG;
+  return lm_head_impl(state, sampling, false, x, gamma, hi, lo, wscale, wscale != nullptr, B, D, V, eps, logits, pval, pidx, stream,
+                      ids != nullptr, ids, n, plp);
+}
+
+extern "C" int lap_decode_finish_lp(int* state, const float* pval, const int* pidx, const float* plp, int* out, float* logp, int B,
+                                    int cap, int eos_token, void* stream) {
+  if (!state || !pval || !pidx || !plp || !out || !logp || B < 1 || B > DEC_MAXB || cap < 1) return LAP_ERR_ARG;
+  hipLaunchKernelGGL(dec_finish_kernel<true>, dim3(1), dim3(256), 0, S_, state, pval, pidx, LM_BLOCKS, out, cap, B, eos_token, plp, logp);
+  LAP_CHECK_LAUNCH();
+  return LAP_OK;
 }

@@ -240,6 +240,8 @@ SIGNATURES: dict[str, list] = {
     "lap_decode_lm_head_subset_sample": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
     "lap_decode_lm_head_subset_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
     "lap_decode_lm_head_subset_sample_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
+    "lap_decode_lm_head_lp": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp],
+    "lap_decode_finish_lp": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
 }
 
 _fn = {}
@@ -1505,8 +1507,9 @@ def _ids_req(ids, V):
         raise ValueError(f"ids: expected 1 <= n <= V = {V} ids in one dimension, got shape {tuple(ids.shape)}")
 
 
-def _decode_lm_head(fn, sampling, state, x, gamma, hi, lo, pval, pidx, logits, eps, wscale, ids):
-    """The body of `decode_lm_head` (sampling None) and `decode_lm_head_sample`; `fn` names the caller in error messages."""
+def _decode_lm_head(fn, sampling, state, x, gamma, hi, lo, pval, pidx, logits, eps, wscale, ids, plp=None):
+    """The body of `decode_lm_head` (sampling None), `decode_lm_head_sample` and `decode_lm_head_lp` (plp given); `fn` names the
+    caller in error messages."""
     _dreq(x, torch.bfloat16, "x"); _dreq(gamma, torch.float32, "gamma")
     smp, lead = "", (_p(state),)
     if sampling is not None:
@@ -1531,6 +1534,13 @@ def _decode_lm_head(fn, sampling, state, x, gamma, hi, lo, pval, pidx, logits, e
         if lo is not None:
             _dreq(lo, torch.bfloat16, "lo")
         planes, f8 = (_p(hi), _p(lo)), ""
+    if plp is not None:     # one entry point for every form
+        _dreq(plp, torch.float32, "plp")
+        if plp.numel() < 3 * B * _fn["lap_decode_lm_blocks"]():
+            raise TypeError(f"{fn}: plp holds f32 [lap_decode_lm_blocks()][B][3]")
+        call("lap_decode_lm_head_lp", _p(state), _p(sampling), _p(x), _p(gamma), _p(hi), _p(lo), _p(wscale), _p(ids),
+             0 if ids is None else ids.numel(), B, D, hi.shape[0], float(eps), _p(logits), _p(pval), _p(pidx), _p(plp))
+        return
     call(f"lap_decode_lm_head{sub}{smp}{f8}", *lead, _p(x), _p(gamma), *planes, *tail, B, D, hi.shape[0], float(eps), _p(logits),
          _p(pval), _p(pidx))
 
@@ -1566,3 +1576,25 @@ def decode_lm_head_sample(state, sampling, x, gamma, hi, lo, pval, pidx, logits=
 
 def decode_finish(state, pval, pidx, out, eos_token):
     call("lap_decode_finish", _p(state), _p(pval), _p(pidx), _p(out), out.shape[0], out.shape[1], int(eos_token))
+
+
+def decode_lm_logp_partials(B, device):
+    """The log-sum-exp partials of `decode_lm_head_lp`: f32 [lap_decode_lm_blocks(), B, 3] = {m, s, z of the block's best}."""
+    return torch.empty((_fn["lap_decode_lm_blocks"](), B, 3), dtype=torch.float32, device=device)
+
+
+def decode_lm_head_lp(state, sampling, x, gamma, hi, lo, pval, pidx, plp, logits=None, eps=1e-6, wscale=None, ids=None):
+    """`decode_lm_head` (sampling None) or `decode_lm_head_sample` of the same arguments, with the same pval / pidx / logits bit
+    for bit, that also leaves the log-sum-exp partials of z = logit * inv_t (the raw logits when greedy) in `plp` for
+    `decode_finish_lp` (lap_decode_lm_head_lp).  ids must be distinct (as `ar_decode.check_allowed_tokens` delivers them): a
+    repeated id would enter the sum once per occurrence, while `sampling.token_logprobs` counts a set."""
+    _decode_lm_head("decode_lm_head_lp", sampling, state, x, gamma, hi, lo, pval, pidx, logits, eps, wscale, ids, plp=plp)
+
+
+def decode_finish_lp(state, pval, pidx, plp, out, logp, eos_token):
+    """`decode_finish` that also writes logp[:, t], the log-probability of the chosen token under the noise-free softmax of z
+    (lap_amd/sampling.py `token_logprobs`).  logp: f32 [B, cap] beside out; columns never written keep what they held."""
+    _dreq(plp, torch.float32, "plp"); _dreq(logp, torch.float32, "logp")
+    if tuple(logp.shape) != tuple(out.shape):
+        raise TypeError(f"decode_finish_lp: logp {tuple(logp.shape)} beside out {tuple(out.shape)}")
+    call("lap_decode_finish_lp", _p(state), _p(pval), _p(pidx), _p(plp), _p(out), _p(logp), out.shape[0], out.shape[1], int(eos_token))

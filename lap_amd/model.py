@@ -692,7 +692,8 @@ class LAP:
             self.serving_cache.refresh()
 
     def sample_tokens(self, rng, observation, *, max_decoding_steps: int = 390, temperature: float = 0.0, collect=None,
-                      decode: str = "eager", sampler: str = "host", decode_weights: str = "bf16", allowed_tokens=None):
+                      decode: str = "eager", sampler: str = "host", decode_weights: str = "bf16", allowed_tokens=None,
+                      return_logprobs: bool = False, num_samples=None):
         """lap.py:678-766 (LAP_AR serving mode): VLM-only prefill, then single-token decode until every sample has emitted
         EOS or `max_decoding_steps` tokens; returns int32 [B, max_decoding_steps] (zeros after the stop).
 
@@ -736,11 +737,25 @@ class LAP:
         -inf outside the set; under sampler="device" the noise of index j stays that of j.  decode="fused" streams only the
         set's rows of the LM head (lap_decode_lm_head_subset*), with logits equal to the unconstrained kernel's bit for bit;
         decode="eager" masks its stored logits.  `collect["logit/<t>"]` is full width with -inf outside the set.
-        `policy_io.allowed_token_ids` builds a set from example language actions."""
+        `policy_io.allowed_token_ids` builds a set from example language actions.
+
+        return_logprobs: False (default): the tokens alone, on the launches of before.  True: (tokens, logprobs), logprobs f32
+        [B, max_decoding_steps] beside the tokens (column 0, the token of the prefill's logits, included; zeros where nothing
+        was written): the log-probability of each token under the noise-free softmax of z = float32(logit * inv_t) (tau = 1 for
+        a greedy decode) over the vocabulary, or over the allowed set.  decode="eager" takes a float32 log_softmax of its stored
+        logits; decode="fused" folds the log-sum-exp into the LM-head pass (lap_decode_lm_head_lp / lap_decode_finish_lp: no
+        logit is stored, no launch is added).  `sampling.token_logprobs` restates it, `sampling.sequence_logprob` sums a row up
+        to its EOS.  The reference has no such output.
+
+        num_samples: best-of-N.  None (default): one decode per observation row.  1 <= N <= 8 (observation of batch 1,
+        decode="fused", sampler="device", temperature > 0; anything else raises ValueError): the prefix is prefilled once, its
+        K / V, key-info words and last row are copied to N rows, and the N rows decode as one fused batch under `rng`, row b
+        drawing with Philox row index b as any batch row does.  Returns (tokens [N, steps], logprobs [N, steps]);
+        `sampling.select_best` picks the answer."""
         from lap_amd import ar_decode       # (it imports this module)
         return ar_decode.sample_tokens(self, rng, observation, max_decoding_steps=max_decoding_steps, temperature=temperature,
                                        collect=collect, decode=decode, sampler=sampler, decode_weights=decode_weights,
-                                       allowed_tokens=allowed_tokens)
+                                       allowed_tokens=allowed_tokens, return_logprobs=return_logprobs, num_samples=num_samples)
 
     DECODE_WEIGHTS = ("bf16", "fp8", "fp8_layers")
 

@@ -107,3 +107,60 @@ def sample_from_logits(logits, temperature: float, seed: int, step: int) -> np.n
     """int32 [rows]: the token every row of float32 `logits` [rows, V] draws at decode step `step` under `seed`; the argmax
     (lowest index among ties) when temperature <= 0."""
     return np.argmax(scores_from_logits(logits, temperature, seed, step), axis=-1).astype(np.int32)
+
+
+# ---- token log-probabilities and best-of-N selection (the specification of lap_decode_lm_head_lp / lap_decode_finish_lp)
+def token_logprobs(logits, tokens, temperature: float, allowed=None) -> np.ndarray:
+    """float64 [rows]: log softmax(z)[token] per row of float32 `logits` [rows, V], where z = float32(logit * inv_t) is the product
+    the sampler forms (z = logit when temperature <= 0: a greedy decode scores its tokens at tau = 1) and everything after that
+    product is float64.  allowed: the softmax runs over these vocabulary ids only (a constrained decode); a token outside the set
+    has log-probability -inf.  The noise of a draw plays no part: this is the probability of the token, not of the draw."""
+    lg = np.ascontiguousarray(np.asarray(logits, dtype=np.float32))
+    if lg.ndim != 2:
+        raise ValueError("logits: [rows, vocab_size]")
+    tok = np.asarray(tokens).reshape(-1).astype(np.int64)
+    if tok.shape[0] != lg.shape[0]:
+        raise ValueError(f"tokens: one per row of logits, got {tok.shape[0]} for {lg.shape[0]} rows")
+    inv_t = inverse_temperature(temperature)
+    z = (lg * inv_t if inv_t != 0.0 else lg).astype(np.float64)
+    rows = np.arange(lg.shape[0])
+    z_tok = z[rows, tok]
+    if allowed is not None:
+        ids = np.unique(np.asarray(allowed).reshape(-1).astype(np.int64))
+        ids = ids[(ids >= 0) & (ids < lg.shape[1])]
+        if ids.size == 0:
+            raise ValueError("allowed: no id inside the vocabulary")
+        z_tok = np.where(np.isin(tok, ids), z_tok, -np.inf)
+        z = z[:, ids]
+    m = z.max(axis=1)
+    return z_tok - (m + np.log(np.exp(z - m[:, None]).sum(axis=1)))
+
+
+def _counted(tokens, eos: int) -> np.ndarray:
+    """bool [rows, steps]: the positions of a row up to and including its first EOS (all of them when it has none)."""
+    tok = np.asarray(tokens)
+    if tok.ndim != 2:
+        raise ValueError("tokens: [rows, steps]")
+    after = np.cumsum(tok == eos, axis=1) - (tok == eos)        # EOS tokens strictly before a position
+    return after == 0
+
+
+def sequence_logprob(tokens, logprobs, eos: int) -> np.ndarray:
+    """float64 [rows]: the sum of a row's token log-probabilities up to and including its first `eos` token, or over the whole
+    row when it has none (a decode keeps writing a finished row until every row has finished: those tokens do not count)."""
+    lp = np.asarray(logprobs, dtype=np.float64)
+    keep = _counted(tokens, eos)
+    if lp.shape != keep.shape:
+        raise ValueError(f"logprobs {lp.shape} beside tokens {keep.shape}")
+    return np.where(keep, lp, 0.0).sum(axis=1)
+
+
+def select_best(tokens, logprobs, eos: int, rule: str = "sum") -> int:
+    """The row a best-of-N request answers with: the largest `sequence_logprob` ("sum") or that sum divided by the number of
+    tokens counted ("mean", which does not favour short answers); the lowest row among ties."""
+    if rule not in ("sum", "mean"):
+        raise ValueError(f"select_best: rule must be 'sum' or 'mean', got {rule!r}")
+    score = sequence_logprob(tokens, logprobs, eos)
+    if rule == "mean":
+        score = score / _counted(tokens, eos).sum(axis=1)
+    return int(np.argmax(score))

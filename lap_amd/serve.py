@@ -104,10 +104,26 @@ class GraphedTokenDecoder:
     when the parameters have changed.  Composes with sampling=True.
 
     allowed_tokens: `sample_tokens`' constrained decoding, fixed at construction (the graphs hold the address of the id buffer):
-    every call decodes inside that set.  None: the whole vocabulary.  Composes with sampling= and weights=."""
+    every call decodes inside that set.  None: the whole vocabulary.  Composes with sampling= and weights=.
+
+    logprobs=True: `sample_tokens`' `return_logprobs`: both graphs are captured on the LM head that also leaves the log-sum-exp
+    partials (no further launch), the log-probability buffer lives beside the context's `out`, and a call returns
+    (tokens, logprobs), both fresh tensors.  Composes with sampling=, weights= and allowed_tokens=.
+
+    num_samples=N (1 <= N <= 8; batch_size 1, sampling=True): `sample_tokens`' best-of-N.  The prefill graph runs at B = 1 and
+    ends with the copies of its prefix K / V, key-info words and last row to N rows; the step graph runs at B = N.  A call
+    (temperature > 0) returns (tokens [N, steps], logprobs [N, steps])."""
 
     def __init__(self, model: LAP, batch_size: int = 1, max_decoding_steps: int = 390, prompt_len: int | None = None,
-                 steps_per_replay: int = 8, sampling: bool = False, weights: str = "bf16", allowed_tokens=None):
+                 steps_per_replay: int = 8, sampling: bool = False, weights: str = "bf16", allowed_tokens=None,
+                 logprobs: bool = False, num_samples=None):
+        self.N = None
+        if num_samples is not None:
+            if not sampling:
+                raise ValueError("GraphedTokenDecoder: num_samples needs a decoder built with sampling=True")
+            self.N = ar_decode.check_num_samples(num_samples, batch_size, decode="fused", sampler="device", temperature=1.0)
+            ar_decode.check_fused_decode(model, self.N)
+        self.logprobs = bool(logprobs) or self.N is not None
         ar_decode.check_fused_decode(model, batch_size)
         ar_decode.check_decode_weights(weights)
         self.weights = weights
@@ -141,9 +157,11 @@ class GraphedTokenDecoder:
 
     def _prefill(self):
         pre = ar_decode.prefill(self.model, self.obs)
+        if self.N is not None:
+            pre = ar_decode.replicate_prefill(pre, self.N)
         if self.ctx is None:
-            self.ctx = ar_decode.DecodeCtx(self.model, self.B, pre.Pn, self.max_steps, self.sampling, self.weights,
-                                           allowed=self.allowed)
+            self.ctx = ar_decode.DecodeCtx(self.model, pre.B, pre.Pn, self.max_steps, self.sampling, self.weights,
+                                           allowed=self.allowed, logprobs=self.logprobs)
         self.ctx.first_token(pre)
 
     def _steps(self):
@@ -170,9 +188,11 @@ class GraphedTokenDecoder:
         torch.cuda.synchronize()
         return self
 
-    def __call__(self, obs: CoTObservation, *, temperature: float = 0.0, seed: int = 0) -> torch.Tensor:
+    def __call__(self, obs: CoTObservation, *, temperature: float = 0.0, seed: int = 0):
         if temperature > 0.0 and not self.sampling:
             raise ValueError("GraphedTokenDecoder: temperature > 0 needs a decoder built with sampling=True")
+        if self.N is not None and not temperature > 0.0:
+            raise ValueError(f"GraphedTokenDecoder: num_samples needs temperature > 0 (greedy candidates are all the same), got {temperature!r}")
         if self.g_step is None:
             self.capture()
         # merged LoRA weights / fp8 decode weights / packed prefill images the graphs hold addresses of follow the parameters in place
@@ -185,6 +205,8 @@ class GraphedTokenDecoder:
             if bool(self.ctx.state[1].item()):      # one host read per replay
                 break
             self.g_step.replay()
+        if self.logprobs:
+            return self.ctx.out.clone(), self.ctx.logp.clone()
         return self.ctx.out.clone()
 
 
@@ -342,10 +364,25 @@ class ARPolicy:
         # device once, here; the decoder is captured with it and sample_tokens gets the checked set on every call
         if self._sample_kwargs.get("allowed_tokens") is not None:
             self._sample_kwargs["allowed_tokens"] = ar_decode.allowed_set(base.model, self._sample_kwargs["allowed_tokens"])
-        if use_graph and base.model.decode_supported(1):
+        # sample_kwargs["return_logprobs"] adds "token_logprobs" and "logprob" (the sum up to the EOS) to a result;
+        # sample_kwargs["num_samples"] = N decodes N candidates per request (best-of-N: decode="fused", sampler="device",
+        # temperature > 0), answers with the one sample_kwargs["select"] ("sum", the default, or "mean": sampling.select_best)
+        # picks, and reports all of them under "candidates".  Both reach either route; "select" is ARPolicy's own key.
+        self._select = self._sample_kwargs.pop("select", "sum")
+        if self._select not in ("sum", "mean"):
+            raise ValueError(f"ARPolicy: select must be 'sum' or 'mean', got {self._select!r}")
+        self._num_samples = self._sample_kwargs.get("num_samples")
+        self._logprobs = bool(self._sample_kwargs.get("return_logprobs", False)) or self._num_samples is not None
+        if self._num_samples is not None:
+            self._sample_kwargs.setdefault("decode", "fused")
+            ar_decode.check_num_samples(self._num_samples, 1, decode=self._sample_kwargs["decode"],
+                                        sampler=self._sample_kwargs.get("sampler", "host"),
+                                        temperature=self._sample_kwargs.get("temperature", 0.0))
+        if use_graph and base.model.decode_supported(self._num_samples or 1):
             self._decoder = GraphedTokenDecoder(base.model, 1, self._sample_kwargs.get("max_decoding_steps", 390),
                                                 sampling=self._device_sampler, weights=weights,
-                                                allowed_tokens=self._sample_kwargs.get("allowed_tokens"))
+                                                allowed_tokens=self._sample_kwargs.get("allowed_tokens"),
+                                                logprobs=self._logprobs, num_samples=self._num_samples)
 
     def __getattr__(self, name):
         return getattr(self._base, name)
@@ -367,10 +404,24 @@ class ARPolicy:
             tokens = self._decoder(o, temperature=temperature, seed=self._calls) if self._device_sampler else self._decoder(o)
         else:
             tokens = base.model.sample_tokens(self._calls, o, **self._sample_kwargs)
-        out = {"state": batched.get("state"), "tokens": tokens.cpu().numpy(), "raw_state": raw_state}
+        extra = {}
+        if self._logprobs:
+            from lap_amd import sampling
+
+            tokens, logp = (t.cpu().numpy() for t in tokens)
+            eos = base.model.EOS_TOKEN
+            seq = sampling.sequence_logprob(tokens, logp, eos)
+            if self._num_samples is not None:     # the answer is one candidate, as a batch of 1; all of them are reported
+                extra["candidates"] = {"tokens": tokens, "logprob": seq}
+                best = sampling.select_best(tokens, logp, eos, self._select)
+                tokens, logp, seq = tokens[best:best + 1], logp[best:best + 1], seq[best:best + 1]
+            extra |= {"token_logprobs": logp, "logprob": seq}
+            out = {"state": batched.get("state"), "tokens": tokens, "raw_state": raw_state} | extra
+        else:
+            out = {"state": batched.get("state"), "tokens": tokens.cpu().numpy(), "raw_state": raw_state}
         model_ms = (time.perf_counter() - t0) * 1e3
-        if base._has_transforms:
-            out = base._output_transform(out)
+        if base._has_transforms:      # (the output stack keeps the keys it knows, CoTOutputs: actions and reasoning; the
+            out = base._output_transform(out) | extra       # log-probabilities and the candidates go round it to the client)
         out["policy_timing"] = {"infer_ms": model_ms}
         return out
 
@@ -390,7 +441,12 @@ def create_trained_policy_ar(*args, sample_kwargs: dict | None = None, language_
     ar_graph: serve greedy requests through a GraphedTokenDecoder (ARPolicy(use_graph=True)); off by default.  With
     sample_kwargs={"temperature": T, "sampler": "device"} the same graphs serve sampled requests too;
     sample_kwargs={"decode_weights": "fp8" | "fp8_layers"} decodes on fp8 weights (implies decode="fused") on either route;
-    sample_kwargs={"allowed_tokens": ids} constrains every token to that set on either route (`policy_io.allowed_token_ids`)."""
+    sample_kwargs={"allowed_tokens": ids} constrains every token to that set on either route (`policy_io.allowed_token_ids`);
+    sample_kwargs={"return_logprobs": True} adds "token_logprobs" (f32 [1, steps]) and "logprob" (the sum up to the EOS) to the
+    result; sample_kwargs={"num_samples": N, "select": "sum" | "mean"} (with "temperature" > 0 and "sampler": "device"; implies
+    decode="fused") decodes N candidates per request, runs the output transforms on the one `sampling.select_best` picks and
+    reports all N under "candidates": {"tokens" [N, steps], "logprob" [N]}.  These keys are added to what the output stack
+    returns ({"actions", "reasoning"}), so a client of this policy and of the websocket server receives them."""
     from lap_amd import policy_io as pio
 
     base = create_trained_policy(*args, use_graph=False, **kwargs)

@@ -4,7 +4,7 @@ rate against the 6.29 TB/s measured copy rate.  Random weights, the reference pr
 run decodes N tokens.  One JSON line.
 
     python tools/bench_ar.py [--tokens 64] [--config lap_bench] [--kwaves 4] [--temperature T] [--weights bf16 fp8 fp8_layers]
-                             [--allowed N]
+                             [--allowed N] [--logprobs] [--num-samples N]
 
 --temperature T > 0 adds the sampled figures: the eager loop with the torch-generator noise (sampler="host"), the eager loop and
 the fused steps with the device noise (sampler="device"), and a GraphedTokenDecoder(sampling=True) called sampled and greedy.
@@ -17,6 +17,12 @@ graphed tokens agree with the bf16 graph's, and the relative error of its first 
 bf16 and every --weights value, in the same process, the graphed ms per token without and with the set (the mean and the
 [min, max] of the timed repeats, which is the run-to-run spread to read the difference against), the bytes per token with the
 set and whether every constrained token lies in it.  --profile-graphed --allowed N replays the constrained graph.
+--logprobs adds the greedy decode with `return_logprobs=True` (the LM head that also leaves the log-sum-exp partials): fused and
+graphed ms per token, next to the plain figures of the same process.
+--num-samples N adds best-of-N (`num_samples=N`, sampled at --temperature or at 1.0): fused and graphed ms per token of the N
+rows, next to one sampled row with log-probabilities on the same kernels, and both prefill graphs (the N-row one ends with the copies).
+The fused best-of-N figure subtracts the plain batch-1 prefill, so the copies to N rows and the allocation of the N-row context are
+spread into its ms per token; the graphed figures subtract their own prefill graph and are the ones to quote.
 """
 import argparse
 import json
@@ -42,6 +48,9 @@ ap.add_argument("--temperature", type=float, default=0.0, help="> 0: also measur
 ap.add_argument("--weights", nargs="+", default=["bf16"], choices=list(LAP.DECODE_WEIGHTS),
                 help="decode weights to measure next to bf16 (fp8, fp8_layers)")
 ap.add_argument("--allowed", type=int, default=0, help="> 0: also measure constrained decoding over the N lowest token ids")
+ap.add_argument("--logprobs", action="store_true", help="also measure greedy decoding that returns token log-probabilities")
+ap.add_argument("--num-samples", type=int, default=0, help="N > 0: also measure best-of-N (N rows from one batch-1 prefill); "
+                "sampled at --temperature, or at 1.0 when that is 0")
 a = ap.parse_args()
 hip.DECODE_KWAVES_DOWN = a.kwaves
 
@@ -162,6 +171,36 @@ if T > 0.0:
         "graphed_greedy_on_sampling_graph_ms_per_token": round(per(t_sgreedy, t_spre), 3),
         "graphed_sampled_equals_fused_sampled": bool(torch.equal(sgot, st(sampler="device", decode="fused")())),
         "greedy_on_sampling_graph_equals_graphed": bool(torch.equal(sdec(o), got))}
+logprobs = {}
+if a.logprobs:          # the same greedy decode with return_logprobs=True: what the log-sum-exp in the LM head and the finish cost
+    t_lfused = timeit(lambda: model.sample_tokens(0, o, max_decoding_steps=N, decode="fused", return_logprobs=True), a.reps)
+    ldec = GraphedTokenDecoder(model, 1, N, logprobs=True).capture()
+    t_lpre = timeit(lambda: (ldec.g_prefill.replay()), a.reps)
+    t_lgraph = timeit(lambda: ldec(o), a.reps)
+    ltok, llp = ldec(o)
+    logprobs = {"logprobs": {
+        "fused_ms_per_token": round(per(t_lfused, t_pre), 3), "graphed_ms_per_token": round(per(t_lgraph, t_lpre), 3),
+        "graphed_ms_per_token_over_plain": round(per(t_lgraph, t_lpre) / g_ms, 4),
+        "tokens_equal_to_plain_graph": bool(torch.equal(ltok, got)), "mean_token_logprob": round(float(llp.mean()), 4)}}
+best_of = {}
+if a.num_samples > 0:   # N rows from one batch-1 prefill against one sampled row on the same kernels (both return log-probabilities)
+    Tn = T if T > 0.0 else 1.0
+    skw = dict(max_decoding_steps=N, temperature=Tn, sampler="device", decode="fused")
+    t_one = timeit(lambda: model.sample_tokens(1, o, return_logprobs=True, **skw), a.reps)
+    t_n = timeit(lambda: model.sample_tokens(1, o, num_samples=a.num_samples, **skw), a.reps)
+    one = GraphedTokenDecoder(model, 1, N, sampling=True, logprobs=True).capture()
+    ndec = GraphedTokenDecoder(model, 1, N, sampling=True, num_samples=a.num_samples).capture()
+    t_1pre, t_npre = (timeit(lambda d=d: (d.g_prefill.replay()), a.reps) for d in (one, ndec))
+    t_1graph = timeit(lambda: one(o, temperature=Tn, seed=1), a.reps)
+    t_ngraph = timeit(lambda: ndec(o, temperature=Tn, seed=1), a.reps)
+    ntok, _ = ndec(o, temperature=Tn, seed=1)
+    best_of = {"best_of": {
+        "num_samples": a.num_samples, "temperature": Tn,
+        "one_row_fused_ms_per_token": round(per(t_one, t_pre), 3), "fused_ms_per_token": round(per(t_n, t_pre), 3),
+        "one_row_graphed_ms_per_token": round(per(t_1graph, t_1pre), 3), "graphed_ms_per_token": round(per(t_ngraph, t_npre), 3),
+        "graphed_ms_per_token_over_one_row": round(per(t_ngraph, t_npre) / per(t_1graph, t_1pre), 4),
+        "one_row_graphed_prefill_ms": round(t_1pre, 3), "graphed_prefill_ms": round(t_npre, 3),
+        "distinct_rows": len({tuple(r) for r in ntok.tolist()})}}
 print(json.dumps({
     "metric": "batch-1 LAP_AR decode LAP-3B bf16 (ms per token after the prefill, greedy, EOS disabled)",
     "tokens": N, "prompt_len": cfg.max_token_len,
@@ -172,4 +211,4 @@ print(json.dumps({
     "algorithmic_bytes_per_token": bytes_tok, "floor_ms_per_token_at_6.29TBps": round(bytes_tok / 6.29e12 * 1e3, 3),
     "achieved_GBps_graphed": round(bytes_tok / (g_ms * 1e-3) / 1e9, 1),
     "share_of_6.29TBps": round(bytes_tok / (g_ms * 1e-3) / 6.29e12, 3), "down_proj_kwaves": a.kwaves} | sampled | ({"weights": quant} if quant else {})
-    | ({"allowed": a.allowed, "constrained": constrained} if constrained else {})))
+    | ({"allowed": a.allowed, "constrained": constrained} if constrained else {}) | logprobs | best_of))
