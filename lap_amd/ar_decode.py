@@ -94,9 +94,24 @@ def check_num_samples(num_samples, batch: int, *, decode: str, sampler: str, tem
     return N
 
 
+def check_filter(top_k, top_p, *, sampler: str, temperature: float):
+    """(top_k, top_p) of a filtered request as the kernels take them, or None when both are neutral or the decode is greedy (the
+    argmax is always kept); ValueError naming the value, or the sampler: the filters are on the device sampler only."""
+    from lap_amd.sampling import check_filter as check_values
+
+    k, p = check_values(top_k, top_p)
+    if top_k is None and top_p is None:
+        return None
+    if sampler != "device" and temperature > 0.0:
+        raise ValueError(f"top_k / top_p need sampler=\"device\" (the filters are part of the device sampler), got sampler={sampler!r}")
+    if (k == 0 and p >= 1.0) or not temperature > 0.0:
+        return None
+    return k, p
+
+
 def sample_tokens(model: LAP, rng, observation, *, max_decoding_steps: int = 390, temperature: float = 0.0, collect=None,
                   decode: str = "eager", sampler: str = "host", decode_weights: str = "bf16", allowed_tokens=None,
-                  return_logprobs: bool = False, num_samples=None):
+                  return_logprobs: bool = False, num_samples=None, top_k=None, top_p=None):
     """`LAP.sample_tokens` (documented there): every argument is checked before any device work."""
     if decode not in ("eager", "fused"):
         raise ValueError(f"sample_tokens: decode must be 'eager' or 'fused', got {decode!r}")
@@ -105,6 +120,7 @@ def sample_tokens(model: LAP, rng, observation, *, max_decoding_steps: int = 390
         raise ValueError(f"sample_tokens: decode_weights={decode_weights!r} runs on the fused decode kernels only: pass decode=\"fused\"")
     if sampler not in ("host", "device"):
         raise ValueError(f"sample_tokens: sampler must be 'host' or 'device', got {sampler!r}")
+    filt = check_filter(top_k, top_p, sampler=sampler, temperature=temperature)
     N = None
     if num_samples is not None:
         N = check_num_samples(num_samples, observation.tokenized_prompt.shape[0], decode=decode, sampler=sampler, temperature=temperature)
@@ -119,12 +135,12 @@ def sample_tokens(model: LAP, rng, observation, *, max_decoding_steps: int = 390
         if decode == "fused" and (sampler == "device" or temperature <= 0.0):   # (the host sampler's noise cannot run on the device state)
             return _sample_fused(model, observation, max_decoding_steps=max_decoding_steps, collect=collect,
                                  sampling=(rng, temperature) if sampler == "device" else None, weights=decode_weights,
-                                 allowed=allowed, logprobs=return_logprobs or N is not None, num_samples=N)
+                                 allowed=allowed, logprobs=return_logprobs or N is not None, num_samples=N, filt=filt)
         if decode_weights != "bf16":
             raise ValueError("sample_tokens: decode_weights other than 'bf16' with temperature > 0 needs sampler='device' (the "
                              "host sampler keeps the eager loop)")
         return _sample_eager(model, rng, observation, max_decoding_steps=max_decoding_steps, temperature=temperature, collect=collect,
-                             device_sampler=sampler == "device", allowed=allowed, logprobs=return_logprobs)
+                             device_sampler=sampler == "device", allowed=allowed, logprobs=return_logprobs, filt=filt)
 
 
 class Prefill(NamedTuple):
@@ -217,9 +233,10 @@ def _lm_logits(model: LAP, rows):
 
 
 def _sample_eager(model: LAP, rng, observation, *, max_decoding_steps: int, temperature: float, collect, device_sampler: bool,
-                  allowed=None, logprobs: bool = False):
+                  allowed=None, logprobs: bool = False, filt=None):
     """allowed: int32 device ids; the logits outside the set are -inf before the argmax or the noise.  logprobs: also the f32
-    log_softmax of logits * inv_t (over the allowed set) at every token, returned beside the tokens."""
+    log_softmax of logits * inv_t (over the allowed set) at every token, returned beside the tokens: over all candidates, also
+    when filt = (top_k, top_p) narrows the draw (lap_filter_gumbel_argmax_rows_f32)."""
     dev = model.device
     B, Pn, cache, kinfo_prefix, qinfo_d, plen, x_last = prefill(model, observation)
     logits = _lm_logits(model, x_last)                                      # decodes the first token (lap.py:716)
@@ -239,7 +256,10 @@ def _sample_eager(model: LAP, rng, observation, *, max_decoding_steps: int, temp
             logits = logits.masked_fill(outside, float("-inf"))
         raw = logits
         if device_sampler and temperature > 0.0:      # one pass over the raw logits, no [B, V] temporaries
-            token = hip.gumbel_argmax_rows(logits, temperature, rng, step)
+            if filt is not None:
+                token = hip.filter_gumbel_argmax_rows(logits, temperature, rng, step, *filt)
+            else:
+                token = hip.gumbel_argmax_rows(logits, temperature, rng, step)
         else:
             if temperature > 0.0:
                 u = torch.rand(logits.shape, generator=g, device=dev, dtype=torch.float32).clamp_(1e-20, 1.0)
@@ -262,16 +282,20 @@ def _sample_eager(model: LAP, rng, observation, *, max_decoding_steps: int, temp
 
 # ---- the fused step: single-token kernels, state on the device (csrc/decode.hip)
 def _sample_fused(model: LAP, observation, *, max_decoding_steps: int, collect=None, sampling=None, weights: str = "bf16",
-                  allowed=None, logprobs: bool = False, num_samples=None):
+                  allowed=None, logprobs: bool = False, num_samples=None, filt=None):
     """sampling: None (the greedy LM head) or (seed, temperature) for the sampling LM head.  weights: `decode_weights`.
+    filt: None, or (top_k, top_p): a filtering context (it needs `sampling`).
     allowed: None or the int32 device ids of `check_allowed_tokens`.  logprobs: the context keeps the token log-probabilities
     and (tokens, logprobs) is returned.  num_samples: the batch-1 prefill is replicated to that many rows."""
     pre = prefill(model, observation)
     if num_samples is not None:
         pre = replicate_prefill(pre, num_samples)
-    ctx = DecodeCtx(model, pre.B, pre.Pn, max_decoding_steps, sampling is not None, weights, allowed=allowed, logprobs=logprobs)
+    ctx = DecodeCtx(model, pre.B, pre.Pn, max_decoding_steps, sampling is not None, weights, allowed=allowed, logprobs=logprobs,
+                    filtering=filt is not None)
     if sampling is not None:
         ctx.set_sampling(*sampling)
+    if filt is not None:
+        ctx.set_filter(*filt)
     lg = None
     if collect is not None:     # (the constrained LM head writes the allowed columns only: the rest keeps the fill)
         lg = torch.empty((pre.B, model.config.vocab_size), dtype=torch.float32, device=model.device)
@@ -296,11 +320,16 @@ def _sample_fused(model: LAP, observation, *, max_decoding_steps: int, collect=N
 class DecodeCtx:
     """One fused decode of `model` (B rows, `Pn` prefix keys, `cap` = max_decoding_steps): the device state, the token output,
     the fixed-capacity generated K/V cache of every layer ([depth, 2, B, cap, head_dim] bf16, 7.2 MB per sample at 390 steps
-    for LAP-3B) and the step's activations.  The prefix K/V cache and kinfo come from the prefill (`first_token` -> `bind`)."""
+    for LAP-3B) and the step's activations.  The prefix K/V cache and kinfo come from the prefill (`first_token` -> `bind`).
+    filtering=True (needs sampling=True): the context draws through top-k / top-p filter words (`set_filter`): its LM head is the
+    plain greedy one, which stores its f32 logits in a [B, V] buffer the context owns, and lap_decode_filter_finish draws from that
+    buffer and does the finish's bookkeeping.  Every other context launches what it launched before."""
 
     def __init__(self, model: LAP, B: int, Pn: int, cap: int, sampling: bool = False, weights: str = "bf16", allowed=None,
-                 logprobs: bool = False):
+                 logprobs: bool = False, filtering: bool = False):
         check_decode_weights(weights)
+        if filtering and not sampling:
+            raise ValueError("DecodeCtx: filtering needs sampling=True (the filters are part of the device sampler)")
         if allowed is not None and (allowed.dtype != torch.int32 or not allowed.is_cuda or allowed.dim() != 1):
             raise ValueError("DecodeCtx: allowed must be the int32 device ids of check_allowed_tokens")
         self.allowed = allowed          # None, or the allowed set of every token (captured graphs keep the buffer's address)
@@ -328,8 +357,22 @@ class DecodeCtx:
         # LM head's log-sum-exp partials; None: the context launches the heads without them
         self.logp = torch.zeros((B, cap), dtype=torch.float32, device=dev) if logprobs else None
         self.plp = hip.decode_lm_logp_partials(B, dev) if logprobs else None
+        # filtering: the filter words {top_k, bits of top_p, 0, 0} (neutral until `set_filter`) and the f32 logits of the step, which
+        # keep -inf outside an allowed set (the constrained head writes the allowed columns only)
+        self.filter = hip.decode_filter(dev) if filtering else None
+        self.logits = None
+        if filtering:
+            self.logits = torch.empty((B, model.config.vocab_size), dtype=torch.float32, device=dev)
+            if allowed is not None:
+                self.logits.fill_(float("-inf"))
         self.prefix = None
         self.kinfo = None
+
+    def set_filter(self, top_k, top_p):
+        """top_k / top_p of the next decode (None: neutral; a host-to-device copy; captured graphs keep the buffer's address)."""
+        if self.filter is None:
+            raise ValueError("this decode context was built without filtering")
+        hip.decode_set_filter(self.filter, top_k, top_p)
 
     def set_sampling(self, seed: int, temperature: float):
         """Seed and temperature of the next decode (a host-to-device copy; captured graphs keep the buffer's address)."""
@@ -370,6 +413,12 @@ class DecodeCtx:
             hi, lo, kw = m.W("llm/embed"), m.ps.w16lo("llm/embed"), {}
         if self.allowed is not None:      # the LM head streams the allowed rows only
             kw["ids"] = self.allowed
+        if self.filter is not None:       # the plain head stores the logits (its partials are not read), the filter kernel draws
+            hip.decode_lm_head(self.state, x, m.F("llm/final_norm"), hi, lo, self.pval, self.pidx, self.logits, **kw)
+            hip.decode_filter_finish(self.state, self.sampling, self.filter, self.logits, self.out, m.EOS_TOKEN, logp=self.logp)
+            if logits is not None:        # (debug: the caller's copy of what the draw saw)
+                logits.copy_(self.logits)
+            return
         if self.logp is not None:         # the same head with the log-sum-exp partials, and the finish that turns them into logp[:, t]
             hip.decode_lm_head_lp(self.state, self.sampling, x, m.F("llm/final_norm"), hi, lo, self.pval, self.pidx, self.plp, logits, **kw)
             hip.decode_finish_lp(self.state, self.pval, self.pidx, self.plp, self.out, self.logp, m.EOS_TOKEN)

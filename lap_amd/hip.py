@@ -242,6 +242,9 @@ SIGNATURES: dict[str, list] = {
     "lap_decode_lm_head_subset_sample_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
     "lap_decode_lm_head_lp": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp],
     "lap_decode_finish_lp": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "lap_filter_gumbel_argmax_rows_f32": [_vp, _i, _i, _i, _f, C.c_uint, C.c_uint, _i, _i, _f, _vp, _vp, _vp, _vp],
+    "lap_decode_filter_words": [],
+    "lap_decode_filter_finish": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
 }
 
 _fn = {}
@@ -433,6 +436,31 @@ def gumbel_argmax_rows(x, temperature, seed, step, out=None):
     if out is None:
         out = torch.empty((x.shape[0],), dtype=torch.int32, device=x.device)
     call("lap_gumbel_argmax_rows_f32", _p(x), x.shape[0], x.shape[1], x.stride(0), inv_t, lo, hi, int(step), _p(out))
+    return out
+
+
+def filter_gumbel_argmax_rows(x, temperature, seed, step, top_k=None, top_p=None, out=None, kept=None, cut=None):
+    """`gumbel_argmax_rows` over the entries that top_k / top_p keep (lap_filter_gumbel_argmax_rows_f32; `sampling.filter_keep`
+    restates the kept set): x f32 [rows, n] -> int32 [rows].  None is the neutral value of either filter, and with both neutral the
+    token is `gumbel_argmax_rows`'.  kept (int32 [rows]) / cut (f32 [rows]), debug: the size of the kept set, the smallest kept z."""
+    from lap_amd.sampling import check_filter
+
+    _req(x, torch.float32, "x")
+    k, p = check_filter(top_k, top_p)
+    lo, hi, inv_t = sampling_words(seed, temperature)
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise TypeError("filter_gumbel_argmax_rows: x must be [rows, n] with contiguous rows")
+    if out is None:
+        out = torch.empty((x.shape[0],), dtype=torch.int32, device=x.device)
+    if kept is not None:
+        _dreq(kept, torch.int32, "kept")
+    if cut is not None:
+        _dreq(cut, torch.float32, "cut")
+    for t, n in ((out, "out"), (kept, "kept"), (cut, "cut")):
+        if t is not None and t.numel() < x.shape[0]:
+            raise TypeError(f"filter_gumbel_argmax_rows: {n} holds one entry per row")
+    call("lap_filter_gumbel_argmax_rows_f32", _p(x), x.shape[0], x.shape[1], x.stride(0), inv_t, lo, hi, int(step), k, p, _p(out),
+         _p(kept), _p(cut))
     return out
 
 
@@ -1598,3 +1626,50 @@ def decode_finish_lp(state, pval, pidx, plp, out, logp, eos_token):
     if tuple(logp.shape) != tuple(out.shape):
         raise TypeError(f"decode_finish_lp: logp {tuple(logp.shape)} beside out {tuple(out.shape)}")
     call("lap_decode_finish_lp", _p(state), _p(pval), _p(pidx), _p(plp), _p(out), _p(logp), out.shape[0], out.shape[1], int(eos_token))
+
+
+def decode_filter(device):
+    """The filter words of a filtering decode (lap_decode_filter_finish): int32 [4] = {top_k, bits of float32 top_p, 0, 0}; the
+    neutral words {0, bits of 1.0, 0, 0} keep every candidate.  A captured graph holds its address; `decode_set_filter` rewrites
+    it between replays."""
+    buf = torch.zeros(_fn["lap_decode_filter_words"](), dtype=torch.int32, device=device)
+    decode_set_filter(buf, None, None)
+    return buf
+
+
+def decode_set_filter(buf, top_k, top_p):
+    """Fill the filter words with a plain host-to-device copy (no kernel).  None: the neutral value."""
+    import numpy as np
+
+    from lap_amd.sampling import check_filter
+
+    _dreq(buf, torch.int32, "filter")
+    k, p = check_filter(top_k, top_p)
+    words = np.array([k, int(np.float32(p).view(np.uint32)), 0, 0], dtype=np.uint32).view(np.int32)
+    buf.copy_(torch.from_numpy(words))
+
+
+def decode_filter_finish(state, sampling, filt, logits, out, eos_token, logp=None, kept=None, cut=None):
+    """`decode_finish` / `decode_finish_lp` of a filtering step: the token of every row is drawn from the f32 `logits` [B, V] that
+    the LM head of the step stored, over the entries the filter words keep, with the sampler's score (lap_decode_filter_finish).
+    logp (f32 [B, cap] beside out): also the token's log-probability over ALL candidates at tau = inv_t.  kept / cut: debug."""
+    _dreq(state, torch.int32, "state"); _dreq(sampling, torch.int32, "sampling"); _dreq(filt, torch.int32, "filter")
+    _dreq(logits, torch.float32, "logits"); _dreq(out, torch.int32, "out")
+    B, cap = out.shape
+    if logits.dim() != 2 or logits.shape[0] != B:
+        raise TypeError(f"decode_filter_finish: logits {tuple(logits.shape)} for {B} rows")
+    if sampling.numel() < _fn["lap_decode_sampling_words"]() or filt.numel() < _fn["lap_decode_filter_words"]():
+        raise TypeError("decode_filter_finish: sampling / filter words: int32 [4] each")
+    if logp is not None:
+        _dreq(logp, torch.float32, "logp")
+        if tuple(logp.shape) != tuple(out.shape):
+            raise TypeError(f"decode_filter_finish: logp {tuple(logp.shape)} beside out {tuple(out.shape)}")
+    if kept is not None:
+        _dreq(kept, torch.int32, "kept")
+    if cut is not None:
+        _dreq(cut, torch.float32, "cut")
+    for t, n in ((kept, "kept"), (cut, "cut")):
+        if t is not None and t.numel() < B:
+            raise TypeError(f"decode_filter_finish: {n} holds one entry per row")
+    call("lap_decode_filter_finish", _p(state), _p(sampling), _p(filt), _p(logits), _p(out), _p(logp), B, logits.shape[1], cap,
+         int(eos_token), _p(kept), _p(cut))

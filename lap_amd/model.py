@@ -693,7 +693,7 @@ class LAP:
 
     def sample_tokens(self, rng, observation, *, max_decoding_steps: int = 390, temperature: float = 0.0, collect=None,
                       decode: str = "eager", sampler: str = "host", decode_weights: str = "bf16", allowed_tokens=None,
-                      return_logprobs: bool = False, num_samples=None):
+                      return_logprobs: bool = False, num_samples=None, top_k=None, top_p=None):
         """lap.py:678-766 (LAP_AR serving mode): VLM-only prefill, then single-token decode until every sample has emitted
         EOS or `max_decoding_steps` tokens; returns int32 [B, max_decoding_steps] (zeros after the stop).
 
@@ -751,11 +751,25 @@ class LAP:
         decode="fused", sampler="device", temperature > 0; anything else raises ValueError): the prefix is prefilled once, its
         K / V, key-info words and last row are copied to N rows, and the N rows decode as one fused batch under `rng`, row b
         drawing with Philox row index b as any batch row does.  Returns (tokens [N, steps], logprobs [N, steps]);
-        `sampling.select_best` picks the answer."""
+        `sampling.select_best` picks the answer.
+
+        top_k, top_p: top-k and nucleus filtering of a sampled draw (sampler="device"; with sampler="host" and temperature > 0
+        they raise ValueError; None, the default, is the neutral value of either and leaves every request as it was).  top_k: an
+        integer >= 0, the draw runs over the k candidates of largest z = float32(logit * inv_t) (ties at the cut go to the lower
+        indices; 0 or k >= the number of candidates keeps all).  top_p in (0, 1]: of what top_k kept, in that order, the entries
+        whose preceding cumulative softmax mass is below top_p times the kept mass (the first always).  The candidates are the
+        allowed set of a constrained decode.  The token is the argmax of the unfiltered sampler's score over the kept entries, so
+        `sampling.sample_from_logits(collect["logit/<t>"], temperature, rng, t, top_k, top_p)` reproduces it and
+        `sampling.filter_keep` gives the kept set.  A greedy decode ignores both.  decode="eager" draws with
+        lap_filter_gumbel_argmax_rows_f32; decode="fused" lets the plain LM head store its f32 logits and draws with
+        lap_decode_filter_finish (one more launch per token than the unfiltered fused step).  `return_logprobs` and best-of-N keep
+        their meaning: a log-probability is the log-softmax over ALL candidates at tau = inv_t, the model's probability of the
+        token, not its probability inside the kept set; `select_best` ranks by it.  The reference has no such option."""
         from lap_amd import ar_decode       # (it imports this module)
         return ar_decode.sample_tokens(self, rng, observation, max_decoding_steps=max_decoding_steps, temperature=temperature,
                                        collect=collect, decode=decode, sampler=sampler, decode_weights=decode_weights,
-                                       allowed_tokens=allowed_tokens, return_logprobs=return_logprobs, num_samples=num_samples)
+                                       allowed_tokens=allowed_tokens, return_logprobs=return_logprobs, num_samples=num_samples,
+                                       top_k=top_k, top_p=top_p)
 
     DECODE_WEIGHTS = ("bf16", "fp8", "fp8_layers")
 

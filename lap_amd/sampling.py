@@ -18,6 +18,9 @@
 The kernels (csrc/sampling.hpp, used by lap_decode_lm_head_sample and lap_gumbel_argmax_rows_f32) compute the same thing; they
 agree with this file up to the last bits of the two logarithms.  A served draw is reproduced offline from the raw logits with
 `sample_from_logits(logits, temperature, seed, step)`.
+
+Top-k and nucleus (top-p) filtering of such a draw (csrc/decode_filter.hip) is specified by `filter_keep` below: the token is the
+argmax of the same score over the kept entries, `sample_from_logits(..., top_k=, top_p=)`.
 """
 from __future__ import annotations
 
@@ -103,10 +106,127 @@ def scores_from_logits(logits, temperature: float, seed: int, step: int) -> np.n
     return lg * inv_t + gumbel_noise(seed, step, lg.shape[0], lg.shape[1])
 
 
-def sample_from_logits(logits, temperature: float, seed: int, step: int) -> np.ndarray:
+def sample_from_logits(logits, temperature: float, seed: int, step: int, top_k=None, top_p=None) -> np.ndarray:
     """int32 [rows]: the token every row of float32 `logits` [rows, V] draws at decode step `step` under `seed`; the argmax
-    (lowest index among ties) when temperature <= 0."""
-    return np.argmax(scores_from_logits(logits, temperature, seed, step), axis=-1).astype(np.int32)
+    (lowest index among ties) when temperature <= 0.  top_k / top_p: the argmax runs over the entries `filter_keep` keeps; with
+    both neutral (None) this is the unfiltered draw, bit for bit."""
+    sc = scores_from_logits(logits, temperature, seed, step)
+    k, p = check_filter(top_k, top_p)
+    if (k or p < 1.0) and inverse_temperature(temperature) != 0.0:
+        sc = np.where(filter_keep(logits, temperature, top_k, top_p), sc, -np.inf).astype(np.float32)
+        # (a kept entry always beats -inf: its score is finite; an all -inf row keeps index 0 as before)
+    return np.argmax(sc, axis=-1).astype(np.int32)
+
+
+# ---- top-k and nucleus (top-p) filtering (the specification of csrc/decode_filter.hip)
+def check_filter(top_k, top_p):
+    """(k, p) as the kernels take them: k an int >= 0 (0: keep all), p a float32 value in (0, 1] (1: keep all); None is the
+    neutral value of either.  ValueError naming the value otherwise."""
+    k = 0
+    if top_k is not None:
+        if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or int(top_k) < 0 or int(top_k) > 0x7FFFFFFF:
+            raise ValueError(f"top_k must be an integer >= 0 (0 or None: no top-k filter), got {top_k!r}")
+        k = int(top_k)
+    p = 1.0
+    if top_p is not None:
+        try:
+            p = float(top_p)
+        except (TypeError, ValueError):
+            raise ValueError(f"top_p must lie in (0, 1], got {top_p!r}") from None
+        if isinstance(top_p, bool) or not 0.0 < p <= 1.0:
+            raise ValueError(f"top_p must lie in (0, 1], got {top_p!r}")
+        p = float(np.float32(p))        # the kernels read top_p as a float32 word
+        if p <= 0.0:
+            raise ValueError(f"top_p must lie in (0, 1] as a float32, got {top_p!r}")
+    return k, p
+
+
+def _filter_order(logits, temperature):
+    """(z float64 [rows, V], order int64 [rows, V], candidates int64 [rows]): z = float32(logit * inv_t) (the raw logit when greedy),
+    the columns of every row by z descending, then index ascending, and the number of entries with z > -inf (they come first)."""
+    lg = np.ascontiguousarray(np.asarray(logits, dtype=np.float32))
+    if lg.ndim != 2:
+        raise ValueError("logits: [rows, vocab_size]")
+    inv_t = inverse_temperature(temperature)
+    z = (lg * inv_t if inv_t != 0.0 else lg).astype(np.float64)
+    order = np.argsort(-z, axis=1, kind="stable")          # stable: equal z keep their index order
+    return z, order, (z > -np.inf).sum(axis=1)
+
+
+def _filter_cut(z, order, ncand, k, p):
+    """Per row: (kept count, cumulative masses c [rows, V] in order relative to exp(z - max z), W [rows]) under top_k = k, top_p = p."""
+    rows, V = z.shape
+    zs = np.take_along_axis(z, order, axis=1)
+    n_k = np.where((k == 0) | (k >= ncand), ncand, k)       # what top_k keeps
+    rank = np.arange(V)[None, :]
+    with np.errstate(invalid="ignore", over="ignore"):
+        w = np.where(rank < n_k[:, None], np.exp(zs - zs[:, :1]), 0.0)
+    w = np.where(np.isfinite(w), w, 0.0)
+    c = np.cumsum(w, axis=1)
+    W = c[:, -1]
+    if p >= 1.0:
+        return n_k, c, W
+    before = np.concatenate([np.zeros((rows, 1)), c[:, :-1]], axis=1)      # c_{r-1}
+    keep = (rank < n_k[:, None]) & ((before < p * W[:, None]) | (rank == 0))
+    return np.minimum(keep.sum(axis=1), n_k), c, W
+
+
+def filter_keep(logits, temperature: float, top_k=None, top_p=None) -> np.ndarray:
+    """bool [rows, V]: the entries of float32 `logits` a filtered draw chooses among.  One row at one step:
+
+    * z[j] = float32(logit[j] * inv_t), the product the sampler forms; everything after it is float64.  The candidates are the
+      entries with z > -inf (a constrained decode leaves -inf outside its set), ordered by z descending, then index ascending.
+    * top_k keeps the first k of that order; None, 0 or k >= the number of candidates keeps all; ties at the cut go to the lower
+      indices.
+    * top_p (0 < top_p <= 1, taken as float64(float32(top_p)): the kernels read a float32 word) applies to what top_k kept:
+      w = exp(z - max z), W = sum w, c_r the cumulative mass in order; rank r is kept while c_{r-1} < top_p * W; rank 0 always;
+      None or 1 keeps all.
+    * temperature <= 0 (greedy) ignores both: the argmax is always kept, so every candidate is reported kept."""
+    k, p = check_filter(top_k, top_p)
+    z, order, ncand = _filter_order(logits, temperature)
+    if inverse_temperature(temperature) == 0.0:
+        k, p = 0, 1.0
+    n, _, _ = _filter_cut(z, order, ncand, k, p)
+    keep_sorted = np.arange(z.shape[1])[None, :] < n[:, None]
+    keep = np.zeros(z.shape, dtype=bool)
+    np.put_along_axis(keep, order, keep_sorted, axis=1)
+    return keep
+
+
+# The relative mass error of the kernel's cut (csrc/decode_filter.hip), from what it computes:
+#   * a mass is q = floor(expf(hi) (1 + lo) 2^40) with z - max z = hi + lo exactly (two-sum).  expf is within 1 ulp (relative
+#     2^-23), the fma that applies (1 + lo) rounds once more (2^-24), exp(lo) - (1 + lo) <= lo^2 / 2 <= 2^-41 (|lo| <= ulp(hi) / 2 <=
+#     2^-20 where a mass is not zero, |hi| < 32): relative error at most 1.5 * 2^-23 + 2^-40 of the entry's own mass, hence of any sum
+#     of masses;
+#   * the truncation to a multiple of 2^-40 loses less than 2^-40 per entry, V * 2^-40 over a row, relative to W >= 1 (the largest
+#     entry has mass 1); the sums themselves are integers and exact; ceil(top_p * W) moves the threshold by less than one more unit.
+# Both c_r and top_p * W carry that error (top_p <= 1), so a comparison c_r < top_p * W can come out differently from float64 only
+# when |c_r - top_p W| / W <= 2 * (1.5 * 2^-23 + (V + 2) * 2^-40); for V <= 2^18 (the vocabulary has 257,152 entries):
+FILTER_MARGIN = 2.0 * (1.5 * 2.0 ** -23 + (2 ** 18 + 2) * 2.0 ** -40)        # 8.35e-07
+
+
+def filter_margin(logits, temperature: float, top_k=None, top_p=None) -> np.ndarray:
+    """float64 [rows]: the smallest |c_r - top_p * W| / W over the comparisons next to the top_p cut: the last one that held
+    (c_{n-2} < top_p W, when n >= 2 entries are kept) and the first one that failed (c_{n-1} >= top_p W, when top_p and not top_k
+    or the end of the candidates ended the kept set).  inf where top_p decides nothing (None, 1, greedy).  A kernel whose masses
+    are within FILTER_MARGIN of float64 keeps exactly `filter_keep`'s set in every row whose margin exceeds FILTER_MARGIN."""
+    k, p = check_filter(top_k, top_p)
+    z, order, ncand = _filter_order(logits, temperature)
+    rows = z.shape[0]
+    out = np.full(rows, np.inf)
+    if p >= 1.0 or inverse_temperature(temperature) == 0.0:
+        return out
+    n, c, W = _filter_cut(z, order, ncand, k, p)
+    n_k = np.where((k == 0) | (k >= ncand), ncand, k)
+    for b in range(rows):
+        if ncand[b] == 0 or not W[b] > 0.0:
+            continue
+        t = p * W[b]
+        if n[b] >= 2:
+            out[b] = min(out[b], abs(c[b, n[b] - 2] - t) / W[b])
+        if n[b] < n_k[b]:
+            out[b] = min(out[b], abs(c[b, n[b] - 1] - t) / W[b])
+    return out
 
 
 # ---- token log-probabilities and best-of-N selection (the specification of lap_decode_lm_head_lp / lap_decode_finish_lp)

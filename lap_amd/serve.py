@@ -112,11 +112,20 @@ class GraphedTokenDecoder:
 
     num_samples=N (1 <= N <= 8; batch_size 1, sampling=True): `sample_tokens`' best-of-N.  The prefill graph runs at B = 1 and
     ends with the copies of its prefix K / V, key-info words and last row to N rows; the step graph runs at B = N.  A call
-    (temperature > 0) returns (tokens [N, steps], logprobs [N, steps])."""
+    (temperature > 0) returns (tokens [N, steps], logprobs [N, steps]).
+
+    filtering=True (needs sampling=True): `sample_tokens`' `top_k` / `top_p`.  Both graphs are captured on the filtering context
+    (the plain LM head stores its f32 logits, lap_decode_filter_finish draws from them); `__call__(obs, temperature=, seed=,
+    top_k=, top_p=)` rewrites four more device words before the first replay, so one capture serves any k and p, and a call with
+    neither returns the filtering=False decoder's tokens.  Composes with weights=, allowed_tokens=, logprobs= (the log-probability
+    stays the one over all candidates) and num_samples=."""
 
     def __init__(self, model: LAP, batch_size: int = 1, max_decoding_steps: int = 390, prompt_len: int | None = None,
                  steps_per_replay: int = 8, sampling: bool = False, weights: str = "bf16", allowed_tokens=None,
-                 logprobs: bool = False, num_samples=None):
+                 logprobs: bool = False, num_samples=None, filtering: bool = False):
+        if filtering and not sampling:
+            raise ValueError("GraphedTokenDecoder: filtering needs a decoder built with sampling=True")
+        self.filtering = bool(filtering)
         self.N = None
         if num_samples is not None:
             if not sampling:
@@ -161,7 +170,7 @@ class GraphedTokenDecoder:
             pre = ar_decode.replicate_prefill(pre, self.N)
         if self.ctx is None:
             self.ctx = ar_decode.DecodeCtx(self.model, pre.B, pre.Pn, self.max_steps, self.sampling, self.weights,
-                                           allowed=self.allowed, logprobs=self.logprobs)
+                                           allowed=self.allowed, logprobs=self.logprobs, filtering=self.filtering)
         self.ctx.first_token(pre)
 
     def _steps(self):
@@ -188,9 +197,12 @@ class GraphedTokenDecoder:
         torch.cuda.synchronize()
         return self
 
-    def __call__(self, obs: CoTObservation, *, temperature: float = 0.0, seed: int = 0):
+    def __call__(self, obs: CoTObservation, *, temperature: float = 0.0, seed: int = 0, top_k=None, top_p=None):
         if temperature > 0.0 and not self.sampling:
             raise ValueError("GraphedTokenDecoder: temperature > 0 needs a decoder built with sampling=True")
+        filt = ar_decode.check_filter(top_k, top_p, sampler="device", temperature=temperature)
+        if filt is not None and not self.filtering:
+            raise ValueError("GraphedTokenDecoder: top_k / top_p need a decoder built with filtering=True")
         if self.N is not None and not temperature > 0.0:
             raise ValueError(f"GraphedTokenDecoder: num_samples needs temperature > 0 (greedy candidates are all the same), got {temperature!r}")
         if self.g_step is None:
@@ -200,6 +212,8 @@ class GraphedTokenDecoder:
         self._load(obs)
         if self.sampling:
             self.ctx.set_sampling(seed, temperature)
+        if self.filtering:
+            self.ctx.set_filter(*(filt or (None, None)))
         self.g_prefill.replay()
         for _ in range((self.max_steps - 1 + self.spr - 1) // self.spr):
             if bool(self.ctx.state[1].item()):      # one host read per replay
@@ -378,11 +392,17 @@ class ARPolicy:
             ar_decode.check_num_samples(self._num_samples, 1, decode=self._sample_kwargs["decode"],
                                         sampler=self._sample_kwargs.get("sampler", "host"),
                                         temperature=self._sample_kwargs.get("temperature", 0.0))
+        # sample_kwargs["top_k"] / ["top_p"] (filtering of a device-sampled draw) reach both routes: checked here, once; the decoder
+        # is captured with filtering=True when either is present and gets them on every call
+        self._filter = {k: self._sample_kwargs[k] for k in ("top_k", "top_p") if self._sample_kwargs.get(k) is not None}
+        ar_decode.check_filter(self._filter.get("top_k"), self._filter.get("top_p"), sampler=self._sample_kwargs.get("sampler", "host"),
+                               temperature=self._sample_kwargs.get("temperature", 0.0))
         if use_graph and base.model.decode_supported(self._num_samples or 1):
             self._decoder = GraphedTokenDecoder(base.model, 1, self._sample_kwargs.get("max_decoding_steps", 390),
                                                 sampling=self._device_sampler, weights=weights,
                                                 allowed_tokens=self._sample_kwargs.get("allowed_tokens"),
-                                                logprobs=self._logprobs, num_samples=self._num_samples)
+                                                logprobs=self._logprobs, num_samples=self._num_samples,
+                                                filtering=bool(self._filter) and self._device_sampler)
 
     def __getattr__(self, name):
         return getattr(self._base, name)
@@ -401,7 +421,8 @@ class ARPolicy:
         temperature = self._sample_kwargs.get("temperature", 0.0)
         if (self._decoder is not None and (temperature <= 0.0 or self._device_sampler)
                 and self._sample_kwargs.get("decode", "eager") in ("eager", "fused") and graph_compatible(self._decoder.obs, o)):
-            tokens = self._decoder(o, temperature=temperature, seed=self._calls) if self._device_sampler else self._decoder(o)
+            tokens = (self._decoder(o, temperature=temperature, seed=self._calls, **self._filter) if self._device_sampler
+                      else self._decoder(o))
         else:
             tokens = base.model.sample_tokens(self._calls, o, **self._sample_kwargs)
         extra = {}
@@ -445,7 +466,11 @@ def create_trained_policy_ar(*args, sample_kwargs: dict | None = None, language_
     sample_kwargs={"return_logprobs": True} adds "token_logprobs" (f32 [1, steps]) and "logprob" (the sum up to the EOS) to the
     result; sample_kwargs={"num_samples": N, "select": "sum" | "mean"} (with "temperature" > 0 and "sampler": "device"; implies
     decode="fused") decodes N candidates per request, runs the output transforms on the one `sampling.select_best` picks and
-    reports all N under "candidates": {"tokens" [N, steps], "logprob" [N]}.  These keys are added to what the output stack
+    reports all N under "candidates": {"tokens" [N, steps], "logprob" [N]};
+    sample_kwargs={"top_k": k, "top_p": p} (with "temperature" > 0 and "sampler": "device") draws every token among the k most
+    likely candidates and, of those, the nucleus of mass p (`LAP.sample_tokens`; `sampling.filter_keep` restates the kept set) on
+    either route: the decoder is captured with filtering=True when either is present; log-probabilities stay the model's (over
+    all candidates), so best-of-N ranks as before.  These keys are added to what the output stack
     returns ({"actions", "reasoning"}), so a client of this policy and of the websocket server receives them."""
     from lap_amd import policy_io as pio
 

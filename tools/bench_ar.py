@@ -19,6 +19,9 @@ bf16 and every --weights value, in the same process, the graphed ms per token wi
 set and whether every constrained token lies in it.  --profile-graphed --allowed N replays the constrained graph.
 --logprobs adds the greedy decode with `return_logprobs=True` (the LM head that also leaves the log-sum-exp partials): fused and
 graphed ms per token, next to the plain figures of the same process.
+--top-k K / --top-p P (with --temperature T > 0) add filtered sampled decoding (`top_k=`, `top_p=`): eager, fused and graphed
+(GraphedTokenDecoder(filtering=True)) ms per token, the same graphs called with neutral words, and the ratio to the unfiltered
+sampling graph.
 --num-samples N adds best-of-N (`num_samples=N`, sampled at --temperature or at 1.0): fused and graphed ms per token of the N
 rows, next to one sampled row with log-probabilities on the same kernels, and both prefill graphs (the N-row one ends with the copies).
 The fused best-of-N figure subtracts the plain batch-1 prefill, so the copies to N rows and the allocation of the N-row context are
@@ -51,6 +54,8 @@ ap.add_argument("--allowed", type=int, default=0, help="> 0: also measure constr
 ap.add_argument("--logprobs", action="store_true", help="also measure greedy decoding that returns token log-probabilities")
 ap.add_argument("--num-samples", type=int, default=0, help="N > 0: also measure best-of-N (N rows from one batch-1 prefill); "
                 "sampled at --temperature, or at 1.0 when that is 0")
+ap.add_argument("--top-k", type=int, default=0, help="with --temperature: also measure filtered sampled decoding (top_k)")
+ap.add_argument("--top-p", type=float, default=1.0, help="with --temperature: also measure filtered sampled decoding (top_p)")
 a = ap.parse_args()
 hip.DECODE_KWAVES_DOWN = a.kwaves
 
@@ -81,8 +86,9 @@ T = a.temperature
 allowed = list(range(a.allowed)) if a.allowed > 0 else None
 if a.profile_graphed:
     if T > 0.0:
-        sdec = GraphedTokenDecoder(model, 1, N, sampling=True, weights=a.weights[-1], allowed_tokens=allowed)
-        sdec(o, temperature=T, seed=1)
+        filtered = a.top_k > 0 or a.top_p < 1.0
+        sdec = GraphedTokenDecoder(model, 1, N, sampling=True, weights=a.weights[-1], allowed_tokens=allowed, filtering=filtered)
+        sdec(o, temperature=T, seed=1, **({"top_k": a.top_k or None, "top_p": a.top_p if a.top_p < 1.0 else None} if filtered else {}))
     elif a.weights[-1] != "bf16" or allowed is not None:
         GraphedTokenDecoder(model, 1, N, weights=a.weights[-1], allowed_tokens=allowed)(o)
     else:
@@ -171,6 +177,22 @@ if T > 0.0:
         "graphed_greedy_on_sampling_graph_ms_per_token": round(per(t_sgreedy, t_spre), 3),
         "graphed_sampled_equals_fused_sampled": bool(torch.equal(sgot, st(sampler="device", decode="fused")())),
         "greedy_on_sampling_graph_equals_graphed": bool(torch.equal(sdec(o), got))}
+    if a.top_k > 0 or a.top_p < 1.0:        # the same sampled decode through the filter kernel (one more launch per token)
+        fkw = {"top_k": a.top_k or None, "top_p": a.top_p if a.top_p < 1.0 else None}
+        t_fe = timeit(st(sampler="device", **fkw), a.reps)
+        t_ff = timeit(st(sampler="device", decode="fused", **fkw), a.reps)
+        fdec = GraphedTokenDecoder(model, 1, N, sampling=True, filtering=True).capture()
+        t_fpre = timeit(lambda: (fdec.g_prefill.replay()), a.reps)
+        t_fgraph = timeit(lambda: fdec(o, temperature=T, seed=1, **fkw), a.reps)
+        t_fneutral = timeit(lambda: fdec(o, temperature=T, seed=1), a.reps)
+        sampled["filtered"] = {
+            "top_k": a.top_k, "top_p": a.top_p,
+            "eager_ms_per_token": round(per(t_fe, t_pre), 3), "fused_ms_per_token": round(per(t_ff, t_pre), 3),
+            "graphed_ms_per_token": round(per(t_fgraph, t_fpre), 3),
+            "graphed_neutral_words_ms_per_token": round(per(t_fneutral, t_fpre), 3),
+            "graphed_ms_per_token_over_unfiltered": round(per(t_fgraph, t_fpre) / per(t_sgraph, t_spre), 4),
+            "graphed_equals_fused": bool(torch.equal(fdec(o, temperature=T, seed=1, **fkw), st(sampler="device", decode="fused", **fkw)())),
+            "neutral_words_equal_unfiltered_graph": bool(torch.equal(fdec(o, temperature=T, seed=1), sgot))}
 logprobs = {}
 if a.logprobs:          # the same greedy decode with return_logprobs=True: what the log-sum-exp in the LM head and the finish cost
     t_lfused = timeit(lambda: model.sample_tokens(0, o, max_decoding_steps=N, decode="fused", return_logprobs=True), a.reps)
