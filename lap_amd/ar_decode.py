@@ -15,6 +15,7 @@ from lap_amd.joint_layers import llm_fwd
 from lap_amd.loss import lm_logits
 from lap_amd.model import LAP, _gen
 from lap_amd.observation import preprocess_observation
+from lap_amd.speculate import check_speculate
 
 DECODE_STEPS_PER_CHECK = 8      # fused steps between two host reads of the device stop flag (eager `decode="fused"`)
 
@@ -111,10 +112,16 @@ def check_filter(top_k, top_p, *, sampler: str, temperature: float):
 
 def sample_tokens(model: LAP, rng, observation, *, max_decoding_steps: int = 390, temperature: float = 0.0, collect=None,
                   decode: str = "eager", sampler: str = "host", decode_weights: str = "bf16", allowed_tokens=None,
-                  return_logprobs: bool = False, num_samples=None, top_k=None, top_p=None):
+                  return_logprobs: bool = False, num_samples=None, top_k=None, top_p=None, speculate=None, draft_tokens=None):
     """`LAP.sample_tokens` (documented there): every argument is checked before any device work."""
     if decode not in ("eager", "fused"):
         raise ValueError(f"sample_tokens: decode must be 'eager' or 'fused', got {decode!r}")
+    S = None
+    if speculate is not None:
+        S = check_speculate(speculate, observation.tokenized_prompt.shape[0], decode=decode, temperature=temperature,
+                            return_logprobs=return_logprobs, num_samples=num_samples, top_k=top_k, top_p=top_p, collect=collect)
+    elif draft_tokens is not None:
+        raise ValueError("sample_tokens: draft_tokens needs speculate=S")
     check_decode_weights(decode_weights)
     if decode_weights != "bf16" and decode != "fused":
         raise ValueError(f"sample_tokens: decode_weights={decode_weights!r} runs on the fused decode kernels only: pass decode=\"fused\"")
@@ -135,7 +142,8 @@ def sample_tokens(model: LAP, rng, observation, *, max_decoding_steps: int = 390
         if decode == "fused" and (sampler == "device" or temperature <= 0.0):   # (the host sampler's noise cannot run on the device state)
             return _sample_fused(model, observation, max_decoding_steps=max_decoding_steps, collect=collect,
                                  sampling=(rng, temperature) if sampler == "device" else None, weights=decode_weights,
-                                 allowed=allowed, logprobs=return_logprobs or N is not None, num_samples=N, filt=filt)
+                                 allowed=allowed, logprobs=return_logprobs or N is not None, num_samples=N, filt=filt,
+                                 speculate=S, draft=draft_tokens)
         if decode_weights != "bf16":
             raise ValueError("sample_tokens: decode_weights other than 'bf16' with temperature > 0 needs sampler='device' (the "
                              "host sampler keeps the eager loop)")
@@ -282,16 +290,20 @@ def _sample_eager(model: LAP, rng, observation, *, max_decoding_steps: int, temp
 
 # ---- the fused step: single-token kernels, state on the device (csrc/decode.hip)
 def _sample_fused(model: LAP, observation, *, max_decoding_steps: int, collect=None, sampling=None, weights: str = "bf16",
-                  allowed=None, logprobs: bool = False, num_samples=None, filt=None):
+                  allowed=None, logprobs: bool = False, num_samples=None, filt=None, speculate=None, draft=None):
     """sampling: None (the greedy LM head) or (seed, temperature) for the sampling LM head.  weights: `decode_weights`.
     filt: None, or (top_k, top_p): a filtering context (it needs `sampling`).
     allowed: None or the int32 device ids of `check_allowed_tokens`.  logprobs: the context keeps the token log-probabilities
-    and (tokens, logprobs) is returned.  num_samples: the batch-1 prefill is replicated to that many rows."""
+    and (tokens, logprobs) is returned.  num_samples: the batch-1 prefill is replicated to that many rows.
+    speculate: None, or the rows S of a verify step (greedy, batch 1: `check_speculate`) with `draft` as the reference sequence;
+    `model.last_spec_stats` then holds (verify_steps, accepted) of the request."""
     pre = prefill(model, observation)
     if num_samples is not None:
         pre = replicate_prefill(pre, num_samples)
     ctx = DecodeCtx(model, pre.B, pre.Pn, max_decoding_steps, sampling is not None, weights, allowed=allowed, logprobs=logprobs,
-                    filtering=filt is not None)
+                    filtering=filt is not None, speculate=speculate)
+    if speculate is not None:
+        ctx.set_draft(draft)
     if sampling is not None:
         ctx.set_sampling(*sampling)
     if filt is not None:
@@ -314,6 +326,8 @@ def _sample_fused(model: LAP, observation, *, max_decoding_steps: int, collect=N
             break
         for _ in range(n):
             ctx.step()
+    if speculate is not None:
+        model.last_spec_stats = ctx.stats()
     return (ctx.out, ctx.logp) if logprobs else ctx.out
 
 
@@ -323,11 +337,21 @@ class DecodeCtx:
     for LAP-3B) and the step's activations.  The prefix K/V cache and kinfo come from the prefill (`first_token` -> `bind`).
     filtering=True (needs sampling=True): the context draws through top-k / top-p filter words (`set_filter`): its LM head is the
     plain greedy one, which stores its f32 logits in a [B, V] buffer the context owns, and lap_decode_filter_finish draws from that
-    buffer and does the finish's bookkeeping.  Every other context launches what it launched before."""
+    buffer and does the finish's bookkeeping.  Every other context launches what it launched before.
+    speculate=S (2 <= S <= 8; B = 1, greedy, no log-probabilities): the context decodes ONE sequence on verify steps of S rows
+    (lap_amd/speculate.py, csrc/decode_spec.hip).  The state, `out`, `plen` and the generated cache stay those of B = 1; the
+    activations, the attention scratch and the LM partials hold S rows; a reference sequence and its length live in one device
+    buffer at a fixed address (`set_draft`).  `first_token` runs the B = 1 head and finish; `step` drafts S - 1 tokens from the
+    reference, runs the layers on the S positions t-1 .. t-1+S-1 and accepts the longest verified run; `stats` reads the
+    counters.  The tokens are those of the context without it."""
 
     def __init__(self, model: LAP, B: int, Pn: int, cap: int, sampling: bool = False, weights: str = "bf16", allowed=None,
-                 logprobs: bool = False, filtering: bool = False):
+                 logprobs: bool = False, filtering: bool = False, speculate=None):
         check_decode_weights(weights)
+        self.S = None
+        if speculate is not None:
+            self.S = check_speculate(speculate, B, return_logprobs=logprobs, temperature=1.0 if sampling else 0.0)
+        R = self.S or B                 # rows of a step's activations
         if filtering and not sampling:
             raise ValueError("DecodeCtx: filtering needs sampling=True (the filters are part of the device sampler)")
         if allowed is not None and (allowed.dtype != torch.int32 or not allowed.is_cuda or allowed.dim() != 1):
@@ -343,13 +367,16 @@ class DecodeCtx:
         self.plen = torch.zeros((B,), dtype=torch.int32, device=dev)
         self.out = torch.zeros((B, cap), dtype=torch.int32, device=dev)
         self.gen = torch.zeros((v.depth, 2, B, cap, v.head_dim), dtype=bf, device=dev)
-        self.x = torch.zeros((B, v.width), dtype=bf, device=dev)
-        self.xa = torch.zeros((B, v.width), dtype=bf, device=dev)
-        self.q = torch.zeros((B, v.num_heads * v.head_dim), dtype=bf, device=dev)
-        self.o = torch.zeros((B, v.num_heads * v.head_dim), dtype=bf, device=dev)
-        self.act = torch.zeros((B, v.mlp_dim), dtype=bf, device=dev)
-        self.attn_scratch = hip.decode_attn_scratch(B, Pn, cap, dev)
-        self.pval, self.pidx = hip.decode_lm_partials(B, dev)
+        self.x = torch.zeros((R, v.width), dtype=bf, device=dev)
+        self.xa = torch.zeros((R, v.width), dtype=bf, device=dev)
+        self.q = torch.zeros((R, v.num_heads * v.head_dim), dtype=bf, device=dev)
+        self.o = torch.zeros((R, v.num_heads * v.head_dim), dtype=bf, device=dev)
+        self.act = torch.zeros((R, v.mlp_dim), dtype=bf, device=dev)
+        self.attn_scratch = hip.decode_attn_scratch(R, Pn, cap, dev)
+        self.pval, self.pidx = hip.decode_lm_partials(R, dev)
+        # speculate: the reference sequence {length, ids[cap]} and the S - 1 drafted tokens of the step
+        self.ref = hip.decode_spec_ref(cap, dev) if self.S else None
+        self.draft = torch.full((self.S - 1,), -1, dtype=torch.int32, device=dev) if self.S else None
         # the sampling words {seed low, seed high, bits of 1 / temperature, 0} of the sampling LM head (zeros: greedy); None:
         # the context decodes on the greedy LM head
         self.sampling = hip.decode_sampling(dev) if sampling else None
@@ -373,6 +400,20 @@ class DecodeCtx:
         if self.filter is None:
             raise ValueError("this decode context was built without filtering")
         hip.decode_set_filter(self.filter, top_k, top_p)
+
+    def set_draft(self, ids):
+        """The reference sequence the next decode drafts from (any integer sequence, truncated to `cap`; None: no draft, every
+        verify step then emits one token): a host-to-device copy; captured graphs keep the buffer's address."""
+        if self.ref is None:
+            raise ValueError("this decode context was built without speculate")
+        hip.decode_set_spec_ref(self.ref, ids)
+
+    def stats(self):
+        """(verify_steps, accepted) of the decode so far: two words of the device state (a host read)."""
+        if self.S is None:
+            raise ValueError("this decode context was built without speculate")
+        a, b = self.state[24:26].tolist()
+        return int(a), int(b)
 
     def set_sampling(self, seed: int, temperature: float):
         """Seed and temperature of the next decode (a host-to-device copy; captured graphs keep the buffer's address)."""
@@ -402,9 +443,10 @@ class DecodeCtx:
         codes, scales = self.model._dec_fp8(name)
         return codes, {"wscale": scales}
 
-    def _token(self, x, logits=None):
+    def _token(self, x, logits=None, verify=False):
         """final norm + LM head over the hi / lo planes + argmax -> out[:, t], EOS mask, t + 1 (lap.py:716-724).  A context
-        with sampling words runs the sampling LM head, which is the greedy one while the words hold inv_t = 0."""
+        with sampling words runs the sampling LM head, which is the greedy one while the words hold inv_t = 0.
+        verify (a speculating context's step): the greedy head on the S rows of x, then the accept kernel."""
         m = self.model
         if self.weights == "fp8":         # one e4m3 plane of the f32 table
             hi, scales = m._dec_fp8("llm/embed")
@@ -413,6 +455,10 @@ class DecodeCtx:
             hi, lo, kw = m.W("llm/embed"), m.ps.w16lo("llm/embed"), {}
         if self.allowed is not None:      # the LM head streams the allowed rows only
             kw["ids"] = self.allowed
+        if verify:
+            hip.decode_lm_head(self.state, x, m.F("llm/final_norm"), hi, lo, self.pval, self.pidx, None, **kw)
+            hip.decode_spec_accept(self.state, self.pval, self.pidx, self.draft, self.out, m.EOS_TOKEN)
+            return
         if self.filter is not None:       # the plain head stores the logits (its partials are not read), the filter kernel draws
             hip.decode_lm_head(self.state, x, m.F("llm/final_norm"), hi, lo, self.pval, self.pidx, self.logits, **kw)
             hip.decode_filter_finish(self.state, self.sampling, self.filter, self.logits, self.out, m.EOS_TOKEN, logp=self.logp)
@@ -435,18 +481,26 @@ class DecodeCtx:
         v = m.v
         NH, HD, KV = v.num_heads, v.head_dim, v.num_kv_heads
         rows, lo, hi = m.ps.embed_rows()
-        hip.decode_embed(self.state, rows, lo, hi, self.out, self.x, math.sqrt(v.width))
+        if self.S:
+            hip.decode_spec_draft(self.state, self.ref, self.out, self.draft)
+            hip.decode_spec_embed(self.state, rows, lo, hi, self.out, self.draft, self.x, math.sqrt(v.width))
+        else:
+            hip.decode_embed(self.state, rows, lo, hi, self.out, self.x, math.sqrt(v.width))
         for l in range(v.depth):
             p = f"llm/{l}/"
             gk, gv = self.gen[l, 0], self.gen[l, 1]
             w, kw = self._w(p + "wqkv0")
-            hip.decode_qkv(self.state, self.x, m.F(p + "n_attn"), w, self.q, gk, gv, NH, HD, HD ** -0.5, **kw)
             ck, cv = self.prefix[l]
-            hip.decode_attention(self.state, self.q, ck, cv, self.kinfo, self.Pn, gk, gv, self.o, self.attn_scratch, NH, KV, HD)
+            if self.S:
+                hip.decode_spec_qkv(self.state, self.x, m.F(p + "n_attn"), w, self.q, gk, gv, NH, HD, HD ** -0.5, **kw)
+                hip.decode_spec_attention(self.state, self.q, ck, cv, self.kinfo, self.Pn, gk, gv, self.o, self.attn_scratch, NH, KV, HD)
+            else:
+                hip.decode_qkv(self.state, self.x, m.F(p + "n_attn"), w, self.q, gk, gv, NH, HD, HD ** -0.5, **kw)
+                hip.decode_attention(self.state, self.q, ck, cv, self.kinfo, self.Pn, gk, gv, self.o, self.attn_scratch, NH, KV, HD)
             w, kw = self._w(p + "wo0")
             hip.decode_proj_residual(self.state, self.o, w, self.x, self.xa, **kw)
             w, kw = self._w(p + "wgu0")
             hip.decode_gate_up(self.state, self.xa, m.F(p + "n_ffw"), w, self.act, **kw)
             w, kw = self._w(p + "wd0")
             hip.decode_proj_residual(self.state, self.act, w, self.xa, self.x, kwaves=hip.DECODE_KWAVES_DOWN, **kw)
-        self._token(self.x, logits)
+        self._token(self.x, logits, verify=bool(self.S))

@@ -32,6 +32,9 @@
 //               the same pass (per block {m, s, z of the best candidate}), and the finish also writes logp[:, t] = z_tok - lse
 //   finish      one block: argmax over the partials with the lowest index among ties, out[:, t] = token, EOS mask, t += 1,
 //               done                                                                         (lap_argmax_rows_f32)
+//   spec_qkv / spec_attention   the qkv and attention kernels on S rows that are consecutive positions of ONE sequence (exact
+//               speculative decoding: EPI_QKV_SPEC and dec_attn_kernel<true> below; csrc/decode_spec.hip holds the draft, embed
+//               and accept kernels of a verify step).  The plain instances' code paths are unchanged.
 // Rounding points are those of the eager step; only the summation order of the dot products differs.
 // Device state is written with plain per-lane stores.
 //
@@ -133,7 +136,13 @@ __device__ __forceinline__ void norm_rows_to_lds(const bf16* x, const float* gam
   __syncthreads();
 }
 
-enum { EPI_QKV = 0, EPI_GEGLU = 1, EPI_RES = 2 };
+enum { EPI_QKV = 0, EPI_GEGLU = 1, EPI_RES = 2, EPI_QKV_SPEC = 3 };
+// EPI_QKV_SPEC (speculative decoding, lap_decode_spec_qkv): the B rows are the consecutive positions t-1 .. t-1+B-1 of ONE
+// sequence (sample 0), not B samples.  Row r rotates at plen[0] + t-1+r and writes K / V to generated-cache row t-1+r of sample 0
+// and q to row r; a row with t-1+r >= cap writes nothing.  The accumulation is EPI_QKV's, so row r holds the bits the plain
+// kernel writes at state[0] = t + r for the same input row.  K / V rows written for drafts that the accept kernel then rejects
+// lie at or beyond the next step's row t'-1; that step overwrites them before a query may see them, because the key count of a
+// query (min(t' + r, cap)) reaches only rows this same step has written.
 
 struct ProjP {
   const int* state;
@@ -159,7 +168,7 @@ struct ProjP8 : ProjP {     // w: e4m3 codes [N][K]
 // wave owns a unit (KW = 1); blocks walk the units with a grid stride.
 template <int EPI>
 __device__ __forceinline__ void unit_features(const ProjP& p, int u, int& f0, int& f1) {
-  if (EPI == EPI_QKV) { const int half = p.HD / 2; f0 = (u / half) * p.HD + u % half; f1 = f0 + half; }
+  if (EPI == EPI_QKV || EPI == EPI_QKV_SPEC) { const int half = p.HD / 2; f0 = (u / half) * p.HD + u % half; f1 = f0 + half; }
   else if (EPI == EPI_GEGLU) { f0 = u; f1 = u + p.H; }
   else { f0 = 2 * u; f1 = 2 * u + 1; }
 }
@@ -173,7 +182,7 @@ __global__ __launch_bounds__(256) void dec_proj_kernel(P p) {
   __shared__ float sacc[KW > 1 ? 4 * 2 * B : 1];
   if (p.state[1]) return;
   const int t = p.state[0];
-  if (EPI == EPI_QKV && (t < 1 || t > p.cap)) return;      // (cache row t - 1)
+  if ((EPI == EPI_QKV || EPI == EPI_QKV_SPEC) && (t < 1 || t > p.cap)) return;      // (cache row t - 1)
   if (NORM) norm_rows_to_lds<B>(p.x, p.gamma, p.K, p.eps, sx, red);
   const bf16* xs = NORM ? sx : p.x;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -255,6 +264,23 @@ __global__ __launch_bounds__(256) void dec_proj_kernel(P p) {
     } else if (EPI == EPI_GEGLU) {
       const float g = round_bf16(y0), up = round_bf16(y1);
       p.out[(long long)b * p.H + f0] = f2bf(round_bf16(gelu_tanh_f(g)) * up);
+    } else if (EPI == EPI_QKV_SPEC) {      // row b is position t-1+b of sample 0 (EPI_QKV's arithmetic)
+      const int half = p.HD / 2, head = u / half, i = u % half;
+      const int s = t - 1 + b;
+      if (s >= p.cap) continue;
+      float x1 = round_bf16(y0), x2 = round_bf16(y1);
+      if (head <= p.NH) {
+        float sn, cs, r1, r2;
+        rope_sincos((float)(p.state[16] + s), i, p.HD, sn, cs);
+        rope_rotate(x1, x2, sn, cs, r1, r2);
+        x1 = round_bf16(r1); x2 = round_bf16(r2);
+        if (head < p.NH) { x1 *= p.q_scale; x2 *= p.q_scale; }
+      }
+      bf16* dst;
+      if (head < p.NH) dst = p.q + (long long)b * p.NH * p.HD + head * p.HD;
+      else dst = (head == p.NH ? p.ck : p.cv) + (long long)s * p.HD;
+      dst[i] = f2bf(x1);
+      dst[i + half] = f2bf(x2);
     } else {
       const int half = p.HD / 2, head = u / half, i = u % half;
       const int s = t - 1;
@@ -314,25 +340,30 @@ struct AttnDecP {
   bf16* o;                             // [B][NH * HD]
 };
 
+// SPEC (speculative decoding, lap_decode_spec_attention): grid y = r, the query is q row r of ONE sequence; the prefix K / V,
+// kinfo and the generated cache are sample 0's, and the generated segment has min(t + r, cap) keys.  The chunk partition is
+// unchanged, so row r's partials are the plain kernel's at state[0] = t + r with B = 1.
+template <bool SPEC>
 __global__ __launch_bounds__(256) void dec_attn_kernel(AttnDecP p) {
   constexpr int NH = DEC_NH, HD = DEC_HD;
   if (p.state[1]) return;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, b = blockIdx.y;
+  const int sb = SPEC ? 0 : b;                 // the sample whose keys row b reads
   const int c = blockIdx.x * 4 + w;
   if (c >= p.nchunk) return;
-  const int t = min(p.state[0], p.cap);
+  const int t = min(SPEC ? p.state[0] + b : p.state[0], p.cap);
   const bf16* kb; const bf16* vb;
   int nkeys, j0;
   if (c < p.npre) {
     j0 = c * KC;
     nkeys = min(KC, p.Pn - j0);
-    kb = p.pk + ((long long)b * p.Pn + j0) * HD;
-    vb = p.pv + ((long long)b * p.Pn + j0) * HD;
+    kb = p.pk + ((long long)sb * p.Pn + j0) * HD;
+    vb = p.pv + ((long long)sb * p.Pn + j0) * HD;
   } else {
     j0 = (c - p.npre) * KC;
     nkeys = max(0, min(KC, t - j0));          // t generated keys (this step's included)
-    kb = p.gk + ((long long)b * p.cap + j0) * HD;
-    vb = p.gv + ((long long)b * p.cap + j0) * HD;
+    kb = p.gk + ((long long)sb * p.cap + j0) * HD;
+    vb = p.gv + ((long long)sb * p.cap + j0) * HD;
   }
   float qf[NH][4];
 #pragma unroll
@@ -352,7 +383,7 @@ __global__ __launch_bounds__(256) void dec_attn_kernel(AttnDecP p) {
       vr[j] = *reinterpret_cast<const bf16x4*>(vb + (long long)j * HD + lane * 4);
     }
   }
-  const bool okl = lane < nkeys && (c < p.npre ? mask_ok(QWORD, p.kinfo[(long long)b * p.Pn + j0 + lane]) : true);
+  const bool okl = lane < nkeys && (c < p.npre ? mask_ok(QWORD, p.kinfo[(long long)sb * p.Pn + j0 + lane]) : true);
   const unsigned long long okmask = __ballot(okl);
   float sj[NH];
   const bool okj = okl;
@@ -831,13 +862,15 @@ int launch_proj(const ProjP8& p, bool f8, int B, dim3 grid, void* stream) {
 }
 
 int qkv_impl(const int* state, const void* x, const float* gamma, const void* wqkv, const float* wscale, bool f8, void* q,
-             void* cache_k, void* cache_v, int B, int D, int NH, int HD, int cap, float q_scale, float eps, void* stream) {
+             void* cache_k, void* cache_v, int B, int D, int NH, int HD, int cap, float q_scale, float eps, void* stream,
+             bool spec = false) {
   if (!lap_decode_ok(B, D, NH, 1, HD, DEC_H, 2) || !state || !gamma || !q || !cache_k || !cache_v || cap < 1 ||
       !aligned16(x) || !aligned16(wqkv) || (f8 && (!wscale || !f8_k_ok(D, 1)))) return LAP_ERR_ARG;
   ProjP8 p{};
   p.state = state; p.x = (const bf16*)x; p.gamma = gamma; p.w = (const bf16*)wqkv; p.K = D; p.units = (NH + 2) * HD / 2;
   p.eps = eps; p.q = (bf16*)q; p.ck = (bf16*)cache_k; p.cv = (bf16*)cache_v; p.cap = cap; p.NH = NH; p.HD = HD; p.q_scale = q_scale;
   p.wscale = wscale;
+  if (spec) return launch_proj<EPI_QKV_SPEC, true, 1>(p, f8, B, dim3((p.units + 3) / 4), stream);
   return launch_proj<EPI_QKV, true, 1>(p, f8, B, dim3((p.units + 3) / 4), stream);
 }
 
@@ -955,9 +988,10 @@ extern "C" int lap_decode_attn_scratch_floats(int B, int Pn, int cap) {
   return B * nchunk * DEC_NH * (DEC_HD + 1);
 }
 
-extern "C" int lap_decode_attention(const int* state, const void* q, const void* prefix_k, const void* prefix_v, const int* kinfo,
-                                    int Pn, const void* cache_k, const void* cache_v, int cap, void* o, float* scratch,
-                                    long long scratch_floats, int B, int NH, int NKV, int HD, void* stream) {
+namespace {
+int attention_impl(const int* state, const void* q, const void* prefix_k, const void* prefix_v, const int* kinfo, int Pn,
+                   const void* cache_k, const void* cache_v, int cap, void* o, float* scratch, long long scratch_floats, int B, int NH,
+                   int NKV, int HD, bool spec, void* stream) {
   if (!state || !q || !prefix_k || !prefix_v || !kinfo || !cache_k || !cache_v || !o || !scratch || Pn < 1 || cap < 1 ||
       !lap_decode_ok(B, DEC_D, NH, NKV, HD, DEC_H, 2) || scratch_floats < lap_decode_attn_scratch_floats(B, Pn, cap) ||
       !aligned16(scratch)) return LAP_ERR_ARG;
@@ -969,11 +1003,20 @@ extern "C" int lap_decode_attention(const int* state, const void* q, const void*
   p.opart = scratch;
   p.lpart = scratch + (long long)B * p.nchunk * DEC_NH * DEC_HD;
   p.o = (bf16*)o;
-  hipLaunchKernelGGL(dec_attn_kernel, dim3((p.nchunk + 3) / 4, B), dim3(256), 0, S_, p);
+  if (spec) hipLaunchKernelGGL(dec_attn_kernel<true>, dim3((p.nchunk + 3) / 4, B), dim3(256), 0, S_, p);
+  else hipLaunchKernelGGL(dec_attn_kernel<false>, dim3((p.nchunk + 3) / 4, B), dim3(256), 0, S_, p);
   LAP_CHECK_LAUNCH();
   hipLaunchKernelGGL(dec_attn_combine_kernel, dim3(DEC_NH, B), dim3(64), 0, S_, p);
   LAP_CHECK_LAUNCH();
   return LAP_OK;
+}
+}  // namespace
+
+extern "C" int lap_decode_attention(const int* state, const void* q, const void* prefix_k, const void* prefix_v, const int* kinfo,
+                                    int Pn, const void* cache_k, const void* cache_v, int cap, void* o, float* scratch,
+                                    long long scratch_floats, int B, int NH, int NKV, int HD, void* stream) {
+  return attention_impl(state, q, prefix_k, prefix_v, kinfo, Pn, cache_k, cache_v, cap, o, scratch, scratch_floats, B, NH, NKV, HD,
+                        false, stream);
 }
 
 extern "C" int lap_decode_lm_head(const int* state, const void* x, const float* gamma, const void* hi, const void* lo, int B, int D,
@@ -1075,4 +1118,21 @@ extern "C" int lap_decode_finish_lp(int* state, const float* pval, const int* pi
   hipLaunchKernelGGL(dec_finish_kernel<true>, dim3(1), dim3(256), 0, S_, state, pval, pidx, LM_BLOCKS, out, cap, B, eos_token, plp, logp);
   LAP_CHECK_LAUNCH();
   return LAP_OK;
+}
+
+// ---- speculative decoding (lap_amd/speculate.py; the draft, embed and accept kernels are csrc/decode_spec.hip): the QKV and
+// attention variants whose S rows are consecutive positions of one sequence.  wscale != NULL: wqkv holds e4m3 codes.
+extern "C" int lap_decode_spec_qkv(const int* state, const void* x, const float* gamma, const void* wqkv, const float* wscale, void* q,
+                                   void* cache_k, void* cache_v, int S, int D, int NH, int HD, int cap, float q_scale, float eps,
+                                   void* stream) {
+  if (S < 2) return LAP_ERR_ARG;
+  return qkv_impl(state, x, gamma, wqkv, wscale, wscale != nullptr, q, cache_k, cache_v, S, D, NH, HD, cap, q_scale, eps, stream, true);
+}
+
+extern "C" int lap_decode_spec_attention(const int* state, const void* q, const void* prefix_k, const void* prefix_v, const int* kinfo,
+                                         int Pn, const void* cache_k, const void* cache_v, int cap, void* o, float* scratch,
+                                         long long scratch_floats, int S, int NH, int NKV, int HD, void* stream) {
+  if (S < 2) return LAP_ERR_ARG;
+  return attention_impl(state, q, prefix_k, prefix_v, kinfo, Pn, cache_k, cache_v, cap, o, scratch, scratch_floats, S, NH, NKV, HD,
+                        true, stream);
 }

@@ -245,6 +245,11 @@ SIGNATURES: dict[str, list] = {
     "lap_filter_gumbel_argmax_rows_f32": [_vp, _i, _i, _i, _f, C.c_uint, C.c_uint, _i, _i, _f, _vp, _vp, _vp, _vp],
     "lap_decode_filter_words": [],
     "lap_decode_filter_finish": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
+    "lap_decode_spec_draft": [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp],
+    "lap_decode_spec_embed": [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _f, _vp],
+    "lap_decode_spec_qkv": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp],
+    "lap_decode_spec_attention": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _ll, _i, _i, _i, _i, _vp],
+    "lap_decode_spec_accept": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
 }
 
 _fn = {}
@@ -1673,3 +1678,90 @@ def decode_filter_finish(state, sampling, filt, logits, out, eos_token, logp=Non
             raise TypeError(f"decode_filter_finish: {n} holds one entry per row")
     call("lap_decode_filter_finish", _p(state), _p(sampling), _p(filt), _p(logits), _p(out), _p(logp), B, logits.shape[1], cap,
          int(eos_token), _p(kept), _p(cut))
+
+
+# ---- greedy speculative decoding of one sequence (csrc/decode_spec.hip; lap_amd/speculate.py restates the rules)
+def _spec_out(out):
+    """The token output of a speculating context: int32 [1, cap] (one sequence)."""
+    _dreq(out, torch.int32, "out")
+    if out.dim() != 2 or out.shape[0] != 1:
+        raise TypeError(f"speculative decoding serves one sequence: out [1, cap], got {tuple(out.shape)}")
+    return out.shape[1]
+
+
+def decode_spec_ref(cap, device):
+    """The reference sequence of a speculating context: int32 [1 + cap] = {its length n, ref[0 .. cap)}; a captured graph holds
+    its address and `decode_set_spec_ref` rewrites it between requests."""
+    return torch.zeros(1 + int(cap), dtype=torch.int32, device=device)
+
+
+def decode_set_spec_ref(buf, ids):
+    """ids (any integer sequence, or None: no draft) truncated to the buffer's capacity: one host-to-device copy."""
+    cap = buf.numel() - 1
+    ids = [] if ids is None else [int(i) for i in torch.as_tensor(ids).reshape(-1).tolist()][:cap]
+    host = torch.zeros(1 + cap, dtype=torch.int32)
+    host[0] = len(ids)
+    if ids:
+        host[1:1 + len(ids)] = torch.tensor(ids, dtype=torch.int32)
+    buf.copy_(host)
+
+
+def decode_spec_draft(state, refbuf, out, draft):
+    """draft[0 .. S-2] (int32 [S - 1]) = the tokens that follow the best anchor of (out[t-2], out[t-1]) in the reference
+    (lap_decode_spec_draft; `speculate.draft_tokens`)."""
+    cap = _spec_out(out)
+    _dreq(state, torch.int32, "state"); _dreq(refbuf, torch.int32, "refbuf"); _dreq(draft, torch.int32, "draft")
+    if refbuf.numel() != cap + 1:
+        raise TypeError(f"decode_spec_draft: the reference buffer holds {refbuf.numel() - 1} ids beside an out of {cap}")
+    call("lap_decode_spec_draft", _p(state), refbuf.data_ptr() + 4, _p(refbuf), _p(out), cap, _p(draft), draft.numel() + 1)
+
+
+def decode_spec_embed(state, table, row_lo, row_hi, out, draft, x, scale):
+    """x [S, D]: row 0 embeds out[t-1], row r embeds draft[r-1] (lap_decode_spec_embed)."""
+    cap = _spec_out(out)
+    _dreq(x, torch.bfloat16, "x"); _dreq(table, torch.float32, "table"); _dreq(draft, torch.int32, "draft")
+    if draft.numel() != x.shape[0] - 1:
+        raise TypeError(f"decode_spec_embed: {draft.numel()} drafted tokens for {x.shape[0]} rows")
+    call("lap_decode_spec_embed", _p(state), _p(table), int(row_lo), int(row_hi), _p(out), _p(draft), cap, _p(x), x.shape[0],
+         x.shape[1], float(scale))
+
+
+def decode_spec_qkv(state, x, gamma, wqkv, q, cache_k, cache_v, NH, HD, q_scale, eps=1e-6, wscale=None):
+    """`decode_qkv` whose S rows are the positions t-1 .. t-1+S-1 of one sequence: cache_k / cache_v bf16 [cap, HD] (or [1, cap,
+    HD]) of that sequence, q [S, NH * HD] (lap_decode_spec_qkv)."""
+    for t, n in ((x, "x"), (q, "q"), (cache_k, "cache_k"), (cache_v, "cache_v")):
+        _dreq(t, torch.bfloat16, n)
+    _dreq(gamma, torch.float32, "gamma")
+    S, D = x.shape
+    if cache_k.numel() != cache_v.numel() or cache_k.numel() % HD or q.shape[0] != S:
+        raise TypeError("decode_spec_qkv: caches [cap, HD] of one sequence and q of S rows")
+    if wscale is not None:
+        _f8req(wqkv, wscale, "wqkv")
+    else:
+        _dreq(wqkv, torch.bfloat16, "wqkv")
+    call("lap_decode_spec_qkv", _p(state), _p(x), _p(gamma), _p(wqkv), _p(wscale), _p(q), _p(cache_k), _p(cache_v), S, D, NH, HD,
+         cache_k.numel() // HD, float(q_scale), float(eps))
+
+
+def decode_spec_attention(state, q, prefix_k, prefix_v, kinfo, Pn, cache_k, cache_v, o, scratch, NH, NKV, HD):
+    """`decode_attention` whose row r is q row r against the prefix of sample 0 and min(t + r, cap) generated keys of the one
+    sequence; scratch as `decode_attn_scratch(S, Pn, cap)` (lap_decode_spec_attention)."""
+    for t, n in ((q, "q"), (prefix_k, "prefix_k"), (prefix_v, "prefix_v"), (cache_k, "cache_k"), (cache_v, "cache_v"), (o, "o")):
+        _dreq(t, torch.bfloat16, n)
+    _dreq(kinfo, torch.int32, "kinfo"); _dreq(scratch, torch.float32, "scratch")
+    if prefix_k.numel() < Pn * HD or prefix_v.numel() < Pn * HD or kinfo.numel() < Pn or o.shape[0] != q.shape[0]:
+        raise TypeError("decode_spec_attention: a prefix of Pn keys with its kinfo words, and o beside q")
+    call("lap_decode_spec_attention", _p(state), _p(q), _p(prefix_k), _p(prefix_v), _p(kinfo), int(Pn), _p(cache_k), _p(cache_v),
+         cache_k.numel() // HD, _p(o), _p(scratch), scratch.numel(), q.shape[0], NH, NKV, HD)
+
+
+def decode_spec_accept(state, pval, pidx, draft, out, eos_token):
+    """The finish of a verify step: the per-row argmax of the S = draft.numel() + 1 rows of partials, then the accept rule
+    (lap_decode_spec_accept; `speculate.accept`)."""
+    cap = _spec_out(out)
+    _dreq(state, torch.int32, "state"); _dreq(pval, torch.float32, "pval"); _dreq(pidx, torch.int32, "pidx")
+    _dreq(draft, torch.int32, "draft")
+    S = draft.numel() + 1
+    if pval.numel() < S * _fn["lap_decode_lm_blocks"]() or pidx.numel() < S * _fn["lap_decode_lm_blocks"]():
+        raise TypeError("decode_spec_accept: pval / pidx hold [lap_decode_lm_blocks()][S] partials")
+    call("lap_decode_spec_accept", _p(state), _p(pval), _p(pidx), _p(draft), _p(out), S, cap, int(eos_token))

@@ -693,7 +693,7 @@ class LAP:
 
     def sample_tokens(self, rng, observation, *, max_decoding_steps: int = 390, temperature: float = 0.0, collect=None,
                       decode: str = "eager", sampler: str = "host", decode_weights: str = "bf16", allowed_tokens=None,
-                      return_logprobs: bool = False, num_samples=None, top_k=None, top_p=None):
+                      return_logprobs: bool = False, num_samples=None, top_k=None, top_p=None, speculate=None, draft_tokens=None):
         """lap.py:678-766 (LAP_AR serving mode): VLM-only prefill, then single-token decode until every sample has emitted
         EOS or `max_decoding_steps` tokens; returns int32 [B, max_decoding_steps] (zeros after the stop).
 
@@ -764,14 +764,27 @@ class LAP:
         lap_filter_gumbel_argmax_rows_f32; decode="fused" lets the plain LM head store its f32 logits and draws with
         lap_decode_filter_finish (one more launch per token than the unfiltered fused step).  `return_logprobs` and best-of-N keep
         their meaning: a log-probability is the log-softmax over ALL candidates at tau = inv_t, the model's probability of the
-        token, not its probability inside the kept set; `select_best` ranks by it.  The reference has no such option."""
+        token, not its probability inside the kept set; `select_best` ranks by it.  The reference has no such option.
+
+        speculate, draft_tokens: exact greedy speculative decoding.  None (default): one token per pass over the weights, as
+        before.  speculate=S, 2 <= S <= 8 (observation of batch 1, decode="fused", greedy; temperature > 0, return_logprobs,
+        num_samples, top_k / top_p and collect raise ValueError): every fused step verifies S consecutive positions of the sequence
+        at once, row 0 the real next position and rows 1 .. S-1 the tokens drafted from `draft_tokens`, an integer sequence that is
+        expected to resemble the answer (in a control loop: the previous request's answer; None drafts nothing).  The draft is
+        the continuation of the reference after the nearest match of the last two generated tokens (`speculate.draft_tokens`);
+        the step emits the first row's token and every following row's while the drafts before it were right
+        (`speculate.accept`).  Every row of the fused kernels is accumulated independently of the batch width, so the returned
+        tokens are those of the call without `speculate`, whatever the draft; only the number of passes over the weights changes
+        (`last_spec_stats` = (verify steps, drafts accepted) of the request).  Composes with decode_weights and allowed_tokens.
+        The reference has no such option."""
         from lap_amd import ar_decode       # (it imports this module)
         return ar_decode.sample_tokens(self, rng, observation, max_decoding_steps=max_decoding_steps, temperature=temperature,
                                        collect=collect, decode=decode, sampler=sampler, decode_weights=decode_weights,
                                        allowed_tokens=allowed_tokens, return_logprobs=return_logprobs, num_samples=num_samples,
-                                       top_k=top_k, top_p=top_p)
+                                       top_k=top_k, top_p=top_p, speculate=speculate, draft_tokens=draft_tokens)
 
     DECODE_WEIGHTS = ("bf16", "fp8", "fp8_layers")
+    last_spec_stats = None      # (verify steps, drafts accepted) of the last `sample_tokens(speculate=S)` request
 
     def decode_supported(self, B: int) -> bool:
         """Whether `sample_tokens(decode="fused")` / `GraphedTokenDecoder` serve `B` rows of this model."""

@@ -118,11 +118,24 @@ class GraphedTokenDecoder:
     (the plain LM head stores its f32 logits, lap_decode_filter_finish draws from them); `__call__(obs, temperature=, seed=,
     top_k=, top_p=)` rewrites four more device words before the first replay, so one capture serves any k and p, and a call with
     neither returns the filtering=False decoder's tokens.  Composes with weights=, allowed_tokens=, logprobs= (the log-probability
-    stays the one over all candidates) and num_samples=."""
+    stays the one over all candidates) and num_samples=.
+
+    speculate=S (2 <= S <= 8; batch_size 1, greedy: sampling=, logprobs=, num_samples= and filtering= raise ValueError):
+    `sample_tokens`' exact speculative decoding.  The step graph is captured on verify steps of S rows, and the reference sequence
+    lives in one device buffer that `__call__(obs, draft_tokens=ids_or_None)` rewrites before the first replay, so one step graph
+    serves any draft.  A call returns the tokens of the decoder without it; `last_stats` = (verify_steps, accepted) of the call.
+    Composes with weights= and allowed_tokens=."""
 
     def __init__(self, model: LAP, batch_size: int = 1, max_decoding_steps: int = 390, prompt_len: int | None = None,
                  steps_per_replay: int = 8, sampling: bool = False, weights: str = "bf16", allowed_tokens=None,
-                 logprobs: bool = False, num_samples=None, filtering: bool = False):
+                 logprobs: bool = False, num_samples=None, filtering: bool = False, speculate=None):
+        self.S = None
+        self.last_stats = None
+        if speculate is not None:
+            from lap_amd.speculate import check_speculate
+
+            self.S = check_speculate(speculate, batch_size, return_logprobs=logprobs, num_samples=num_samples,
+                                     temperature=1.0 if sampling else 0.0, top_k=0 if filtering else None)
         if filtering and not sampling:
             raise ValueError("GraphedTokenDecoder: filtering needs a decoder built with sampling=True")
         self.filtering = bool(filtering)
@@ -170,7 +183,7 @@ class GraphedTokenDecoder:
             pre = ar_decode.replicate_prefill(pre, self.N)
         if self.ctx is None:
             self.ctx = ar_decode.DecodeCtx(self.model, pre.B, pre.Pn, self.max_steps, self.sampling, self.weights,
-                                           allowed=self.allowed, logprobs=self.logprobs, filtering=self.filtering)
+                                           allowed=self.allowed, logprobs=self.logprobs, filtering=self.filtering, speculate=self.S)
         self.ctx.first_token(pre)
 
     def _steps(self):
@@ -197,7 +210,9 @@ class GraphedTokenDecoder:
         torch.cuda.synchronize()
         return self
 
-    def __call__(self, obs: CoTObservation, *, temperature: float = 0.0, seed: int = 0, top_k=None, top_p=None):
+    def __call__(self, obs: CoTObservation, *, temperature: float = 0.0, seed: int = 0, top_k=None, top_p=None, draft_tokens=None):
+        if draft_tokens is not None and self.S is None:
+            raise ValueError("GraphedTokenDecoder: draft_tokens needs a decoder built with speculate=S")
         if temperature > 0.0 and not self.sampling:
             raise ValueError("GraphedTokenDecoder: temperature > 0 needs a decoder built with sampling=True")
         filt = ar_decode.check_filter(top_k, top_p, sampler="device", temperature=temperature)
@@ -214,11 +229,15 @@ class GraphedTokenDecoder:
             self.ctx.set_sampling(seed, temperature)
         if self.filtering:
             self.ctx.set_filter(*(filt or (None, None)))
+        if self.S is not None:
+            self.ctx.set_draft(draft_tokens)
         self.g_prefill.replay()
         for _ in range((self.max_steps - 1 + self.spr - 1) // self.spr):
             if bool(self.ctx.state[1].item()):      # one host read per replay
                 break
             self.g_step.replay()
+        if self.S is not None:
+            self.last_stats = self.ctx.stats()
         if self.logprobs:
             return self.ctx.out.clone(), self.ctx.logp.clone()
         return self.ctx.out.clone()
@@ -397,12 +416,24 @@ class ARPolicy:
         self._filter = {k: self._sample_kwargs[k] for k in ("top_k", "top_p") if self._sample_kwargs.get(k) is not None}
         ar_decode.check_filter(self._filter.get("top_k"), self._filter.get("top_p"), sampler=self._sample_kwargs.get("sampler", "host"),
                                temperature=self._sample_kwargs.get("temperature", 0.0))
+        # sample_kwargs["speculate"] = S (exact greedy speculative decoding; implies decode="fused") reaches both routes: the
+        # policy keeps the previous answer's tokens, up to and including the EOS, and passes them as the draft of the next request
+        # (the first request drafts nothing); "policy_timing" gains "spec_steps" and "spec_accepted"
+        self._speculate = self._sample_kwargs.get("speculate")
+        self._prev_tokens = None
+        if self._speculate is not None:
+            from lap_amd.speculate import check_speculate
+
+            check_speculate(self._speculate, 1, decode=self._sample_kwargs.setdefault("decode", "fused"),
+                            temperature=self._sample_kwargs.get("temperature", 0.0), return_logprobs=self._logprobs,
+                            num_samples=self._num_samples, top_k=self._sample_kwargs.get("top_k"), top_p=self._sample_kwargs.get("top_p"),
+                            collect=self._sample_kwargs.get("collect"))
         if use_graph and base.model.decode_supported(self._num_samples or 1):
             self._decoder = GraphedTokenDecoder(base.model, 1, self._sample_kwargs.get("max_decoding_steps", 390),
-                                                sampling=self._device_sampler, weights=weights,
+                                                sampling=self._device_sampler and self._speculate is None, weights=weights,
                                                 allowed_tokens=self._sample_kwargs.get("allowed_tokens"),
                                                 logprobs=self._logprobs, num_samples=self._num_samples,
-                                                filtering=bool(self._filter) and self._device_sampler)
+                                                filtering=bool(self._filter) and self._device_sampler, speculate=self._speculate)
 
     def __getattr__(self, name):
         return getattr(self._base, name)
@@ -419,12 +450,24 @@ class ARPolicy:
         o, batched = base._to_observation(inputs)
         self._calls += 1
         temperature = self._sample_kwargs.get("temperature", 0.0)
+        spec_stats = None
         if (self._decoder is not None and (temperature <= 0.0 or self._device_sampler)
                 and self._sample_kwargs.get("decode", "eager") in ("eager", "fused") and graph_compatible(self._decoder.obs, o)):
-            tokens = (self._decoder(o, temperature=temperature, seed=self._calls, **self._filter) if self._device_sampler
-                      else self._decoder(o))
+            if self._speculate is not None:
+                tokens = self._decoder(o, draft_tokens=self._prev_tokens)
+                spec_stats = self._decoder.last_stats
+            else:
+                tokens = (self._decoder(o, temperature=temperature, seed=self._calls, **self._filter) if self._device_sampler
+                          else self._decoder(o))
+        elif self._speculate is not None:
+            tokens = base.model.sample_tokens(self._calls, o, draft_tokens=self._prev_tokens, **self._sample_kwargs)
+            spec_stats = base.model.last_spec_stats
         else:
             tokens = base.model.sample_tokens(self._calls, o, **self._sample_kwargs)
+        if self._speculate is not None:     # the next request's draft: this answer up to and including its EOS
+            row = tokens[0].cpu().numpy()
+            stop = np.flatnonzero(row == base.model.EOS_TOKEN)
+            self._prev_tokens = row[:int(stop[0]) + 1] if stop.size else row
         extra = {}
         if self._logprobs:
             from lap_amd import sampling
@@ -444,6 +487,8 @@ class ARPolicy:
         if base._has_transforms:      # (the output stack keeps the keys it knows, CoTOutputs: actions and reasoning; the
             out = base._output_transform(out) | extra       # log-probabilities and the candidates go round it to the client)
         out["policy_timing"] = {"infer_ms": model_ms}
+        if spec_stats is not None:
+            out["policy_timing"] |= {"spec_steps": spec_stats[0], "spec_accepted": spec_stats[1]}
         return out
 
     def infer(self, obs: dict, *, noise=None) -> dict:
@@ -470,7 +515,10 @@ def create_trained_policy_ar(*args, sample_kwargs: dict | None = None, language_
     sample_kwargs={"top_k": k, "top_p": p} (with "temperature" > 0 and "sampler": "device") draws every token among the k most
     likely candidates and, of those, the nucleus of mass p (`LAP.sample_tokens`; `sampling.filter_keep` restates the kept set) on
     either route: the decoder is captured with filtering=True when either is present; log-probabilities stay the model's (over
-    all candidates), so best-of-N ranks as before.  These keys are added to what the output stack
+    all candidates), so best-of-N ranks as before;
+    sample_kwargs={"speculate": S} (2 <= S <= 8, greedy; implies decode="fused") decodes every request on verify steps of S rows
+    with the previous request's answer as the draft (`LAP.sample_tokens`): the tokens are unchanged, and "policy_timing" gains
+    "spec_steps" and "spec_accepted".  These keys are added to what the output stack
     returns ({"actions", "reasoning"}), so a client of this policy and of the websocket server receives them."""
     from lap_amd import policy_io as pio
 

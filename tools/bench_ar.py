@@ -4,7 +4,7 @@ rate against the 6.29 TB/s measured copy rate.  Random weights, the reference pr
 run decodes N tokens.  One JSON line.
 
     python tools/bench_ar.py [--tokens 64] [--config lap_bench] [--kwaves 4] [--temperature T] [--weights bf16 fp8 fp8_layers]
-                             [--allowed N] [--logprobs] [--num-samples N]
+                             [--allowed N] [--logprobs] [--num-samples N] [--speculate S [S ...]]
 
 --temperature T > 0 adds the sampled figures: the eager loop with the torch-generator noise (sampler="host"), the eager loop and
 the fused steps with the device noise (sampler="device"), and a GraphedTokenDecoder(sampling=True) called sampled and greedy.
@@ -26,6 +26,11 @@ sampling graph.
 rows, next to one sampled row with log-probabilities on the same kernels, and both prefill graphs (the N-row one ends with the copies).
 The fused best-of-N figure subtracts the plain batch-1 prefill, so the copies to N rows and the allocation of the N-row context are
 spread into its ms per token; the graphed figures subtract their own prefill graph and are the ones to quote.
+--speculate S [S ...] adds exact speculative decoding (`speculate=S`) for bf16 and every --weights value, in the same process as
+the plain graph of those weights: a GraphedTokenDecoder(speculate=S) called with the answer itself as the draft (full acceptance)
+and without a draft (zero acceptance, the price of a wrong guess), each as the mean and [min, max] of the timed repeats; ms per
+verify step, ms per token, whether the tokens equal the plain graph's, and the break-even the two imply: the mean tokens per
+verify step, and the share of the S - 1 drafts that must be accepted, at which a speculating decode costs what the plain one does.
 """
 import argparse
 import json
@@ -56,6 +61,7 @@ ap.add_argument("--num-samples", type=int, default=0, help="N > 0: also measure 
                 "sampled at --temperature, or at 1.0 when that is 0")
 ap.add_argument("--top-k", type=int, default=0, help="with --temperature: also measure filtered sampled decoding (top_k)")
 ap.add_argument("--top-p", type=float, default=1.0, help="with --temperature: also measure filtered sampled decoding (top_p)")
+ap.add_argument("--speculate", type=int, nargs="+", default=[], help="also measure exact speculative decoding at these verify-step widths")
 a = ap.parse_args()
 hip.DECODE_KWAVES_DOWN = a.kwaves
 
@@ -223,6 +229,41 @@ if a.num_samples > 0:   # N rows from one batch-1 prefill against one sampled ro
         "graphed_ms_per_token_over_one_row": round(per(t_ngraph, t_npre) / per(t_1graph, t_1pre), 4),
         "one_row_graphed_prefill_ms": round(t_1pre, 3), "graphed_prefill_ms": round(t_npre, 3),
         "distinct_rows": len({tuple(r) for r in ntok.tolist()})}}
+speculative = {}
+if a.speculate:
+    def spread(fn):
+        ms = [timeit(fn, 1) for _ in range(max(a.reps, 3))]
+        return sum(ms) / len(ms), [round(min(ms), 3), round(max(ms), 3)]
+
+    for wname in dict.fromkeys(["bf16", *a.weights]):
+        pdec = GraphedTokenDecoder(model, 1, N, weights=wname).capture()
+        t_ppre = timeit(lambda: (pdec.g_prefill.replay()), a.reps)
+        t_plain, plain_mm = spread(lambda: pdec(o))
+        answer = pdec(o)
+        draft = answer[0].tolist()
+        plain_ms = per(t_plain, t_ppre)
+        rows = {"plain_graphed_ms_per_token": round(plain_ms, 3),
+                "plain_graphed_ms_per_token_min_max": [round(per(x, t_ppre), 3) for x in plain_mm]}
+        for S in a.speculate:
+            sd = GraphedTokenDecoder(model, 1, N, weights=wname, speculate=S).capture()
+            t_spre = timeit(lambda: (sd.g_prefill.replay()), a.reps)
+            t_full, full_mm = spread(lambda: sd(o, draft_tokens=draft))
+            full_tok, full_stats = sd(o, draft_tokens=draft), sd.last_stats
+            t_zero, zero_mm = spread(lambda: sd(o))
+            zero_tok, zero_stats = sd(o), sd.last_stats
+            step_ms = (t_zero - t_spre) / zero_stats[0]       # (every verify step of a decode without a draft emits one token)
+            rows[f"S{S}"] = {
+                "verify_step_ms": round(step_ms, 3), "verify_step_ms_at_full_acceptance": round((t_full - t_spre) / full_stats[0], 3),
+                "full_acceptance_ms_per_token": round(per(t_full, t_spre), 3),
+                "full_acceptance_ms_per_token_min_max": [round(per(x, t_spre), 3) for x in full_mm],
+                "zero_acceptance_ms_per_token": round(per(t_zero, t_spre), 3),
+                "zero_acceptance_ms_per_token_min_max": [round(per(x, t_spre), 3) for x in zero_mm],
+                "full_acceptance_verify_steps_accepted": list(full_stats), "zero_acceptance_verify_steps_accepted": list(zero_stats),
+                "speedup_at_full_acceptance": round(plain_ms / per(t_full, t_spre), 3),
+                "break_even_tokens_per_verify_step": round(step_ms / plain_ms, 3),
+                "break_even_draft_acceptance_rate": round((step_ms / plain_ms - 1) / (S - 1), 3),
+                "tokens_equal_plain_graph": bool(torch.equal(full_tok, answer) and torch.equal(zero_tok, answer))}
+        speculative[wname] = rows
 print(json.dumps({
     "metric": "batch-1 LAP_AR decode LAP-3B bf16 (ms per token after the prefill, greedy, EOS disabled)",
     "tokens": N, "prompt_len": cfg.max_token_len,
@@ -233,4 +274,4 @@ print(json.dumps({
     "algorithmic_bytes_per_token": bytes_tok, "floor_ms_per_token_at_6.29TBps": round(bytes_tok / 6.29e12 * 1e3, 3),
     "achieved_GBps_graphed": round(bytes_tok / (g_ms * 1e-3) / 1e9, 1),
     "share_of_6.29TBps": round(bytes_tok / (g_ms * 1e-3) / 6.29e12, 3), "down_proj_kwaves": a.kwaves} | sampled | ({"weights": quant} if quant else {})
-    | ({"allowed": a.allowed, "constrained": constrained} if constrained else {}) | logprobs | best_of))
+    | ({"allowed": a.allowed, "constrained": constrained} if constrained else {}) | logprobs | best_of | ({"speculate": speculative} if speculative else {})))
