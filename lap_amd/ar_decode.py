@@ -110,12 +110,71 @@ def check_filter(top_k, top_p, *, sampler: str, temperature: float):
     return k, p
 
 
+def check_grammar(grammar, vocab_size: int, eos_token: int, *, allowed_tokens=None, top_k=None, top_p=None, speculate=None,
+                  sampler: str = "device", temperature: float = 0.0):
+    """The host automaton of a grammar-constrained request (`grammar`: a grammar.TokenAutomaton or its `to_device` form), checked
+    (`grammar.check_automaton`) and compared with the model's vocabulary and EOS token; ValueError naming what it does not
+    combine with: allowed_tokens (the automaton's union replaces the set), top_k / top_p, speculate, and the host sampler at
+    temperature > 0 (the constrained draw is part of the device sampler)."""
+    from lap_amd.grammar import DeviceAutomaton, TokenAutomaton, check_automaton
+
+    host = grammar.host if isinstance(grammar, DeviceAutomaton) else grammar
+    if not isinstance(host, TokenAutomaton):
+        raise ValueError(f"grammar: expected a grammar.TokenAutomaton (or its to_device form), got {type(grammar).__name__}")
+    if allowed_tokens is not None:
+        raise ValueError("grammar does not combine with allowed_tokens: the union of the automaton's edges replaces the set")
+    if top_k is not None or top_p is not None:
+        raise ValueError("grammar does not combine with top_k / top_p")
+    if speculate is not None:
+        raise ValueError("grammar does not combine with speculate")
+    if sampler != "device" and temperature > 0.0:
+        raise ValueError(f"grammar at temperature > 0 needs sampler=\"device\" (the constrained draw is part of the device sampler), "
+                         f"got sampler={sampler!r}")
+    if (host.vocab_size, host.eos_token) != (vocab_size, eos_token):
+        raise ValueError(f"grammar: the automaton was built for vocab_size {host.vocab_size} and EOS token {host.eos_token}, the model "
+                         f"has vocab_size {vocab_size} and EOS token {eos_token}")
+    if not isinstance(grammar, DeviceAutomaton):        # (`to_device` has checked the other form)
+        check_automaton(host)
+    return host
+
+
+def _on_device(t: torch.Tensor, device) -> bool:
+    """Whether tensor `t` lives on `device`, index included ("cuda" names the current device)."""
+    dev = torch.device(device)
+    if t.device.type != dev.type:
+        return False
+    if dev.type != "cuda":
+        return True
+    return t.device.index == (torch.cuda.current_device() if dev.index is None else dev.index)
+
+
+def grammar_on_device(model: LAP, grammar, host):
+    """The automaton `grammar`, whose host form `check_grammar` returned as `host`, on the model's device: a DeviceAutomaton that
+    is already there is handed back as it is, so a server copies its automaton at start-up and not per request; anything else is
+    copied from `host` without a second `check_automaton`."""
+    from lap_amd.grammar import DeviceAutomaton
+
+    if isinstance(grammar, DeviceAutomaton) and _on_device(grammar.ids, model.device):
+        return grammar
+    return host.to_device(model.device, check=False)
+
+
+def device_grammar(model: LAP, grammar, **combined):
+    """`check_grammar` for `model` (one `check_automaton` of a host automaton), then `grammar_on_device`."""
+    return grammar_on_device(model, grammar, check_grammar(grammar, model.config.vocab_size, model.EOS_TOKEN, **combined))
+
+
 def sample_tokens(model: LAP, rng, observation, *, max_decoding_steps: int = 390, temperature: float = 0.0, collect=None,
                   decode: str = "eager", sampler: str = "host", decode_weights: str = "bf16", allowed_tokens=None,
-                  return_logprobs: bool = False, num_samples=None, top_k=None, top_p=None, speculate=None, draft_tokens=None):
+                  return_logprobs: bool = False, num_samples=None, top_k=None, top_p=None, speculate=None, draft_tokens=None,
+                  grammar=None):
     """`LAP.sample_tokens` (documented there): every argument is checked before any device work."""
     if decode not in ("eager", "fused"):
         raise ValueError(f"sample_tokens: decode must be 'eager' or 'fused', got {decode!r}")
+    grammar_host = None
+    if grammar is not None:
+        grammar_host = check_grammar(grammar, model.config.vocab_size, model.EOS_TOKEN, allowed_tokens=allowed_tokens, top_k=top_k,
+                                     top_p=top_p, speculate=speculate, sampler=sampler, temperature=temperature)
     S = None
     if speculate is not None:
         S = check_speculate(speculate, observation.tokenized_prompt.shape[0], decode=decode, temperature=temperature,
@@ -138,17 +197,19 @@ def sample_tokens(model: LAP, rng, observation, *, max_decoding_steps: int = 390
     allowed = None
     if allowed_tokens is not None:
         allowed = allowed_set(model, allowed_tokens).ids
+    if grammar is not None:
+        grammar = grammar_on_device(model, grammar, grammar_host)
     with model._serving_weights():
         if decode == "fused" and (sampler == "device" or temperature <= 0.0):   # (the host sampler's noise cannot run on the device state)
             return _sample_fused(model, observation, max_decoding_steps=max_decoding_steps, collect=collect,
                                  sampling=(rng, temperature) if sampler == "device" else None, weights=decode_weights,
                                  allowed=allowed, logprobs=return_logprobs or N is not None, num_samples=N, filt=filt,
-                                 speculate=S, draft=draft_tokens)
+                                 speculate=S, draft=draft_tokens, grammar=grammar)
         if decode_weights != "bf16":
             raise ValueError("sample_tokens: decode_weights other than 'bf16' with temperature > 0 needs sampler='device' (the "
                              "host sampler keeps the eager loop)")
         return _sample_eager(model, rng, observation, max_decoding_steps=max_decoding_steps, temperature=temperature, collect=collect,
-                             device_sampler=sampler == "device", allowed=allowed, logprobs=return_logprobs, filt=filt)
+                             device_sampler=sampler == "device", allowed=allowed, logprobs=return_logprobs, filt=filt, grammar=grammar)
 
 
 class Prefill(NamedTuple):
@@ -240,9 +301,34 @@ def _lm_logits(model: LAP, rows):
     return lm_logits(model, pl, 0, model.config.vocab_size)      # the f32 table as hi + lo, as in the training loss
 
 
+def _grammar_mask(g, q, V: int):
+    """bool [B, V]: the ids the state q[b] (int64 device [B]) of the device automaton `g` allows, per row."""
+    counts = g.offsets[1:] - g.offsets[:-1]
+    edge_state = torch.repeat_interleave(torch.arange(counts.numel(), device=q.device), counts.long())
+    rows, cols = (edge_state[None, :] == q[:, None]).nonzero(as_tuple=True)
+    mask = torch.zeros((q.numel(), V), dtype=torch.bool, device=q.device)
+    mask[rows, g.ids[cols].long()] = True
+    return mask
+
+
+def _grammar_step(g, q, token):
+    """The states after `token` [B]: a binary search (`torch.searchsorted`) for the token in the segment of q[b].  A segment's
+    ids ascend and the segments follow in state order, so (state, id) ascends over the whole edge array; the search of
+    (q[b], token[b]) in it lands inside the segment of q[b]."""
+    lo, hi = g.offsets[q].long(), g.offsets[q + 1].long()
+    counts = (g.offsets[1:] - g.offsets[:-1]).long()
+    V = int(g.host.vocab_size)
+    key = torch.repeat_interleave(torch.arange(counts.numel(), device=q.device), counts) * V + g.ids.long()
+    pos = torch.searchsorted(key, q * V + token.long()).clamp_(max=key.numel() - 1)
+    ok = (pos >= lo) & (pos < hi) & (g.ids[pos].long() == token.long())
+    return torch.where(ok, g.next[pos].long(), q)       # (a token outside the segment: only from a row of -inf; the state stays)
+
+
 def _sample_eager(model: LAP, rng, observation, *, max_decoding_steps: int, temperature: float, collect, device_sampler: bool,
-                  allowed=None, logprobs: bool = False, filt=None):
-    """allowed: int32 device ids; the logits outside the set are -inf before the argmax or the noise.  logprobs: also the f32
+                  allowed=None, logprobs: bool = False, filt=None, grammar=None):
+    """grammar: a DeviceAutomaton; the mask of every row's state is built with torch ops, the draw is the unconstrained one on the
+    masked logits, the transition a `torch.searchsorted` (slow and simple: the second implementation beside the fused route).
+    allowed: int32 device ids; the logits outside the set are -inf before the argmax or the noise.  logprobs: also the f32
     log_softmax of logits * inv_t (over the allowed set) at every token, returned beside the tokens: over all candidates, also
     when filt = (top_k, top_p) narrows the draw (lap_filter_gumbel_argmax_rows_f32)."""
     dev = model.device
@@ -258,10 +344,13 @@ def _sample_eager(model: LAP, rng, observation, *, max_decoding_steps: int, temp
     if allowed is not None:
         outside = torch.ones((model.config.vocab_size,), dtype=torch.bool, device=dev)
         outside[allowed.long()] = False
+    gq = torch.zeros((B,), dtype=torch.int64, device=dev) if grammar is not None else None
     step = 0
     while step < max_decoding_steps:
         if outside is not None:
             logits = logits.masked_fill(outside, float("-inf"))
+        if gq is not None:
+            logits = logits.masked_fill(~_grammar_mask(grammar, gq, model.config.vocab_size), float("-inf"))
         raw = logits
         if device_sampler and temperature > 0.0:      # one pass over the raw logits, no [B, V] temporaries
             if filt is not None:
@@ -276,6 +365,8 @@ def _sample_eager(model: LAP, rng, observation, *, max_decoding_steps: int, temp
         if collect is not None:
             collect[f"logit/{step}"] = logits.clone()
         out[:, step] = token
+        if gq is not None:
+            gq = _grammar_step(grammar, gq, token)
         if logp is not None:
             z = raw * inv_t if inv_t != 0.0 else raw
             logp[:, step] = torch.log_softmax(z, dim=-1).gather(1, token.view(B, 1).long()).view(B)
@@ -290,8 +381,9 @@ def _sample_eager(model: LAP, rng, observation, *, max_decoding_steps: int, temp
 
 # ---- the fused step: single-token kernels, state on the device (csrc/decode.hip)
 def _sample_fused(model: LAP, observation, *, max_decoding_steps: int, collect=None, sampling=None, weights: str = "bf16",
-                  allowed=None, logprobs: bool = False, num_samples=None, filt=None, speculate=None, draft=None):
-    """sampling: None (the greedy LM head) or (seed, temperature) for the sampling LM head.  weights: `decode_weights`.
+                  allowed=None, logprobs: bool = False, num_samples=None, filt=None, speculate=None, draft=None, grammar=None):
+    """grammar: None, or a DeviceAutomaton: a grammar context.
+    sampling: None (the greedy LM head) or (seed, temperature) for the sampling LM head.  weights: `decode_weights`.
     filt: None, or (top_k, top_p): a filtering context (it needs `sampling`).
     allowed: None or the int32 device ids of `check_allowed_tokens`.  logprobs: the context keeps the token log-probabilities
     and (tokens, logprobs) is returned.  num_samples: the batch-1 prefill is replicated to that many rows.
@@ -301,7 +393,7 @@ def _sample_fused(model: LAP, observation, *, max_decoding_steps: int, collect=N
     if num_samples is not None:
         pre = replicate_prefill(pre, num_samples)
     ctx = DecodeCtx(model, pre.B, pre.Pn, max_decoding_steps, sampling is not None, weights, allowed=allowed, logprobs=logprobs,
-                    filtering=filt is not None, speculate=speculate)
+                    filtering=filt is not None, speculate=speculate, grammar=grammar)
     if speculate is not None:
         ctx.set_draft(draft)
     if sampling is not None:
@@ -311,7 +403,7 @@ def _sample_fused(model: LAP, observation, *, max_decoding_steps: int, collect=N
     lg = None
     if collect is not None:     # (the constrained LM head writes the allowed columns only: the rest keeps the fill)
         lg = torch.empty((pre.B, model.config.vocab_size), dtype=torch.float32, device=model.device)
-        if allowed is not None:
+        if allowed is not None or grammar is not None:
             lg.fill_(float("-inf"))
     ctx.first_token(pre, lg)
     if collect is not None:     # debug: one host read per token
@@ -343,11 +435,22 @@ class DecodeCtx:
     activations, the attention scratch and the LM partials hold S rows; a reference sequence and its length live in one device
     buffer at a fixed address (`set_draft`).  `first_token` runs the B = 1 head and finish; `step` drafts S - 1 tokens from the
     reference, runs the layers on the S positions t-1 .. t-1+S-1 and accepts the longest verified run; `stats` reads the
-    counters.  The tokens are those of the context without it."""
+    counters.  The tokens are those of the context without it.
+    grammar=DeviceAutomaton (not with allowed, filtering or speculate): the context draws every row's token among the edges of
+    the automaton state that row is in (lap_amd/grammar.py).  It owns `gstate` (int32 [B], zeroed by `first_token` with a device
+    op that a captured prefill replays) and a [B, V] f32 logits buffer, written to -inf once; its LM head is the plain SUBSET head
+    (bf16 or fp8) over the automaton's union, which stores its logits there, and lap_decode_grammar_finish draws from them, moves
+    `gstate` and does the finish's bookkeeping, with the log-probability over the state's set when logprobs is on."""
 
     def __init__(self, model: LAP, B: int, Pn: int, cap: int, sampling: bool = False, weights: str = "bf16", allowed=None,
-                 logprobs: bool = False, filtering: bool = False, speculate=None):
+                 logprobs: bool = False, filtering: bool = False, speculate=None, grammar=None):
         check_decode_weights(weights)
+        if grammar is not None:
+            check_grammar(grammar, model.config.vocab_size, model.EOS_TOKEN, allowed_tokens=allowed, top_k=0 if filtering else None,
+                          speculate=speculate)
+            if not grammar.ids.is_cuda:
+                raise ValueError("DecodeCtx: grammar must be the automaton on the device (TokenAutomaton.to_device)")
+        self.grammar = grammar          # None, or the device automaton (captured graphs keep its buffers' addresses)
         self.S = None
         if speculate is not None:
             self.S = check_speculate(speculate, B, return_logprobs=logprobs, temperature=1.0 if sampling else 0.0)
@@ -383,7 +486,7 @@ class DecodeCtx:
         # logprobs: the log-probability of every token of `out` beside it (f32 [B, cap], zeros where nothing was written) and the
         # LM head's log-sum-exp partials; None: the context launches the heads without them
         self.logp = torch.zeros((B, cap), dtype=torch.float32, device=dev) if logprobs else None
-        self.plp = hip.decode_lm_logp_partials(B, dev) if logprobs else None
+        self.plp = hip.decode_lm_logp_partials(B, dev) if logprobs and grammar is None else None
         # filtering: the filter words {top_k, bits of top_p, 0, 0} (neutral until `set_filter`) and the f32 logits of the step, which
         # keep -inf outside an allowed set (the constrained head writes the allowed columns only)
         self.filter = hip.decode_filter(dev) if filtering else None
@@ -392,6 +495,12 @@ class DecodeCtx:
             self.logits = torch.empty((B, model.config.vocab_size), dtype=torch.float32, device=dev)
             if allowed is not None:
                 self.logits.fill_(float("-inf"))
+        # grammar: the automaton state of every row, and the f32 logits of the step (-inf outside the union, written once: the
+        # SUBSET head writes the union's columns only)
+        self.gstate = None
+        if grammar is not None:
+            self.gstate = torch.zeros((B,), dtype=torch.int32, device=dev)
+            self.logits = torch.full((B, model.config.vocab_size), float("-inf"), dtype=torch.float32, device=dev)
         self.prefix = None
         self.kinfo = None
 
@@ -434,6 +543,8 @@ class DecodeCtx:
         hip.decode_init(self.state, self.plen, self.out)
         if self.logp is not None:
             self.logp.zero_()
+        if self.gstate is not None:       # every request starts in state 0 (a device op: the prefill graph captures it)
+            self.gstate.zero_()
         self._token(pre.x_last, logits)
 
     def _w(self, name):
@@ -458,6 +569,14 @@ class DecodeCtx:
         if verify:
             hip.decode_lm_head(self.state, x, m.F("llm/final_norm"), hi, lo, self.pval, self.pidx, None, **kw)
             hip.decode_spec_accept(self.state, self.pval, self.pidx, self.draft, self.out, m.EOS_TOKEN)
+            return
+        if self.grammar is not None:      # the plain head over the union stores the logits, the grammar kernel draws and moves gstate
+            g = self.grammar
+            hip.decode_lm_head(self.state, x, m.F("llm/final_norm"), hi, lo, self.pval, self.pidx, self.logits, **(kw | {"ids": g.union}))
+            hip.decode_grammar_finish(self.state, self.sampling, self.gstate, g.offsets, g.ids, g.next, self.logits, self.out,
+                                      m.EOS_TOKEN, logp=self.logp)
+            if logits is not None:        # (debug: the caller's copy of what the draw saw)
+                logits.copy_(self.logits)
             return
         if self.filter is not None:       # the plain head stores the logits (its partials are not read), the filter kernel draws
             hip.decode_lm_head(self.state, x, m.F("llm/final_norm"), hi, lo, self.pval, self.pidx, self.logits, **kw)

@@ -250,6 +250,7 @@ SIGNATURES: dict[str, list] = {
     "lap_decode_spec_qkv": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp],
     "lap_decode_spec_attention": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _ll, _i, _i, _i, _i, _vp],
     "lap_decode_spec_accept": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "lap_decode_grammar_finish": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
 }
 
 _fn = {}
@@ -1678,6 +1679,33 @@ def decode_filter_finish(state, sampling, filt, logits, out, eos_token, logp=Non
             raise TypeError(f"decode_filter_finish: {n} holds one entry per row")
     call("lap_decode_filter_finish", _p(state), _p(sampling), _p(filt), _p(logits), _p(out), _p(logp), B, logits.shape[1], cap,
          int(eos_token), _p(kept), _p(cut))
+
+
+def decode_grammar_finish(state, sampling, gstate, offsets, ids, nxt, logits, out, eos_token, logp=None):
+    """`decode_finish` / `decode_finish_lp` of a grammar-constrained step (lap_decode_grammar_finish): row b draws among the edges of
+    its automaton state gstate[b] (int32 [B], advanced in place) from the f32 `logits` [B, V] that the SUBSET LM head over the
+    automaton's union stored.  offsets [Q+1], ids [E], nxt [E]: the int32 device CSR of `grammar.TokenAutomaton.to_device` (checked
+    there, once: checking it here would read the device on every token).  sampling: the sampling words, or None (greedy).
+    logp (f32 [B, cap] beside out): also the token's log-probability over its state's set."""
+    _dreq(state, torch.int32, "state"); _dreq(gstate, torch.int32, "gstate"); _dreq(logits, torch.float32, "logits")
+    _dreq(out, torch.int32, "out")
+    for t, n in ((offsets, "offsets"), (ids, "ids"), (nxt, "next")):
+        _dreq(t, torch.int32, n)
+    B, cap = out.shape
+    if logits.dim() != 2 or logits.shape[0] != B or gstate.numel() != B:
+        raise TypeError(f"decode_grammar_finish: logits {tuple(logits.shape)}, gstate {tuple(gstate.shape)} for {B} rows")
+    if offsets.numel() < 2 or nxt.numel() != ids.numel() or ids.numel() < 1:
+        raise TypeError(f"decode_grammar_finish: offsets [Q+1], ids [E], next [E]; got {offsets.numel()}, {ids.numel()}, {nxt.numel()}")
+    if sampling is not None:
+        _dreq(sampling, torch.int32, "sampling")
+        if sampling.numel() < _fn["lap_decode_sampling_words"]():
+            raise TypeError("decode_grammar_finish: sampling words: int32 [4]")
+    if logp is not None:
+        _dreq(logp, torch.float32, "logp")
+        if tuple(logp.shape) != tuple(out.shape):
+            raise TypeError(f"decode_grammar_finish: logp {tuple(logp.shape)} beside out {tuple(out.shape)}")
+    call("lap_decode_grammar_finish", _p(state), _p(sampling), _p(gstate), _p(offsets), _p(ids), _p(nxt), offsets.numel() - 1,
+         ids.numel(), _p(logits), _p(out), _p(logp), B, logits.shape[1], cap, int(eos_token))
 
 
 # ---- greedy speculative decoding of one sequence (csrc/decode_spec.hip; lap_amd/speculate.py restates the rules)

@@ -346,6 +346,48 @@ def get_language_action_format(name: str) -> LanguageActionFormat:
     return LANGUAGE_ACTION_FORMAT_REGISTRY[name]
 
 
+# ------------------------------------------------------------------------------------------------ grammars
+def word_graph(format: LanguageActionFormat, *, max_cm: int = 50, max_degrees: int = 90, rotation_precision: int = 10):
+    """The word-level automaton (`grammar.WordGraph`) of what a registered format writes, for grammar-constrained decoding.
+
+    Verbose formats (`summarize_numeric_actions` with "<decimal_places>f"): clauses "move <dir> <n> cm" in the axis order x, z, y,
+    then (include_rotation) "tilt left|right", "tilt back|forward", "rotate counterclockwise|clockwise" "<n> degrees", each
+    optional, in that order, joined by ", ", and "open gripper" / "close gripper" last.  <n> of a move has `decimal_places`
+    digits and lies in (0, max_cm]; <n> of a rotation is a multiple of `rotation_precision` in (0, max_degrees] (zero clauses are
+    not written).  VLA-0 formats: exactly action_horizon * action_dim integers in [0, num_bins].  The compact style is not built."""
+    from lap_amd.grammar import WordGraph
+
+    if format.style == "vla0":
+        n = format.action_horizon * format.action_dim
+        nums = [str(i) for i in range(format.num_bins + 1)]
+        return WordGraph({i: [(w, i + 1) for w in nums] for i in range(n)}, 0, frozenset([n]))
+    if format.style != "verbose":
+        raise ValueError(f"word_graph: the {format.style!r} style has no grammar here (verbose and vla0 formats only)")
+    if max_cm < 1 or max_degrees < rotation_precision or rotation_precision < 1:
+        raise ValueError(f"word_graph: max_cm >= 1 and max_degrees >= rotation_precision >= 1, got {max_cm}, {max_degrees}, {rotation_precision}")
+    nd = format.decimal_places
+    cms = [f"{k / 10 ** nd:.{nd}f}" for k in range(1, max_cm * 10 ** nd + 1)]
+    degs = [str(d) for d in range(rotation_precision, max_degrees + 1, rotation_precision)]
+    # stage k: the k-th optional clause; (verb, (word for +, word for -), numbers, unit)
+    stages = [("move", _MOVE_WORDS[ax], cms, format.translation_unit) for ax in (0, 2, 1)]
+    if format.include_rotation:
+        stages += [("tilt", _ROT_WRITE[0], degs, "degrees"), ("tilt", _ROT_WRITE[1], degs, "degrees"), ("rotate", _ROT_WRITE[2], degs, "degrees")]
+    n = len(stages)
+    edges: dict = {}
+    for k in range(n + 1):              # ("s", k): clauses k .. n-1 and the gripper clause may follow
+        verbs: dict = {}
+        for j in range(k, n):
+            verbs.setdefault(stages[j][0], []).append(j)
+        edges[("s", k)] = [(v, ("v", v, k)) for v in verbs] + [("open", "g"), ("close", "g")]
+        for v, js in verbs.items():     # after the verb: the direction words of the clauses it can still open
+            edges[("v", v, k)] = [(name.split(" ", 1)[1], ("n", j)) for j in js for name in stages[j][1]]
+    for j, (_, _, nums, unit) in enumerate(stages):
+        edges[("n", j)] = [(w, ("u", j)) for w in nums]
+        edges[("u", j)] = [(unit + ",", ("s", j + 1))]
+    edges["g"] = [("gripper", "end")]
+    return WordGraph(edges, ("s", 0), frozenset(["end"]))
+
+
 # ------------------------------------------------------------------------------------------------ training labels
 @dataclasses.dataclass
 class ActionProcessor:

@@ -693,7 +693,8 @@ class LAP:
 
     def sample_tokens(self, rng, observation, *, max_decoding_steps: int = 390, temperature: float = 0.0, collect=None,
                       decode: str = "eager", sampler: str = "host", decode_weights: str = "bf16", allowed_tokens=None,
-                      return_logprobs: bool = False, num_samples=None, top_k=None, top_p=None, speculate=None, draft_tokens=None):
+                      return_logprobs: bool = False, num_samples=None, top_k=None, top_p=None, speculate=None, draft_tokens=None,
+                      grammar=None):
         """lap.py:678-766 (LAP_AR serving mode): VLM-only prefill, then single-token decode until every sample has emitted
         EOS or `max_decoding_steps` tokens; returns int32 [B, max_decoding_steps] (zeros after the stop).
 
@@ -776,12 +777,27 @@ class LAP:
         (`speculate.accept`).  Every row of the fused kernels is accumulated independently of the batch width, so the returned
         tokens are those of the call without `speculate`, whatever the draft; only the number of passes over the weights changes
         (`last_spec_stats` = (verify steps, drafts accepted) of the request).  Composes with decode_weights and allowed_tokens.
-        The reference has no such option."""
+        The reference has no such option.
+
+        grammar: grammar-constrained decoding.  None (default): as before.  A `grammar.TokenAutomaton` (or its `to_device` form),
+        a deterministic automaton over token ids built for this model's vocabulary and EOS token
+        (`policy_io.grammar_automaton` builds one from a language-action format and the tokenizer): every row starts in state 0,
+        token t of row b is drawn among the ids its state allows, by the rule of `allowed_tokens` on that state's set (the
+        argmax of the unconstrained score, lowest index among ties; under sampler="device" the noise of index j stays that of j),
+        and the row moves along the edge of its token, so an answer that ends before its budget is a sentence of the format.  After
+        its EOS a row stays in a sink state and keeps emitting EOS.  decode="fused" keeps the state of every row on the device:
+        the SUBSET LM head streams the union of all edges and stores its f32 logits, lap_decode_grammar_finish draws from the
+        state's segment and moves the state (rows of a best-of-N batch diverge); decode="eager" masks its stored logits per row and
+        steps with a `torch.searchsorted`.  `grammar.decode_reference` restates the draw on `collect`ed logits.  With
+        return_logprobs / num_samples a log-probability is the one over the state's set.  Composes with temperature > 0 under
+        sampler="device", return_logprobs, num_samples and decode_weights; allowed_tokens, top_k / top_p, speculate and the host
+        sampler at temperature > 0 raise ValueError, as does an automaton built for another vocabulary size or EOS token.  The
+        reference has no such option."""
         from lap_amd import ar_decode       # (it imports this module)
         return ar_decode.sample_tokens(self, rng, observation, max_decoding_steps=max_decoding_steps, temperature=temperature,
                                        collect=collect, decode=decode, sampler=sampler, decode_weights=decode_weights,
                                        allowed_tokens=allowed_tokens, return_logprobs=return_logprobs, num_samples=num_samples,
-                                       top_k=top_k, top_p=top_p, speculate=speculate, draft_tokens=draft_tokens)
+                                       top_k=top_k, top_p=top_p, speculate=speculate, draft_tokens=draft_tokens, grammar=grammar)
 
     DECODE_WEIGHTS = ("bf16", "fp8", "fp8_layers")
     last_spec_stats = None      # (verify steps, drafts accepted) of the last `sample_tokens(speculate=S)` request

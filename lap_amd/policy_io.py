@@ -554,6 +554,28 @@ def allowed_token_ids(tokenizer: PaligemmaTokenizer, texts, extra_ids=()) -> np.
     return np.asarray(sorted(ids), dtype=np.int32)
 
 
+def grammar_automaton(tokenizer: PaligemmaTokenizer, format, *, vocab_size: int | None = None, check_sentences: int = 8, **limits):
+    """The token automaton (`grammar.TokenAutomaton`) of a language-action format under `tokenizer`, for
+    `LAP.sample_tokens(grammar=...)`: `lang_actions.word_graph(format, **limits)` (limits: max_cm, max_degrees,
+    rotation_precision) with every word encoded on its own, as `tokenize` encodes a language action.  format: a
+    LanguageActionFormat or a registered name.  vocab_size: the model's (default: the tokenizer's).
+    The construction rests on the tokenizer never merging across whitespace; that is checked here: `check_sentences` random
+    sentences of the format, encoded whole, must be accepted (ValueError otherwise)."""
+    from lap_amd import grammar, lang_actions
+
+    if isinstance(format, str):
+        format = lang_actions.get_language_action_format(format)
+    sp = tokenizer._tokenizer
+    graph = lang_actions.word_graph(format, **limits)
+    encode = lambda text: sp.encode(text, add_bos=False, add_eos=False)
+    auto = grammar.automaton_from_words(encode, graph, int(sp.eos_id()), int(vocab_size or sp.vocab_size()))
+    for text in grammar.random_sentences(graph, check_sentences, seed=0):
+        if not auto.accepts(list(encode(text)) + [auto.eos_token]):
+            raise ValueError(f"grammar_automaton: the tokenizer encodes {text!r} differently from its words one by one (it merges "
+                             "across whitespace?): the word-level construction does not hold for it")
+    return auto
+
+
 @dataclasses.dataclass(frozen=True)
 class TokenizePromptAndReasoning:
     """transforms.py:27-113: consumes prompt / language_actions / dataset_name / frame_description / time horizon, adds the

@@ -124,11 +124,20 @@ class GraphedTokenDecoder:
     `sample_tokens`' exact speculative decoding.  The step graph is captured on verify steps of S rows, and the reference sequence
     lives in one device buffer that `__call__(obs, draft_tokens=ids_or_None)` rewrites before the first replay, so one step graph
     serves any draft.  A call returns the tokens of the decoder without it; `last_stats` = (verify_steps, accepted) of the call.
-    Composes with weights= and allowed_tokens=."""
+    Composes with weights= and allowed_tokens=.
+
+    grammar: `sample_tokens`' grammar-constrained decoding, a `grammar.TokenAutomaton` fixed at construction (the graphs hold the
+    addresses of its device buffers).  The automaton state of every row lives in the context and is zeroed inside the prefill graph,
+    so one capture serves every request and every request starts in state 0.  Composes with sampling=, weights=, logprobs= and
+    num_samples=; allowed_tokens=, filtering= and speculate= raise ValueError."""
 
     def __init__(self, model: LAP, batch_size: int = 1, max_decoding_steps: int = 390, prompt_len: int | None = None,
                  steps_per_replay: int = 8, sampling: bool = False, weights: str = "bf16", allowed_tokens=None,
-                 logprobs: bool = False, num_samples=None, filtering: bool = False, speculate=None):
+                 logprobs: bool = False, num_samples=None, filtering: bool = False, speculate=None, grammar=None):
+        self.grammar = None
+        if grammar is not None:
+            self.grammar = ar_decode.device_grammar(model, grammar, allowed_tokens=allowed_tokens, top_k=0 if filtering else None,
+                                                    speculate=speculate)
         self.S = None
         self.last_stats = None
         if speculate is not None:
@@ -183,7 +192,8 @@ class GraphedTokenDecoder:
             pre = ar_decode.replicate_prefill(pre, self.N)
         if self.ctx is None:
             self.ctx = ar_decode.DecodeCtx(self.model, pre.B, pre.Pn, self.max_steps, self.sampling, self.weights,
-                                           allowed=self.allowed, logprobs=self.logprobs, filtering=self.filtering, speculate=self.S)
+                                           allowed=self.allowed, logprobs=self.logprobs, filtering=self.filtering, speculate=self.S,
+                                           grammar=self.grammar)
         self.ctx.first_token(pre)
 
     def _steps(self):
@@ -393,6 +403,13 @@ class ARPolicy:
         if weights != "bf16":
             if self._sample_kwargs.setdefault("decode", "fused") != "fused":
                 raise ValueError(f"ARPolicy: decode_weights={weights!r} needs decode=\"fused\", got {self._sample_kwargs['decode']!r}")
+        # sample_kwargs["grammar"] (grammar-constrained decoding: a grammar.TokenAutomaton) reaches both routes: it is checked and
+        # put on the device once, here; the decoder is captured with it and sample_tokens gets the device form on every call
+        if self._sample_kwargs.get("grammar") is not None:
+            kw = self._sample_kwargs
+            self._sample_kwargs["grammar"] = ar_decode.device_grammar(
+                base.model, kw["grammar"], allowed_tokens=kw.get("allowed_tokens"), top_k=kw.get("top_k"), top_p=kw.get("top_p"),
+                speculate=kw.get("speculate"), sampler=kw.get("sampler", "host"), temperature=kw.get("temperature", 0.0))
         # sample_kwargs["allowed_tokens"] (constrained decoding) reaches both routes as well: the set is checked and put on the
         # device once, here; the decoder is captured with it and sample_tokens gets the checked set on every call
         if self._sample_kwargs.get("allowed_tokens") is not None:
@@ -433,7 +450,8 @@ class ARPolicy:
                                                 sampling=self._device_sampler and self._speculate is None, weights=weights,
                                                 allowed_tokens=self._sample_kwargs.get("allowed_tokens"),
                                                 logprobs=self._logprobs, num_samples=self._num_samples,
-                                                filtering=bool(self._filter) and self._device_sampler, speculate=self._speculate)
+                                                filtering=bool(self._filter) and self._device_sampler, speculate=self._speculate,
+                                                grammar=self._sample_kwargs.get("grammar"))
 
     def __getattr__(self, name):
         return getattr(self._base, name)
@@ -499,7 +517,7 @@ class ARPolicy:
 
 
 def create_trained_policy_ar(*args, sample_kwargs: dict | None = None, language_action_format="verbose_eef_with_rotation",
-                             ar_graph: bool = False, **kwargs) -> ARPolicy:
+                             ar_graph: bool = False, grammar: bool = False, grammar_limits: dict | None = None, **kwargs) -> ARPolicy:
     """policy_config_adapter.py:157-160 with the AR output stack [DetokenizeReasoning, CoTOutputs(language_action_format)]:
     generated ids -> text -> [dx, dy, dz, droll, dpitch, dyaw, gripper] (the language action describes the whole chunk as
     one delta, output_transforms.py:75-104; `Unnormalize` has no `actions` statistics to apply to such deltas and is left out
@@ -519,10 +537,17 @@ def create_trained_policy_ar(*args, sample_kwargs: dict | None = None, language_
     sample_kwargs={"speculate": S} (2 <= S <= 8, greedy; implies decode="fused") decodes every request on verify steps of S rows
     with the previous request's answer as the draft (`LAP.sample_tokens`): the tokens are unchanged, and "policy_timing" gains
     "spec_steps" and "spec_accepted".  These keys are added to what the output stack
-    returns ({"actions", "reasoning"}), so a client of this policy and of the websocket server receives them."""
+    returns ({"actions", "reasoning"}), so a client of this policy and of the websocket server receives them.
+    grammar=True: every answer is constrained to the grammar of `language_action_format` (`policy_io.grammar_automaton` under the
+    policy's tokenizer, for the model's vocabulary; sample_kwargs["grammar"] may instead hold an automaton of one's own), so a
+    sampled answer (best-of-N, temperature > 0) always parses; grammar_limits: the keywords of `lang_actions.word_graph`."""
     from lap_amd import policy_io as pio
 
     base = create_trained_policy(*args, use_graph=False, **kwargs)
     tok = next(t.tokenizer for t in base._transforms if isinstance(t, pio.TokenizePromptAndReasoning))
+    if grammar:
+        sample_kwargs = dict(sample_kwargs or {})
+        sample_kwargs["grammar"] = pio.grammar_automaton(tok, language_action_format, vocab_size=base.model.config.vocab_size,
+                                                         **(grammar_limits or {}))
     base._output_transform = pio.compose([pio.DetokenizeReasoning(tok), pio.CoTOutputs(language_action_format=language_action_format)])
     return ARPolicy(base, sample_kwargs=sample_kwargs, use_graph=ar_graph)

@@ -4,7 +4,7 @@ rate against the 6.29 TB/s measured copy rate.  Random weights, the reference pr
 run decodes N tokens.  One JSON line.
 
     python tools/bench_ar.py [--tokens 64] [--config lap_bench] [--kwaves 4] [--temperature T] [--weights bf16 fp8 fp8_layers]
-                             [--allowed N] [--logprobs] [--num-samples N] [--speculate S [S ...]]
+                             [--allowed N] [--logprobs] [--num-samples N] [--speculate S [S ...]] [--grammar verbose]
 
 --temperature T > 0 adds the sampled figures: the eager loop with the torch-generator noise (sampler="host"), the eager loop and
 the fused steps with the device noise (sampler="device"), and a GraphedTokenDecoder(sampling=True) called sampled and greedy.
@@ -31,6 +31,14 @@ the plain graph of those weights: a GraphedTokenDecoder(speculate=S) called with
 and without a draft (zero acceptance, the price of a wrong guess), each as the mean and [min, max] of the timed repeats; ms per
 verify step, ms per token, whether the tokens equal the plain graph's, and the break-even the two imply: the mean tokens per
 verify step, and the share of the S - 1 drafts that must be accepted, at which a speculating decode costs what the plain one does.
+--grammar verbose adds grammar-constrained decoding (`grammar=`) with the automaton of the verbose-with-rotation format, graphed at
+B = 1: ms per token with the automaton and ms per token of `allowed_tokens=` over the same union set, from this process (the two
+decoders take turns; each figure is the mean and [min, max] of at least seven timed repeats), Q, E and the size of the union, and
+the time per launch of what differs between the two steps (the SUBSET head without and with the logits store, lap_decode_finish
+and lap_decode_grammar_finish, each from a captured graph of back-to-back launches).  No tokenizer model is needed: a word is encoded as a
+head piece and single-character pieces with ids in order of first use, which gives the automaton the shape a real tokenizer gives
+it.  The automaton needs a real EOS id (the model's is set to 1 for this part), so after "gripper" the sentence may start again and a
+row ends only when it draws EOS there; the grammar figure is per token actually decoded, which the result reports.
 """
 import argparse
 import json
@@ -61,6 +69,7 @@ ap.add_argument("--num-samples", type=int, default=0, help="N > 0: also measure 
                 "sampled at --temperature, or at 1.0 when that is 0")
 ap.add_argument("--top-k", type=int, default=0, help="with --temperature: also measure filtered sampled decoding (top_k)")
 ap.add_argument("--top-p", type=float, default=1.0, help="with --temperature: also measure filtered sampled decoding (top_p)")
+ap.add_argument("--grammar", choices=["verbose"], default=None, help="also measure grammar-constrained decoding (verbose-with-rotation)")
 ap.add_argument("--speculate", type=int, nargs="+", default=[], help="also measure exact speculative decoding at these verify-step widths")
 a = ap.parse_args()
 hip.DECODE_KWAVES_DOWN = a.kwaves
@@ -264,6 +273,74 @@ if a.speculate:
                 "break_even_draft_acceptance_rate": round((step_ms / plain_ms - 1) / (S - 1), 3),
                 "tokens_equal_plain_graph": bool(torch.equal(full_tok, answer) and torch.equal(zero_tok, answer))}
         speculative[wname] = rows
+grammar_res = {}
+if a.grammar:
+    from lap_amd import grammar as G, lang_actions as LA
+
+    pieces = {}
+    encode = lambda w: [pieces.setdefault(p, 2 + len(pieces)) for p in ["\u2581" + w[0], *w[1:]]]
+    wg = LA.word_graph(LA.VERBOSE_WITH_ROTATION_FORMAT)
+    wg = G.WordGraph(wg.edges | {"end": wg.edges[wg.start]}, wg.start, wg.accepting)        # after "gripper": EOS, or the next sentence
+    model.EOS_TOKEN = 1
+    auto = G.automaton_from_words(encode, wg, 1, cfg.vocab_size)
+
+    gdec = GraphedTokenDecoder(model, 1, N, grammar=auto).capture()
+    adec = GraphedTokenDecoder(model, 1, N, allowed_tokens=auto.union()).capture()
+    pre = {d: timeit(lambda d=d: (d.g_prefill.replay()), a.reps) for d in (gdec, adec)}
+    runs = {gdec: [], adec: []}
+    for _ in range(max(a.reps, 7)):         # the two decoders take turns, so that a drift of the machine reaches both
+        for d in (gdec, adec):
+            t = timeit(lambda: d(o), 1)
+            runs[d].append((t - pre[d]) / max(int(d.ctx.state[0]) - 1, 1))
+    res = lambda d: (round(sum(runs[d]) / len(runs[d]), 3), [round(min(runs[d]), 3), round(max(runs[d]), 3)], int(d.ctx.state[0]))
+    g_res, a_res = res(gdec), res(adec)
+    gtok = gdec(o)
+
+    # the two launches a grammar step has in place of the allowed step's: the SUBSET head with and without the logits store, and
+    # the two finishes, each as a captured graph of n launches on the grammar context's buffers (EOS disabled in these launches)
+    ctx, dg, n_l = gdec.ctx, gdec.grammar, min(56, N - 2)
+
+    def launches(fn):
+        with model._serving_weights():
+            side = torch.cuda.Stream(device=dev)
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                fn()
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                for _ in range(n_l):
+                    fn()
+        us = []
+        for _ in range(6):
+            ctx.state[:3] = torch.tensor([1, 0, 0], dtype=torch.int32, device=dev)
+            ctx.gstate.zero_()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            g.replay()
+            e1.record()
+            torch.cuda.synchronize()
+            us.append(e0.elapsed_time(e1) / n_l * 1e3)
+        return round(sum(us[1:]) / 5, 2)
+
+    gamma, hi, lo = model.F("llm/final_norm"), model.W("llm/embed"), model.ps.w16lo("llm/embed")
+    head = lambda lg: (lambda: hip.decode_lm_head(ctx.state, ctx.x, gamma, hi, lo, ctx.pval, ctx.pidx, lg, ids=dg.union))
+    launch_us = {
+        "subset_head_us": launches(head(None)), "subset_head_with_logits_store_us": launches(head(ctx.logits)),
+        "finish_us": launches(lambda: hip.decode_finish(ctx.state, ctx.pval, ctx.pidx, ctx.out, -1)),
+        "grammar_finish_us": launches(lambda: hip.decode_grammar_finish(ctx.state, None, ctx.gstate, dg.offsets, dg.ids, dg.next,
+                                                                        ctx.logits, ctx.out, -1)),
+        "launches_per_graph": n_l}
+    model.EOS_TOKEN = -1
+    grammar_res = {"grammar": {
+        "format": "verbose_with_rotation", "Q": auto.num_states, "E": auto.num_edges, "union": int(auto.union().shape[0]),
+        "grammar_graphed_ms_per_token": g_res[0], "grammar_graphed_ms_per_token_min_max": g_res[1], "grammar_tokens_decoded": g_res[2],
+        "allowed_union_graphed_ms_per_token": a_res[0], "allowed_union_graphed_ms_per_token_min_max": a_res[1],
+        "allowed_union_tokens_decoded": a_res[2], "plain_graphed_ms_per_token": round(g_ms, 3),
+        "grammar_row_is_accepted_or_cut_by_the_budget": bool(auto.accepts(gtok[0].cpu().numpy()) or int((gtok[0] == 1).sum()) == 0),
+        "launch_us": launch_us}}
 print(json.dumps({
     "metric": "batch-1 LAP_AR decode LAP-3B bf16 (ms per token after the prefill, greedy, EOS disabled)",
     "tokens": N, "prompt_len": cfg.max_token_len,
@@ -274,4 +351,4 @@ print(json.dumps({
     "algorithmic_bytes_per_token": bytes_tok, "floor_ms_per_token_at_6.29TBps": round(bytes_tok / 6.29e12 * 1e3, 3),
     "achieved_GBps_graphed": round(bytes_tok / (g_ms * 1e-3) / 1e9, 1),
     "share_of_6.29TBps": round(bytes_tok / (g_ms * 1e-3) / 6.29e12, 3), "down_proj_kwaves": a.kwaves} | sampled | ({"weights": quant} if quant else {})
-    | ({"allowed": a.allowed, "constrained": constrained} if constrained else {}) | logprobs | best_of | ({"speculate": speculative} if speculative else {})))
+    | ({"allowed": a.allowed, "constrained": constrained} if constrained else {}) | logprobs | best_of | ({"speculate": speculative} if speculative else {}) | grammar_res))
