@@ -15,7 +15,7 @@ from lap_amd.joint_layers import llm_fwd
 from lap_amd.loss import lm_logits
 from lap_amd.model import LAP, _gen
 from lap_amd.observation import preprocess_observation
-from lap_amd.speculate import check_speculate
+from lap_amd.speculate import check_jump_forward, check_speculate
 
 DECODE_STEPS_PER_CHECK = 8      # fused steps between two host reads of the device stop flag (eager `decode="fused"`)
 
@@ -167,7 +167,7 @@ def device_grammar(model: LAP, grammar, **combined):
 def sample_tokens(model: LAP, rng, observation, *, max_decoding_steps: int = 390, temperature: float = 0.0, collect=None,
                   decode: str = "eager", sampler: str = "host", decode_weights: str = "bf16", allowed_tokens=None,
                   return_logprobs: bool = False, num_samples=None, top_k=None, top_p=None, speculate=None, draft_tokens=None,
-                  grammar=None):
+                  grammar=None, jump_forward=None):
     """`LAP.sample_tokens` (documented there): every argument is checked before any device work."""
     if decode not in ("eager", "fused"):
         raise ValueError(f"sample_tokens: decode must be 'eager' or 'fused', got {decode!r}")
@@ -179,8 +179,12 @@ def sample_tokens(model: LAP, rng, observation, *, max_decoding_steps: int = 390
     if speculate is not None:
         S = check_speculate(speculate, observation.tokenized_prompt.shape[0], decode=decode, temperature=temperature,
                             return_logprobs=return_logprobs, num_samples=num_samples, top_k=top_k, top_p=top_p, collect=collect)
-    elif draft_tokens is not None:
+    elif draft_tokens is not None and jump_forward is None:
         raise ValueError("sample_tokens: draft_tokens needs speculate=S")
+    J = None
+    if jump_forward is not None:
+        J = check_jump_forward(jump_forward, observation.tokenized_prompt.shape[0], grammar=grammar, decode=decode, sampler=sampler,
+                               temperature=temperature, num_samples=num_samples, collect=collect)
     check_decode_weights(decode_weights)
     if decode_weights != "bf16" and decode != "fused":
         raise ValueError(f"sample_tokens: decode_weights={decode_weights!r} runs on the fused decode kernels only: pass decode=\"fused\"")
@@ -204,7 +208,7 @@ def sample_tokens(model: LAP, rng, observation, *, max_decoding_steps: int = 390
             return _sample_fused(model, observation, max_decoding_steps=max_decoding_steps, collect=collect,
                                  sampling=(rng, temperature) if sampler == "device" else None, weights=decode_weights,
                                  allowed=allowed, logprobs=return_logprobs or N is not None, num_samples=N, filt=filt,
-                                 speculate=S, draft=draft_tokens, grammar=grammar)
+                                 speculate=S, draft=draft_tokens, grammar=grammar, jump=J)
         if decode_weights != "bf16":
             raise ValueError("sample_tokens: decode_weights other than 'bf16' with temperature > 0 needs sampler='device' (the "
                              "host sampler keeps the eager loop)")
@@ -381,8 +385,9 @@ def _sample_eager(model: LAP, rng, observation, *, max_decoding_steps: int, temp
 
 # ---- the fused step: single-token kernels, state on the device (csrc/decode.hip)
 def _sample_fused(model: LAP, observation, *, max_decoding_steps: int, collect=None, sampling=None, weights: str = "bf16",
-                  allowed=None, logprobs: bool = False, num_samples=None, filt=None, speculate=None, draft=None, grammar=None):
-    """grammar: None, or a DeviceAutomaton: a grammar context.
+                  allowed=None, logprobs: bool = False, num_samples=None, filt=None, speculate=None, draft=None, grammar=None, jump=None):
+    """grammar: None, or a DeviceAutomaton: a grammar context.  jump: None, or the rows S of a jump-forward step of that context
+    (`check_jump_forward`), with `draft` as the reference sequence and `model.last_spec_stats` as under speculate.
     sampling: None (the greedy LM head) or (seed, temperature) for the sampling LM head.  weights: `decode_weights`.
     filt: None, or (top_k, top_p): a filtering context (it needs `sampling`).
     allowed: None or the int32 device ids of `check_allowed_tokens`.  logprobs: the context keeps the token log-probabilities
@@ -393,8 +398,8 @@ def _sample_fused(model: LAP, observation, *, max_decoding_steps: int, collect=N
     if num_samples is not None:
         pre = replicate_prefill(pre, num_samples)
     ctx = DecodeCtx(model, pre.B, pre.Pn, max_decoding_steps, sampling is not None, weights, allowed=allowed, logprobs=logprobs,
-                    filtering=filt is not None, speculate=speculate, grammar=grammar)
-    if speculate is not None:
+                    filtering=filt is not None, speculate=speculate, grammar=grammar, jump_forward=jump)
+    if speculate is not None or jump is not None:
         ctx.set_draft(draft)
     if sampling is not None:
         ctx.set_sampling(*sampling)
@@ -418,7 +423,7 @@ def _sample_fused(model: LAP, observation, *, max_decoding_steps: int, collect=N
             break
         for _ in range(n):
             ctx.step()
-    if speculate is not None:
+    if speculate is not None or jump is not None:
         model.last_spec_stats = ctx.stats()
     return (ctx.out, ctx.logp) if logprobs else ctx.out
 
@@ -440,11 +445,21 @@ class DecodeCtx:
     the automaton state that row is in (lap_amd/grammar.py).  It owns `gstate` (int32 [B], zeroed by `first_token` with a device
     op that a captured prefill replays) and a [B, V] f32 logits buffer, written to -inf once; its LM head is the plain SUBSET head
     (bf16 or fp8) over the automaton's union, which stores its logits there, and lap_decode_grammar_finish draws from them, moves
-    `gstate` and does the finish's bookkeeping, with the log-probability over the state's set when logprobs is on."""
+    `gstate` and does the finish's bookkeeping, with the log-probability over the state's set when logprobs is on.
+    jump_forward=S (2 <= S <= 8; needs grammar, B = 1; with or without sampling and logprobs): the grammar context decodes ONE
+    sequence on steps of S rows, in the arrangement of speculate=S (state, `out`, `logp`, `gstate` and the generated cache of
+    B = 1; activations, attention scratch, LM partials and the logits buffer of S rows).  `step` drafts from the reference
+    (`set_draft`), overwrites the drafts with the grammar's (lap_decode_grammar_draft: a state with one edge forces its token), runs
+    the layers on the S positions, the plain SUBSET head over the union on the S rows, and lap_decode_grammar_spec_finish, which
+    draws the rows in sequence with the single-row finish's bits and accepts the longest verified run.  Tokens and
+    log-probabilities are those of the grammar context without it; `stats` reads the counters."""
 
     def __init__(self, model: LAP, B: int, Pn: int, cap: int, sampling: bool = False, weights: str = "bf16", allowed=None,
-                 logprobs: bool = False, filtering: bool = False, speculate=None, grammar=None):
+                 logprobs: bool = False, filtering: bool = False, speculate=None, grammar=None, jump_forward=None):
         check_decode_weights(weights)
+        self.J = None
+        if jump_forward is not None:
+            self.J = check_jump_forward(jump_forward, B, grammar=grammar)
         if grammar is not None:
             check_grammar(grammar, model.config.vocab_size, model.EOS_TOKEN, allowed_tokens=allowed, top_k=0 if filtering else None,
                           speculate=speculate)
@@ -454,7 +469,7 @@ class DecodeCtx:
         self.S = None
         if speculate is not None:
             self.S = check_speculate(speculate, B, return_logprobs=logprobs, temperature=1.0 if sampling else 0.0)
-        R = self.S or B                 # rows of a step's activations
+        R = self.S or self.J or B       # rows of a step's activations
         if filtering and not sampling:
             raise ValueError("DecodeCtx: filtering needs sampling=True (the filters are part of the device sampler)")
         if allowed is not None and (allowed.dtype != torch.int32 or not allowed.is_cuda or allowed.dim() != 1):
@@ -478,8 +493,8 @@ class DecodeCtx:
         self.attn_scratch = hip.decode_attn_scratch(R, Pn, cap, dev)
         self.pval, self.pidx = hip.decode_lm_partials(R, dev)
         # speculate: the reference sequence {length, ids[cap]} and the S - 1 drafted tokens of the step
-        self.ref = hip.decode_spec_ref(cap, dev) if self.S else None
-        self.draft = torch.full((self.S - 1,), -1, dtype=torch.int32, device=dev) if self.S else None
+        self.ref = hip.decode_spec_ref(cap, dev) if R != B else None
+        self.draft = torch.full((R - 1,), -1, dtype=torch.int32, device=dev) if R != B else None
         # the sampling words {seed low, seed high, bits of 1 / temperature, 0} of the sampling LM head (zeros: greedy); None:
         # the context decodes on the greedy LM head
         self.sampling = hip.decode_sampling(dev) if sampling else None
@@ -500,7 +515,7 @@ class DecodeCtx:
         self.gstate = None
         if grammar is not None:
             self.gstate = torch.zeros((B,), dtype=torch.int32, device=dev)
-            self.logits = torch.full((B, model.config.vocab_size), float("-inf"), dtype=torch.float32, device=dev)
+            self.logits = torch.full((R, model.config.vocab_size), float("-inf"), dtype=torch.float32, device=dev)
         self.prefix = None
         self.kinfo = None
 
@@ -514,13 +529,13 @@ class DecodeCtx:
         """The reference sequence the next decode drafts from (any integer sequence, truncated to `cap`; None: no draft, every
         verify step then emits one token): a host-to-device copy; captured graphs keep the buffer's address."""
         if self.ref is None:
-            raise ValueError("this decode context was built without speculate")
+            raise ValueError("this decode context was built without speculate or jump_forward")
         hip.decode_set_spec_ref(self.ref, ids)
 
     def stats(self):
         """(verify_steps, accepted) of the decode so far: two words of the device state (a host read)."""
-        if self.S is None:
-            raise ValueError("this decode context was built without speculate")
+        if self.ref is None:
+            raise ValueError("this decode context was built without speculate or jump_forward")
         a, b = self.state[24:26].tolist()
         return int(a), int(b)
 
@@ -566,17 +581,24 @@ class DecodeCtx:
             hi, lo, kw = m.W("llm/embed"), m.ps.w16lo("llm/embed"), {}
         if self.allowed is not None:      # the LM head streams the allowed rows only
             kw["ids"] = self.allowed
+        if verify and self.J:             # the plain head over the union stores the S rows of logits, the finish draws them in sequence
+            g = self.grammar
+            hip.decode_lm_head(self.state, x, m.F("llm/final_norm"), hi, lo, self.pval, self.pidx, self.logits, **(kw | {"ids": g.union}))
+            hip.decode_grammar_spec_finish(self.state, self.sampling, self.gstate, g.offsets, g.ids, g.next, self.logits, self.draft,
+                                           self.out, m.EOS_TOKEN, logp=self.logp)
+            return
         if verify:
             hip.decode_lm_head(self.state, x, m.F("llm/final_norm"), hi, lo, self.pval, self.pidx, None, **kw)
             hip.decode_spec_accept(self.state, self.pval, self.pidx, self.draft, self.out, m.EOS_TOKEN)
             return
         if self.grammar is not None:      # the plain head over the union stores the logits, the grammar kernel draws and moves gstate
             g = self.grammar
-            hip.decode_lm_head(self.state, x, m.F("llm/final_norm"), hi, lo, self.pval, self.pidx, self.logits, **(kw | {"ids": g.union}))
-            hip.decode_grammar_finish(self.state, self.sampling, self.gstate, g.offsets, g.ids, g.next, self.logits, self.out,
+            lg = self.logits[:self.B]     # (a jump-forward context: row 0 of its S rows)
+            hip.decode_lm_head(self.state, x, m.F("llm/final_norm"), hi, lo, self.pval, self.pidx, lg, **(kw | {"ids": g.union}))
+            hip.decode_grammar_finish(self.state, self.sampling, self.gstate, g.offsets, g.ids, g.next, lg, self.out,
                                       m.EOS_TOKEN, logp=self.logp)
             if logits is not None:        # (debug: the caller's copy of what the draw saw)
-                logits.copy_(self.logits)
+                logits.copy_(lg)
             return
         if self.filter is not None:       # the plain head stores the logits (its partials are not read), the filter kernel draws
             hip.decode_lm_head(self.state, x, m.F("llm/final_norm"), hi, lo, self.pval, self.pidx, self.logits, **kw)
@@ -600,8 +622,13 @@ class DecodeCtx:
         v = m.v
         NH, HD, KV = v.num_heads, v.head_dim, v.num_kv_heads
         rows, lo, hi = m.ps.embed_rows()
-        if self.S:
+        rows_of_one = bool(self.S or self.J)        # the rows are S positions of one sequence
+        if rows_of_one:
             hip.decode_spec_draft(self.state, self.ref, self.out, self.draft)
+            if self.J:
+                g = self.grammar
+                hip.decode_grammar_draft(self.state, self.gstate, g.offsets, g.ids, g.next, self.draft, self.out, m.config.vocab_size,
+                                         m.EOS_TOKEN)
             hip.decode_spec_embed(self.state, rows, lo, hi, self.out, self.draft, self.x, math.sqrt(v.width))
         else:
             hip.decode_embed(self.state, rows, lo, hi, self.out, self.x, math.sqrt(v.width))
@@ -610,7 +637,7 @@ class DecodeCtx:
             gk, gv = self.gen[l, 0], self.gen[l, 1]
             w, kw = self._w(p + "wqkv0")
             ck, cv = self.prefix[l]
-            if self.S:
+            if rows_of_one:
                 hip.decode_spec_qkv(self.state, self.x, m.F(p + "n_attn"), w, self.q, gk, gv, NH, HD, HD ** -0.5, **kw)
                 hip.decode_spec_attention(self.state, self.q, ck, cv, self.kinfo, self.Pn, gk, gv, self.o, self.attn_scratch, NH, KV, HD)
             else:
@@ -622,4 +649,4 @@ class DecodeCtx:
             hip.decode_gate_up(self.state, self.xa, m.F(p + "n_ffw"), w, self.act, **kw)
             w, kw = self._w(p + "wd0")
             hip.decode_proj_residual(self.state, self.act, w, self.xa, self.x, kwaves=hip.DECODE_KWAVES_DOWN, **kw)
-        self._token(self.x, logits, verify=bool(self.S))
+        self._token(self.x, logits, verify=rows_of_one)

@@ -251,6 +251,8 @@ SIGNATURES: dict[str, list] = {
     "lap_decode_spec_attention": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _ll, _i, _i, _i, _i, _vp],
     "lap_decode_spec_accept": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "lap_decode_grammar_finish": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "lap_decode_grammar_draft": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp],
+    "lap_decode_grammar_spec_finish": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
 }
 
 _fn = {}
@@ -1706,6 +1708,50 @@ def decode_grammar_finish(state, sampling, gstate, offsets, ids, nxt, logits, ou
             raise TypeError(f"decode_grammar_finish: logp {tuple(logp.shape)} beside out {tuple(out.shape)}")
     call("lap_decode_grammar_finish", _p(state), _p(sampling), _p(gstate), _p(offsets), _p(ids), _p(nxt), offsets.numel() - 1,
          ids.numel(), _p(logits), _p(out), _p(logp), B, logits.shape[1], cap, int(eos_token))
+
+
+def _automaton_req(fn, offsets, ids, nxt):
+    for t, n in ((offsets, "offsets"), (ids, "ids"), (nxt, "next")):
+        _dreq(t, torch.int32, n)
+    if offsets.numel() < 2 or nxt.numel() != ids.numel() or ids.numel() < 1:
+        raise TypeError(f"{fn}: offsets [Q+1], ids [E], next [E]; got {offsets.numel()}, {ids.numel()}, {nxt.numel()}")
+
+
+def decode_grammar_draft(state, gstate, offsets, ids, nxt, draft, out, V, eos_token):
+    """The drafts of a jump-forward step (lap_decode_grammar_draft; `speculate.grammar_drafts`), over the raw reference drafts that
+    `decode_spec_draft` left in draft [S - 1]: from the state gstate[0], a state with a single edge drafts that id, any other keeps
+    the reference's draft when it is one of its edges, and the first position with neither ends the run (-1 from there on).
+    out: the [1, cap] token output of the one sequence (its cap bounds t, as in `decode_spec_draft`)."""
+    cap = _spec_out(out)
+    _dreq(state, torch.int32, "state"); _dreq(gstate, torch.int32, "gstate"); _dreq(draft, torch.int32, "draft")
+    _automaton_req("decode_grammar_draft", offsets, ids, nxt)
+    if gstate.numel() != 1:
+        raise TypeError(f"decode_grammar_draft: gstate of one sequence, got {tuple(gstate.shape)}")
+    call("lap_decode_grammar_draft", _p(state), _p(gstate), _p(offsets), _p(ids), _p(nxt), offsets.numel() - 1, ids.numel(), int(V),
+         cap, int(eos_token), _p(draft), draft.numel() + 1)
+
+
+def decode_grammar_spec_finish(state, sampling, gstate, offsets, ids, nxt, logits, draft, out, eos_token, logp=None):
+    """The finish of a jump-forward step (lap_decode_grammar_spec_finish; `speculate.grammar_verify`): the S = draft.numel() + 1 rows
+    of f32 `logits` [S, V] are drawn in sequence, row r from the state the rows before it led to, at step t + r, each with the bits
+    of `decode_grammar_finish` at B = 1; then the accept rule of `decode_spec_accept`.  out / logp: [1, cap]."""
+    cap = _spec_out(out)
+    _dreq(state, torch.int32, "state"); _dreq(gstate, torch.int32, "gstate"); _dreq(logits, torch.float32, "logits")
+    _dreq(draft, torch.int32, "draft")
+    _automaton_req("decode_grammar_spec_finish", offsets, ids, nxt)
+    S = draft.numel() + 1
+    if logits.dim() != 2 or logits.shape[0] != S or gstate.numel() != 1:
+        raise TypeError(f"decode_grammar_spec_finish: logits {tuple(logits.shape)}, gstate {tuple(gstate.shape)} for {S} rows of one sequence")
+    if sampling is not None:
+        _dreq(sampling, torch.int32, "sampling")
+        if sampling.numel() < _fn["lap_decode_sampling_words"]():
+            raise TypeError("decode_grammar_spec_finish: sampling words: int32 [4]")
+    if logp is not None:
+        _dreq(logp, torch.float32, "logp")
+        if tuple(logp.shape) != tuple(out.shape):
+            raise TypeError(f"decode_grammar_spec_finish: logp {tuple(logp.shape)} beside out {tuple(out.shape)}")
+    call("lap_decode_grammar_spec_finish", _p(state), _p(sampling), _p(gstate), _p(offsets), _p(ids), _p(nxt), offsets.numel() - 1,
+         ids.numel(), _p(logits), _p(draft), _p(out), _p(logp), S, logits.shape[1], cap, int(eos_token))
 
 
 # ---- greedy speculative decoding of one sequence (csrc/decode_spec.hip; lap_amd/speculate.py restates the rules)

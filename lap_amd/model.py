@@ -694,7 +694,7 @@ class LAP:
     def sample_tokens(self, rng, observation, *, max_decoding_steps: int = 390, temperature: float = 0.0, collect=None,
                       decode: str = "eager", sampler: str = "host", decode_weights: str = "bf16", allowed_tokens=None,
                       return_logprobs: bool = False, num_samples=None, top_k=None, top_p=None, speculate=None, draft_tokens=None,
-                      grammar=None):
+                      grammar=None, jump_forward=None):
         """lap.py:678-766 (LAP_AR serving mode): VLM-only prefill, then single-token decode until every sample has emitted
         EOS or `max_decoding_steps` tokens; returns int32 [B, max_decoding_steps] (zeros after the stop).
 
@@ -792,15 +792,27 @@ class LAP:
         return_logprobs / num_samples a log-probability is the one over the state's set.  Composes with temperature > 0 under
         sampler="device", return_logprobs, num_samples and decode_weights; allowed_tokens, top_k / top_p, speculate and the host
         sampler at temperature > 0 raise ValueError, as does an automaton built for another vocabulary size or EOS token.  The
+        reference has no such option.
+
+        jump_forward: jump-forward grammar decoding.  None (default): a grammar decode emits one token per pass over the weights,
+        as before.  jump_forward=S, 2 <= S <= 8 (needs grammar=, decode="fused", an observation of batch 1, num_samples None,
+        collect None, and sampler="device" when temperature > 0; anything else raises ValueError): the constrained decode runs on
+        steps of S rows, as `speculate` does.  Whenever the automaton state has a single edge the next token is known before the
+        model runs, at any temperature, so it is drafted, and a run of such tokens rides along one pass; in the other states
+        `draft_tokens` (optional, as under `speculate`) may draft (`speculate.grammar_drafts`).  Row r draws with the noise of step
+        t + r from the state the rows before it led to (lap_decode_grammar_spec_finish: the single-row finish's bits, row after
+        row), so tokens and log-probabilities are those of the call without `jump_forward`, sampled or greedy, whatever the draft;
+        `last_spec_stats` = (steps, drafts accepted).  Composes with return_logprobs, decode_weights and temperature > 0.  The
         reference has no such option."""
         from lap_amd import ar_decode       # (it imports this module)
         return ar_decode.sample_tokens(self, rng, observation, max_decoding_steps=max_decoding_steps, temperature=temperature,
                                        collect=collect, decode=decode, sampler=sampler, decode_weights=decode_weights,
                                        allowed_tokens=allowed_tokens, return_logprobs=return_logprobs, num_samples=num_samples,
-                                       top_k=top_k, top_p=top_p, speculate=speculate, draft_tokens=draft_tokens, grammar=grammar)
+                                       top_k=top_k, top_p=top_p, speculate=speculate, draft_tokens=draft_tokens, grammar=grammar,
+                                       jump_forward=jump_forward)
 
     DECODE_WEIGHTS = ("bf16", "fp8", "fp8_layers")
-    last_spec_stats = None      # (verify steps, drafts accepted) of the last `sample_tokens(speculate=S)` request
+    last_spec_stats = None      # (verify steps, drafts accepted) of the last `sample_tokens(speculate=S)` or `(jump_forward=S)` request
 
     def decode_supported(self, B: int) -> bool:
         """Whether `sample_tokens(decode="fused")` / `GraphedTokenDecoder` serve `B` rows of this model."""

@@ -129,15 +129,29 @@ class GraphedTokenDecoder:
     grammar: `sample_tokens`' grammar-constrained decoding, a `grammar.TokenAutomaton` fixed at construction (the graphs hold the
     addresses of its device buffers).  The automaton state of every row lives in the context and is zeroed inside the prefill graph,
     so one capture serves every request and every request starts in state 0.  Composes with sampling=, weights=, logprobs= and
-    num_samples=; allowed_tokens=, filtering= and speculate= raise ValueError."""
+    num_samples=; allowed_tokens=, filtering= and speculate= raise ValueError.
+
+    jump_forward=S (2 <= S <= 8; needs grammar=, batch_size 1 and no num_samples): `sample_tokens`' jump-forward grammar decoding.
+    The step graph is captured on steps of S rows that are driven by device state alone (the automaton state, the reference
+    buffer, the sampling words), so one capture serves greedy and sampled requests and any `draft_tokens`; a call returns what the
+    decoder without it returns, log-probabilities included, and `last_stats` = (verify_steps, accepted).  Composes with sampling=,
+    weights= and logprobs=."""
 
     def __init__(self, model: LAP, batch_size: int = 1, max_decoding_steps: int = 390, prompt_len: int | None = None,
                  steps_per_replay: int = 8, sampling: bool = False, weights: str = "bf16", allowed_tokens=None,
-                 logprobs: bool = False, num_samples=None, filtering: bool = False, speculate=None, grammar=None):
+                 logprobs: bool = False, num_samples=None, filtering: bool = False, speculate=None, grammar=None, jump_forward=None):
         self.grammar = None
+        host = None
         if grammar is not None:
-            self.grammar = ar_decode.device_grammar(model, grammar, allowed_tokens=allowed_tokens, top_k=0 if filtering else None,
-                                                    speculate=speculate)
+            host = ar_decode.check_grammar(grammar, model.config.vocab_size, model.EOS_TOKEN, allowed_tokens=allowed_tokens,
+                                           top_k=0 if filtering else None, speculate=speculate)
+        self.J = None
+        if jump_forward is not None:
+            from lap_amd.speculate import check_jump_forward
+
+            self.J = check_jump_forward(jump_forward, batch_size, grammar=grammar, num_samples=num_samples)
+        if grammar is not None:
+            self.grammar = ar_decode.grammar_on_device(model, grammar, host)
         self.S = None
         self.last_stats = None
         if speculate is not None:
@@ -193,7 +207,7 @@ class GraphedTokenDecoder:
         if self.ctx is None:
             self.ctx = ar_decode.DecodeCtx(self.model, pre.B, pre.Pn, self.max_steps, self.sampling, self.weights,
                                            allowed=self.allowed, logprobs=self.logprobs, filtering=self.filtering, speculate=self.S,
-                                           grammar=self.grammar)
+                                           grammar=self.grammar, jump_forward=self.J)
         self.ctx.first_token(pre)
 
     def _steps(self):
@@ -221,7 +235,7 @@ class GraphedTokenDecoder:
         return self
 
     def __call__(self, obs: CoTObservation, *, temperature: float = 0.0, seed: int = 0, top_k=None, top_p=None, draft_tokens=None):
-        if draft_tokens is not None and self.S is None:
+        if draft_tokens is not None and self.S is None and self.J is None:
             raise ValueError("GraphedTokenDecoder: draft_tokens needs a decoder built with speculate=S")
         if temperature > 0.0 and not self.sampling:
             raise ValueError("GraphedTokenDecoder: temperature > 0 needs a decoder built with sampling=True")
@@ -239,14 +253,14 @@ class GraphedTokenDecoder:
             self.ctx.set_sampling(seed, temperature)
         if self.filtering:
             self.ctx.set_filter(*(filt or (None, None)))
-        if self.S is not None:
+        if self.S is not None or self.J is not None:
             self.ctx.set_draft(draft_tokens)
         self.g_prefill.replay()
         for _ in range((self.max_steps - 1 + self.spr - 1) // self.spr):
             if bool(self.ctx.state[1].item()):      # one host read per replay
                 break
             self.g_step.replay()
-        if self.S is not None:
+        if self.S is not None or self.J is not None:
             self.last_stats = self.ctx.stats()
         if self.logprobs:
             return self.ctx.out.clone(), self.ctx.logp.clone()
@@ -405,11 +419,25 @@ class ARPolicy:
                 raise ValueError(f"ARPolicy: decode_weights={weights!r} needs decode=\"fused\", got {self._sample_kwargs['decode']!r}")
         # sample_kwargs["grammar"] (grammar-constrained decoding: a grammar.TokenAutomaton) reaches both routes: it is checked and
         # put on the device once, here; the decoder is captured with it and sample_tokens gets the device form on every call
-        if self._sample_kwargs.get("grammar") is not None:
-            kw = self._sample_kwargs
-            self._sample_kwargs["grammar"] = ar_decode.device_grammar(
-                base.model, kw["grammar"], allowed_tokens=kw.get("allowed_tokens"), top_k=kw.get("top_k"), top_p=kw.get("top_p"),
-                speculate=kw.get("speculate"), sampler=kw.get("sampler", "host"), temperature=kw.get("temperature", 0.0))
+        # sample_kwargs["jump_forward"] = S (jump-forward grammar decoding; needs "grammar", implies decode="fused") reaches both
+        # routes and is checked between the grammar's own check and its copy to the device; like "speculate" it makes the policy
+        # pass the previous answer as the draft of the next request and report "spec_steps" / "spec_accepted"
+        kw = self._sample_kwargs
+        self._jump = kw.get("jump_forward")
+        host = None
+        if kw.get("grammar") is not None:
+            host = ar_decode.check_grammar(
+                kw["grammar"], base.model.config.vocab_size, base.model.EOS_TOKEN, allowed_tokens=kw.get("allowed_tokens"),
+                top_k=kw.get("top_k"), top_p=kw.get("top_p"), speculate=kw.get("speculate"), sampler=kw.get("sampler", "host"),
+                temperature=kw.get("temperature", 0.0))
+        if self._jump is not None:
+            from lap_amd.speculate import check_jump_forward
+
+            check_jump_forward(self._jump, 1, grammar=kw.get("grammar"), decode=kw.get("decode", "fused"), sampler=kw.get("sampler", "host"),
+                               temperature=kw.get("temperature", 0.0), num_samples=kw.get("num_samples"), collect=kw.get("collect"))
+            kw.setdefault("decode", "fused")
+        if host is not None:
+            kw["grammar"] = ar_decode.grammar_on_device(base.model, kw["grammar"], host)
         # sample_kwargs["allowed_tokens"] (constrained decoding) reaches both routes as well: the set is checked and put on the
         # device once, here; the decoder is captured with it and sample_tokens gets the checked set on every call
         if self._sample_kwargs.get("allowed_tokens") is not None:
@@ -437,6 +465,7 @@ class ARPolicy:
         # policy keeps the previous answer's tokens, up to and including the EOS, and passes them as the draft of the next request
         # (the first request drafts nothing); "policy_timing" gains "spec_steps" and "spec_accepted"
         self._speculate = self._sample_kwargs.get("speculate")
+        self._drafting = self._speculate is not None or self._jump is not None
         self._prev_tokens = None
         if self._speculate is not None:
             from lap_amd.speculate import check_speculate
@@ -451,7 +480,7 @@ class ARPolicy:
                                                 allowed_tokens=self._sample_kwargs.get("allowed_tokens"),
                                                 logprobs=self._logprobs, num_samples=self._num_samples,
                                                 filtering=bool(self._filter) and self._device_sampler, speculate=self._speculate,
-                                                grammar=self._sample_kwargs.get("grammar"))
+                                                grammar=self._sample_kwargs.get("grammar"), jump_forward=self._jump)
 
     def __getattr__(self, name):
         return getattr(self._base, name)
@@ -474,16 +503,20 @@ class ARPolicy:
             if self._speculate is not None:
                 tokens = self._decoder(o, draft_tokens=self._prev_tokens)
                 spec_stats = self._decoder.last_stats
+            elif self._jump is not None:
+                tokens = (self._decoder(o, temperature=temperature, seed=self._calls, draft_tokens=self._prev_tokens)
+                          if self._device_sampler else self._decoder(o, draft_tokens=self._prev_tokens))
+                spec_stats = self._decoder.last_stats
             else:
                 tokens = (self._decoder(o, temperature=temperature, seed=self._calls, **self._filter) if self._device_sampler
                           else self._decoder(o))
-        elif self._speculate is not None:
+        elif self._drafting:
             tokens = base.model.sample_tokens(self._calls, o, draft_tokens=self._prev_tokens, **self._sample_kwargs)
             spec_stats = base.model.last_spec_stats
         else:
             tokens = base.model.sample_tokens(self._calls, o, **self._sample_kwargs)
-        if self._speculate is not None:     # the next request's draft: this answer up to and including its EOS
-            row = tokens[0].cpu().numpy()
+        if self._drafting:                  # the next request's draft: this answer up to and including its EOS
+            row = (tokens[0] if self._logprobs else tokens)[0].cpu().numpy()
             stop = np.flatnonzero(row == base.model.EOS_TOKEN)
             self._prev_tokens = row[:int(stop[0]) + 1] if stop.size else row
         extra = {}
@@ -517,7 +550,8 @@ class ARPolicy:
 
 
 def create_trained_policy_ar(*args, sample_kwargs: dict | None = None, language_action_format="verbose_eef_with_rotation",
-                             ar_graph: bool = False, grammar: bool = False, grammar_limits: dict | None = None, **kwargs) -> ARPolicy:
+                             ar_graph: bool = False, grammar: bool = False, grammar_limits: dict | None = None, jump_forward=None,
+                             **kwargs) -> ARPolicy:
     """policy_config_adapter.py:157-160 with the AR output stack [DetokenizeReasoning, CoTOutputs(language_action_format)]:
     generated ids -> text -> [dx, dy, dz, droll, dpitch, dyaw, gripper] (the language action describes the whole chunk as
     one delta, output_transforms.py:75-104; `Unnormalize` has no `actions` statistics to apply to such deltas and is left out
@@ -540,7 +574,11 @@ def create_trained_policy_ar(*args, sample_kwargs: dict | None = None, language_
     returns ({"actions", "reasoning"}), so a client of this policy and of the websocket server receives them.
     grammar=True: every answer is constrained to the grammar of `language_action_format` (`policy_io.grammar_automaton` under the
     policy's tokenizer, for the model's vocabulary; sample_kwargs["grammar"] may instead hold an automaton of one's own), so a
-    sampled answer (best-of-N, temperature > 0) always parses; grammar_limits: the keywords of `lang_actions.word_graph`."""
+    sampled answer (best-of-N, temperature > 0) always parses; grammar_limits: the keywords of `lang_actions.word_graph`.
+    jump_forward=S (2 <= S <= 8; with grammar=True or an automaton in sample_kwargs; the same as sample_kwargs={"jump_forward": S}):
+    the constrained answer is decoded on steps of S rows on which the tokens the grammar forces, and what the previous request's
+    answer drafts, ride along (`LAP.sample_tokens`); tokens and log-probabilities are unchanged, at any temperature, and
+    "policy_timing" gains "spec_steps" and "spec_accepted"."""
     from lap_amd import policy_io as pio
 
     base = create_trained_policy(*args, use_graph=False, **kwargs)
@@ -549,5 +587,7 @@ def create_trained_policy_ar(*args, sample_kwargs: dict | None = None, language_
         sample_kwargs = dict(sample_kwargs or {})
         sample_kwargs["grammar"] = pio.grammar_automaton(tok, language_action_format, vocab_size=base.model.config.vocab_size,
                                                          **(grammar_limits or {}))
+    if jump_forward is not None:
+        sample_kwargs = dict(sample_kwargs or {}) | {"jump_forward": jump_forward}
     base._output_transform = pio.compose([pio.DetokenizeReasoning(tok), pio.CoTOutputs(language_action_format=language_action_format)])
     return ARPolicy(base, sample_kwargs=sample_kwargs, use_graph=ar_graph)

@@ -6,6 +6,13 @@ A verify step of S rows (2 <= S <= 8) runs the fused decode kernels on the conse
 row 0 feeds the real last token out[t-1], row r the drafted token draft[r-1].  Row r computes what the single-token step at t + r
 computes provided drafts 0 .. r-1 were right, so emitting tok[0] and then tok[r] while draft[r-1] == tok[r-1] reproduces the greedy
 decode token for token; only the number of passes over the weights changes.
+
+Jump-forward grammar decoding (`jump_forward=S`) runs a grammar-constrained decode (lap_amd/grammar.py) on the same S-row steps.  In
+an automaton state with a single edge the next token is known before the model runs, at any temperature, so it is drafted;
+elsewhere the reference may draft.  The constrained draw of row r is that of the single-row grammar step at step index t + r from
+the state the rows before it led to, so the accepted run reproduces the plain grammar decode, sampled or greedy.
+`grammar_drafts`, `grammar_verify` and `replay_grammar` are the specification of lap_decode_grammar_draft and
+lap_decode_grammar_spec_finish (csrc/decode_grammar.hip).
 """
 from __future__ import annotations
 
@@ -71,6 +78,115 @@ def replay(tokens, ref, S: int, cap: int, eos: int):
         t += len(e)
         done = t >= cap or eos in e.tolist()
     return steps, accepted
+
+
+def _segment(automaton, q: int):
+    """The ids state q allows; None for a q outside the automaton (the kernels never use such a q as an address)."""
+    return automaton.allowed(int(q)) if 0 <= int(q) < automaton.num_states else None
+
+
+def grammar_drafts(automaton, q: int, refdraft) -> np.ndarray:
+    """The S - 1 drafts of a jump-forward step from the automaton state `q` after the last written token; `refdraft` (int [S-1]) is
+    what `draft_tokens(ref, out, t, S)` gives (all -1 without a reference).  For r = 0 .. S-2: a state with one edge drafts that id;
+    otherwise refdraft[r] is drafted when the state allows it; otherwise this draft and every later one is -1.  After a drafted
+    token q = step(q, draft); drafts after a drafted EOS are -1, as are all drafts from a q outside the automaton."""
+    refdraft = np.asarray(refdraft).reshape(-1)
+    out = np.full(refdraft.shape[0], -1, dtype=np.int32)
+    q = int(q)
+    for r in range(refdraft.shape[0]):
+        seg = _segment(automaton, q)
+        if seg is None:
+            break
+        d = int(seg[0]) if seg.shape[0] == 1 else int(refdraft[r])
+        nq = automaton.step(q, d)
+        if nq < 0:
+            break
+        out[r] = d
+        if d == automaton.eos_token:
+            break
+        q = nq
+    return out
+
+
+def grammar_verify(logits, automaton, q: int, drafts, t: int, cap: int, temperature: float, seed: int):
+    """What a jump-forward step emits from its float32 `logits` [S, V]: (emitted int32 [n], logp float64 [n], q_after), with
+    out[t + i] = emitted[i].  Row r is the constrained draw of `grammar.decode_reference` for row index 0 at step index t + r from the
+    state q_r (q_0 = q, q_{r+1} = step(q_r, tok[r])): `sampling.sample_from_logits` on the logits set to -inf outside allowed(q_r),
+    and `sampling.token_logprobs` over that set.  A row whose q_r lies outside the automaton emits the EOS token with
+    log-probability -inf and keeps its state.  The accept rule is `accept`'s: tok[0], then tok[r] while tok[r-1] != eos and
+    drafts[r-1] == tok[r-1] and t + r < cap.  Empty when t >= cap.  q_after: the state after the last emitted token."""
+    from lap_amd import sampling
+
+    lg = np.asarray(logits, dtype=np.float32)
+    drafts = np.asarray(drafts).reshape(-1)
+    eos = automaton.eos_token
+    q = int(q)
+    if t >= cap:
+        return np.zeros((0,), np.int32), np.zeros((0,), np.float64), q
+    emitted, logp = [], []
+    for r in range(lg.shape[0]):
+        if r > 0 and not (emitted[-1] != eos and int(drafts[r - 1]) == emitted[-1] and t + r < cap):
+            break
+        seg = _segment(automaton, q)
+        if seg is None:
+            emitted.append(eos)
+            logp.append(-np.inf)
+            continue
+        masked = np.full((1, lg.shape[1]), -np.inf, dtype=np.float32)
+        masked[0, seg] = lg[r, seg]
+        tok = sampling.sample_from_logits(masked, temperature, seed, t + r)
+        emitted.append(int(tok[0]))
+        logp.append(float(sampling.token_logprobs(lg[r:r + 1], tok, temperature, allowed=seg)[0]))
+        nq = automaton.step(q, int(tok[0]))
+        if nq < 0:
+            raise ValueError(f"row {r}: token {int(tok[0])} is not allowed (every allowed logit is -inf or NaN)")
+        q = nq
+    return np.array(emitted, dtype=np.int32), np.array(logp, dtype=np.float64), q
+
+
+def replay_grammar(tokens, automaton, ref, S: int, cap: int):
+    """(verify_steps, accepted) of a jump-forward decode whose answer is `tokens` (one row of `sample_tokens`, zeros after the
+    stop) under the reference `ref`, as `replay` gives them for `speculate`: the steps are replayed with `draft_tokens`,
+    `grammar_drafts` and `accept`, row r's token being tokens[t + r] while the drafts before it are right."""
+    tokens = np.asarray(tokens).reshape(-1)
+    eos = automaton.eos_token
+    q = automaton.step(0, int(tokens[0]))
+    t, steps, accepted, done = 1, 0, 0, cap <= 1 or int(tokens[0]) == eos
+    while not done:
+        d = grammar_drafts(automaton, q, draft_tokens(ref, tokens, t, S))
+        tok = np.array([int(tokens[t + r]) if t + r < cap else -2 for r in range(S)])
+        e = accept(tok, d, t, cap, eos)
+        for x in e.tolist():
+            q = automaton.step(q, x) if q >= 0 else q
+        steps += 1
+        accepted += len(e) - 1
+        t += len(e)
+        done = t >= cap or eos in e.tolist()
+    return steps, accepted
+
+
+def check_jump_forward(jump_forward, batch: int, *, grammar, decode: str = "fused", sampler: str = "device", temperature: float = 0.0,
+                       num_samples=None, collect=None) -> int:
+    """`jump_forward` of a request as the number of rows S of a step; ValueError naming the condition it breaks."""
+    if isinstance(jump_forward, bool) or not isinstance(jump_forward, (int, np.integer)):
+        raise ValueError(f"jump_forward must be an integer, got {jump_forward!r}")
+    S = int(jump_forward)
+    if not MIN_ROWS <= S <= MAX_ROWS:
+        raise ValueError(f"jump_forward must lie in [{MIN_ROWS}, {MAX_ROWS}] (the rows of one fused step), got {S}")
+    if grammar is None:
+        raise ValueError("jump_forward needs grammar= (the forced tokens are those of the automaton's single-edge states)")
+    if decode != "fused":
+        raise ValueError(f"jump_forward needs decode=\"fused\" (its steps run on the fused decode kernels), got decode={decode!r}")
+    if batch != 1:
+        raise ValueError(f"jump_forward needs an observation of batch 1 (the rows of a step are positions of one sequence), got batch {batch}")
+    if num_samples is not None:
+        raise ValueError(f"jump_forward does not combine with best-of-N: num_samples must be None, got {num_samples!r}")
+    if collect is not None:
+        raise ValueError("jump_forward does not hand out logits: collect must be None")
+    if sampler != "device" and temperature > 0.0:
+        raise ValueError(f"jump_forward at temperature > 0 needs sampler=\"device\" (the constrained draw is part of the device sampler), "
+                         f"got sampler={sampler!r}")
+    return S
 
 
 def check_speculate(speculate, batch: int, *, decode: str = "fused", temperature: float = 0.0, return_logprobs: bool = False,

@@ -5,6 +5,7 @@ run decodes N tokens.  One JSON line.
 
     python tools/bench_ar.py [--tokens 64] [--config lap_bench] [--kwaves 4] [--temperature T] [--weights bf16 fp8 fp8_layers]
                              [--allowed N] [--logprobs] [--num-samples N] [--speculate S [S ...]] [--grammar verbose]
+                             [--jump-forward S [S ...]]
 
 --temperature T > 0 adds the sampled figures: the eager loop with the torch-generator noise (sampler="host"), the eager loop and
 the fused steps with the device noise (sampler="device"), and a GraphedTokenDecoder(sampling=True) called sampled and greedy.
@@ -39,6 +40,12 @@ and lap_decode_grammar_finish, each from a captured graph of back-to-back launch
 head piece and single-character pieces with ids in order of first use, which gives the automaton the shape a real tokenizer gives
 it.  The automaton needs a real EOS id (the model's is set to 1 for this part), so after "gripper" the sentence may start again and a
 row ends only when it draws EOS there; the grammar figure is per token actually decoded, which the result reports.
+--jump-forward S [S ...] (with --grammar verbose) adds jump-forward grammar decoding (`grammar=` + `jump_forward=S`), graphed at B = 1
+on the automaton of the same synthetic word graph WITHOUT the restart after "gripper", so the greedy answer is one sentence that
+ends in its EOS: ms per answer (the call minus the prefill graph) of `grammar=` alone and of every S, without a reference (only
+the tokens the grammar forces ride along) and with the answer itself as the reference (every step is full), each as the mean and
+[min, max] of the timed repeats with the decoders taking turns; the steps and accepted drafts (`last_stats`), whether tokens and
+log-probabilities equal the plain grammar graph's, and the cost of one S-row step relative to one single-row step.
 """
 import argparse
 import json
@@ -70,8 +77,11 @@ ap.add_argument("--num-samples", type=int, default=0, help="N > 0: also measure 
 ap.add_argument("--top-k", type=int, default=0, help="with --temperature: also measure filtered sampled decoding (top_k)")
 ap.add_argument("--top-p", type=float, default=1.0, help="with --temperature: also measure filtered sampled decoding (top_p)")
 ap.add_argument("--grammar", choices=["verbose"], default=None, help="also measure grammar-constrained decoding (verbose-with-rotation)")
+ap.add_argument("--jump-forward", type=int, nargs="+", default=[], help="with --grammar: also measure grammar + jump_forward at these step widths")
 ap.add_argument("--speculate", type=int, nargs="+", default=[], help="also measure exact speculative decoding at these verify-step widths")
 a = ap.parse_args()
+if a.jump_forward and not a.grammar:
+    ap.error("--jump-forward needs --grammar")
 hip.DECODE_KWAVES_DOWN = a.kwaves
 
 cfg = get_config(a.config).model
@@ -341,6 +351,53 @@ if a.grammar:
         "allowed_union_tokens_decoded": a_res[2], "plain_graphed_ms_per_token": round(g_ms, 3),
         "grammar_row_is_accepted_or_cut_by_the_budget": bool(auto.accepts(gtok[0].cpu().numpy()) or int((gtok[0] == 1).sum()) == 0),
         "launch_us": launch_us}}
+if a.jump_forward:
+    model.EOS_TOKEN = 1
+    auto1 = G.automaton_from_words(encode, LA.word_graph(LA.VERBOSE_WITH_ROTATION_FORMAT), 1, cfg.vocab_size)      # one sentence, then EOS
+    decs = {0: GraphedTokenDecoder(model, 1, N, grammar=auto1, logprobs=True).capture()}
+    for S in a.jump_forward:
+        decs[S] = GraphedTokenDecoder(model, 1, N, grammar=auto1, logprobs=True, jump_forward=S).capture()
+    pre = {S: timeit(lambda d=d: (d.g_prefill.replay()), a.reps) for S, d in decs.items()}
+    answer, answer_lp = decs[0](o)
+    row = answer[0].tolist()
+    ans = row[:row.index(1) + 1] if 1 in row else row
+    forced_states, q = 0, 0
+    for x in ans:
+        forced_states += int(len(auto1.allowed(q)) == 1)
+        q = auto1.step(q, x)
+    runs = {(S, r): [] for S in decs for r in ("none", "answer") if S or r == "none"}
+    stats, equal = {}, {}
+    for _ in range(max(a.reps, 7)):         # the decoders take turns, so that a drift of the machine reaches all of them
+        for S, r in runs:
+            kw = {"draft_tokens": ans if r == "answer" else None} if S else {}
+            runs[(S, r)].append(timeit(lambda: decs[S](o, **kw), 1) - pre[S])
+            if S:
+                jgot = decs[S](o, **kw)
+                stats[(S, r)] = list(decs[S].last_stats)
+                equal[(S, r)] = bool(torch.equal(jgot[0], answer) and torch.equal(jgot[1].view(torch.int32), answer_lp.view(torch.int32)))
+    mean = lambda k: sum(runs[k]) / len(runs[k])
+    plain_ms = mean((0, "none"))
+    one_row_step_ms = plain_ms / max(len(ans) - 1, 1)
+    jf = {"format": "verbose_with_rotation", "Q": auto1.num_states, "E": auto1.num_edges, "union": int(auto1.union().shape[0]),
+          "answer_tokens": len(ans), "answer_ends_in_eos": bool(ans[-1] == 1), "tokens_from_single_edge_states": forced_states,
+          "grammar_ms_per_answer": round(plain_ms, 3),
+          "grammar_ms_per_answer_min_max": [round(min(runs[(0, "none")]), 3), round(max(runs[(0, "none")]), 3)],
+          "single_row_step_ms": round(one_row_step_ms, 4)}
+    for S in a.jump_forward:
+        step_ms = mean((S, "none")) / max(stats[(S, "none")][0], 1)
+        jf[f"S{S}"] = {
+            "forced_only_ms_per_answer": round(mean((S, "none")), 3),
+            "forced_only_ms_per_answer_min_max": [round(min(runs[(S, "none")]), 3), round(max(runs[(S, "none")]), 3)],
+            "forced_only_steps_accepted": stats[(S, "none")],
+            "answer_as_reference_ms_per_answer": round(mean((S, "answer")), 3),
+            "answer_as_reference_ms_per_answer_min_max": [round(min(runs[(S, "answer")]), 3), round(max(runs[(S, "answer")]), 3)],
+            "answer_as_reference_steps_accepted": stats[(S, "answer")],
+            "step_ms": round(step_ms, 4), "step_cost_over_single_row_step": round(step_ms / one_row_step_ms, 3),
+            "forced_only_speedup": round(plain_ms / mean((S, "none")), 3),
+            "answer_as_reference_speedup": round(plain_ms / mean((S, "answer")), 3),
+            "tokens_and_logprobs_equal_plain_grammar_graph": equal[(S, "none")] and equal[(S, "answer")]}
+    model.EOS_TOKEN = -1
+    grammar_res["grammar_jump_forward"] = jf
 print(json.dumps({
     "metric": "batch-1 LAP_AR decode LAP-3B bf16 (ms per token after the prefill, greedy, EOS disabled)",
     "tokens": N, "prompt_len": cfg.max_token_len,
