@@ -167,10 +167,15 @@ def device_grammar(model: LAP, grammar, **combined):
 def sample_tokens(model: LAP, rng, observation, *, max_decoding_steps: int = 390, temperature: float = 0.0, collect=None,
                   decode: str = "eager", sampler: str = "host", decode_weights: str = "bf16", allowed_tokens=None,
                   return_logprobs: bool = False, num_samples=None, top_k=None, top_p=None, speculate=None, draft_tokens=None,
-                  grammar=None, jump_forward=None):
+                  grammar=None, jump_forward=None, num_beams=None, early_stop: bool = True):
     """`LAP.sample_tokens` (documented there): every argument is checked before any device work."""
     if decode not in ("eager", "fused"):
         raise ValueError(f"sample_tokens: decode must be 'eager' or 'fused', got {decode!r}")
+    if num_beams is not None:
+        return _sample_beams(model, observation, num_beams, early_stop, max_decoding_steps=max_decoding_steps, temperature=temperature,
+                             collect=collect, decode=decode, sampler=sampler, decode_weights=decode_weights, allowed_tokens=allowed_tokens,
+                             return_logprobs=return_logprobs, num_samples=num_samples, top_k=top_k, top_p=top_p, speculate=speculate,
+                             draft_tokens=draft_tokens, grammar=grammar, jump_forward=jump_forward)
     grammar_host = None
     if grammar is not None:
         grammar_host = check_grammar(grammar, model.config.vocab_size, model.EOS_TOKEN, allowed_tokens=allowed_tokens, top_k=top_k,
@@ -214,6 +219,35 @@ def sample_tokens(model: LAP, rng, observation, *, max_decoding_steps: int = 390
                              "host sampler keeps the eager loop)")
         return _sample_eager(model, rng, observation, max_decoding_steps=max_decoding_steps, temperature=temperature, collect=collect,
                              device_sampler=sampler == "device", allowed=allowed, logprobs=return_logprobs, filt=filt, grammar=grammar)
+
+
+def _sample_beams(model: LAP, observation, num_beams, early_stop, *, max_decoding_steps, temperature, collect, decode, sampler,
+                  decode_weights, allowed_tokens, return_logprobs, num_samples, top_k, top_p, speculate, draft_tokens, grammar, jump_forward):
+    """`sample_tokens(num_beams=N)`: the checks, then the fused or the eager beam decode; the rank-0 beam as [1, cap] tokens (and
+    its token log-probabilities)."""
+    from lap_amd.beam import check_num_beams
+
+    N = check_num_beams(num_beams, observation.tokenized_prompt.shape[0], decode=decode, temperature=temperature, sampler=sampler,
+                        num_samples=num_samples, top_k=top_k, top_p=top_p, speculate=speculate, grammar=grammar, jump_forward=jump_forward,
+                        collect=collect)
+    if draft_tokens is not None:
+        raise ValueError("sample_tokens: draft_tokens needs speculate=S")
+    check_decode_weights(decode_weights)
+    if decode_weights != "bf16" and decode != "fused":
+        raise ValueError(f"sample_tokens: decode_weights={decode_weights!r} runs on the fused decode kernels only: pass decode=\"fused\"")
+    if max_decoding_steps < 1:
+        raise ValueError(f"sample_tokens: num_beams needs max_decoding_steps >= 1, got {max_decoding_steps}")
+    if decode == "fused":
+        check_fused_decode(model, N)
+    allowed = allowed_set(model, allowed_tokens).ids if allowed_tokens is not None else None
+    with model._serving_weights():
+        if decode == "fused":
+            tokens, logp, _ = beam_decode_fused(model, observation, N, max_decoding_steps=max_decoding_steps, early_stop=early_stop,
+                                                weights=decode_weights, allowed=allowed)
+        else:
+            tokens, logp, _ = beam_decode_eager(model, observation, N, max_decoding_steps=max_decoding_steps, early_stop=early_stop,
+                                                allowed=allowed)
+    return (tokens[:1].contiguous(), logp[:1].contiguous()) if return_logprobs else tokens[:1].contiguous()
 
 
 class Prefill(NamedTuple):
@@ -383,6 +417,63 @@ def _sample_eager(model: LAP, rng, observation, *, max_decoding_steps: int, temp
     return (out, logp) if logprobs else out
 
 
+def beam_decode_eager(model: LAP, observation, N: int, *, max_decoding_steps: int, early_stop: bool = True, allowed=None, on_step=None):
+    """Beam search on the eager step, the second implementation beside `beam_decode_fused` (call it under `_serving_weights`): the
+    batch-1 prefill replicated to N rows, per-step f32 logits from the generic launches, `beam.beam_step` on the host in float64,
+    `index_select` by parent on the generated K / V.  allowed: int32 device ids.  on_step: `beam.beam_search`'s hook.
+    Returns (tokens int32 [N, cap], logp f32 [N, cap], scores f32 [N]) on the device, in rank order."""
+    import numpy as np
+
+    from lap_amd import beam as bm
+
+    dev = model.device
+    B, Pn, cache, kinfo_prefix, qinfo_d, plen, x_last = replicate_prefill(prefill(model, observation), N)
+    outside = None
+    if allowed is not None:
+        outside = torch.ones((model.config.vocab_size,), dtype=torch.bool, device=dev)
+        outside[allowed.long()] = False
+    gen = [(None, None)] * model.v.depth
+    state = {"gen": gen}
+
+    def logits_fn(prefixes):
+        t = prefixes.shape[1]
+        if t == 0:
+            lg = _lm_logits(model, x_last)
+        else:
+            token = torch.from_numpy(np.ascontiguousarray(prefixes[:, t - 1])).to(dev)
+            pos = (plen + (t - 1)).to(torch.int32).view(B, 1).contiguous()
+            lg = _vlm_decode_step(model, token, pos, t - 1, cache, state["gen"], qinfo_d, kinfo_prefix, B, Pn)
+        if outside is not None:
+            lg = lg.masked_fill(outside, float("-inf"))
+        return lg.cpu().numpy()
+
+    def reorder(t, logits, scores, finished, res):
+        if on_step is not None:
+            on_step(t, logits, scores, finished, res)
+        par = torch.from_numpy(res[0]).to(dev).long()
+        state["gen"] = [(gk, gv) if gk is None else (gk.index_select(0, par), gv.index_select(0, par)) for gk, gv in state["gen"]]
+
+    tokens, logp, scores = bm.beam_search(logits_fn, N, max_decoding_steps, model.EOS_TOKEN, early_stop, on_step=reorder)
+    return (torch.from_numpy(tokens).to(dev), torch.from_numpy(logp.astype(np.float32)).to(dev),
+            torch.from_numpy(scores.astype(np.float32)).to(dev))
+
+
+def beam_decode_fused(model: LAP, observation, N: int, *, max_decoding_steps: int, early_stop: bool = True, weights: str = "bf16",
+                      allowed=None):
+    """Beam search on the fused step (call it under `_serving_weights`): `replicate_prefill` to N rows and a `DecodeCtx(beams=N)`.
+    Returns `DecodeCtx.beam_result()`: (tokens int32 [N, cap], logp f32 [N, cap], scores f32 [N]) in rank order."""
+    pre = replicate_prefill(prefill(model, observation), N)
+    ctx = DecodeCtx(model, N, pre.Pn, max_decoding_steps, weights=weights, allowed=allowed, beams=N, early_stop=early_stop)
+    ctx.first_token(pre)
+    n = DECODE_STEPS_PER_CHECK
+    for _ in range((max_decoding_steps - 1 + n - 1) // n):
+        if bool(ctx.state[1].item()):
+            break
+        for _ in range(n):
+            ctx.step()
+    return ctx.beam_result()
+
+
 # ---- the fused step: single-token kernels, state on the device (csrc/decode.hip)
 def _sample_fused(model: LAP, observation, *, max_decoding_steps: int, collect=None, sampling=None, weights: str = "bf16",
                   allowed=None, logprobs: bool = False, num_samples=None, filt=None, speculate=None, draft=None, grammar=None, jump=None):
@@ -452,11 +543,27 @@ class DecodeCtx:
     (`set_draft`), overwrites the drafts with the grammar's (lap_decode_grammar_draft: a state with one edge forces its token), runs
     the layers on the S positions, the plain SUBSET head over the union on the S rows, and lap_decode_grammar_spec_finish, which
     draws the rows in sequence with the single-row finish's bits and accepts the longest verified run.  Tokens and
-    log-probabilities are those of the grammar context without it; `stats` reads the counters."""
+    log-probabilities are those of the grammar context without it; `stats` reads the counters.
+    beams=N (B = N; greedy, not with filtering, speculate, grammar or jump_forward; composes with weights and allowed): the rows are
+    the beams of one beam search (lap_amd/beam.py, csrc/decode_beam.hip).  The context owns the beam buffer (scores, finished,
+    parent, the `early_stop` flag; reset by `first_token` with a device copy that a captured prefill replays), the [N, V] f32 logits
+    of the step, the [N, N] candidates and `logp`.  Its LM head is the plain greedy one (plain / SUBSET / fp8), which stores its
+    logits; lap_decode_beam_topn and lap_decode_beam_select finish the step, and `step` starts with lap_decode_beam_reorder, which
+    moves the generated K / V rows to the parents the last select chose.  `beam_result` hands out all beams."""
 
     def __init__(self, model: LAP, B: int, Pn: int, cap: int, sampling: bool = False, weights: str = "bf16", allowed=None,
-                 logprobs: bool = False, filtering: bool = False, speculate=None, grammar=None, jump_forward=None):
+                 logprobs: bool = False, filtering: bool = False, speculate=None, grammar=None, jump_forward=None, beams=None,
+                 early_stop: bool = True):
         check_decode_weights(weights)
+        self.beams = None
+        if beams is not None:
+            from lap_amd.beam import check_num_beams
+
+            self.beams = check_num_beams(beams, 1, temperature=1.0 if sampling else 0.0, top_k=0 if filtering else None,
+                                         speculate=speculate, grammar=grammar, jump_forward=jump_forward)
+            if B != self.beams:
+                raise ValueError(f"DecodeCtx: beams={self.beams} are the rows of the batch, got B {B}")
+            logprobs = True
         self.J = None
         if jump_forward is not None:
             self.J = check_jump_forward(jump_forward, B, grammar=grammar)
@@ -501,7 +608,7 @@ class DecodeCtx:
         # logprobs: the log-probability of every token of `out` beside it (f32 [B, cap], zeros where nothing was written) and the
         # LM head's log-sum-exp partials; None: the context launches the heads without them
         self.logp = torch.zeros((B, cap), dtype=torch.float32, device=dev) if logprobs else None
-        self.plp = hip.decode_lm_logp_partials(B, dev) if logprobs and grammar is None else None
+        self.plp = hip.decode_lm_logp_partials(B, dev) if logprobs and grammar is None and self.beams is None else None
         # filtering: the filter words {top_k, bits of top_p, 0, 0} (neutral until `set_filter`) and the f32 logits of the step, which
         # keep -inf outside an allowed set (the constrained head writes the allowed columns only)
         self.filter = hip.decode_filter(dev) if filtering else None
@@ -516,8 +623,32 @@ class DecodeCtx:
         if grammar is not None:
             self.gstate = torch.zeros((B,), dtype=torch.int32, device=dev)
             self.logits = torch.full((R, model.config.vocab_size), float("-inf"), dtype=torch.float32, device=dev)
+        # beams: the beam buffer and what a fresh decode copies over it, the f32 logits of the step (-inf outside an allowed set,
+        # written once) and the N best (log-probability, id) of every row
+        self.beam = None
+        if self.beams is not None:
+            self.beam_init = hip.decode_beam_init_words(B, early_stop, dev)
+            self.beam = self.beam_init.clone()
+            self.logits = torch.empty((B, model.config.vocab_size), dtype=torch.float32, device=dev)
+            if allowed is not None:
+                self.logits.fill_(float("-inf"))
+            self.cand_logp = torch.zeros((B, B), dtype=torch.float32, device=dev)
+            self.cand_id = torch.full((B, B), -1, dtype=torch.int32, device=dev)
         self.prefix = None
         self.kinfo = None
+
+    def beam_result(self):
+        """All beams of the decode so far, in rank order: (tokens int32 [N, cap], logp f32 [N, cap], scores f32 [N]), fresh
+        tensors; `scores` is the device's running f32 sum of a beam's token log-probabilities (-inf: a padding beam)."""
+        if self.beam is None:
+            raise ValueError("this decode context was built without beams")
+        return self.out.clone(), self.logp.clone(), self.beam[:self.B].clone().view(torch.float32)
+
+    def beam_reorders(self) -> int:
+        """The steps of the decode so far whose parent permutation was not the identity (a host read)."""
+        if self.beam is None:
+            raise ValueError("this decode context was built without beams")
+        return int(self.beam[25].item())
 
     def set_filter(self, top_k, top_p):
         """top_k / top_p of the next decode (None: neutral; a host-to-device copy; captured graphs keep the buffer's address)."""
@@ -560,6 +691,8 @@ class DecodeCtx:
             self.logp.zero_()
         if self.gstate is not None:       # every request starts in state 0 (a device op: the prefill graph captures it)
             self.gstate.zero_()
+        if self.beam is not None:         # every request starts from {0, -inf, ...} (a device copy: the prefill graph captures it)
+            self.beam.copy_(self.beam_init)
         self._token(pre.x_last, logits)
 
     def _w(self, name):
@@ -581,6 +714,12 @@ class DecodeCtx:
             hi, lo, kw = m.W("llm/embed"), m.ps.w16lo("llm/embed"), {}
         if self.allowed is not None:      # the LM head streams the allowed rows only
             kw["ids"] = self.allowed
+        if self.beam is not None:         # the plain head stores the logits, topn and select finish the step
+            hip.decode_lm_head(self.state, x, m.F("llm/final_norm"), hi, lo, self.pval, self.pidx, self.logits, **kw)
+            hip.decode_beam_topn(self.state, self.beam, self.logits, self.cand_logp, self.cand_id, self.cap)
+            hip.decode_beam_select(self.state, self.beam, self.cand_logp, self.cand_id, self.out, self.logp, m.config.vocab_size,
+                                   m.EOS_TOKEN)
+            return
         if verify and self.J:             # the plain head over the union stores the S rows of logits, the finish draws them in sequence
             g = self.grammar
             hip.decode_lm_head(self.state, x, m.F("llm/final_norm"), hi, lo, self.pval, self.pidx, self.logits, **(kw | {"ids": g.union}))
@@ -623,6 +762,8 @@ class DecodeCtx:
         NH, HD, KV = v.num_heads, v.head_dim, v.num_kv_heads
         rows, lo, hi = m.ps.embed_rows()
         rows_of_one = bool(self.S or self.J)        # the rows are S positions of one sequence
+        if self.beam is not None:         # the generated K / V of every beam become those of the parent the last select chose
+            hip.decode_beam_reorder(self.state, self.beam, self.gen)
         if rows_of_one:
             hip.decode_spec_draft(self.state, self.ref, self.out, self.draft)
             if self.J:

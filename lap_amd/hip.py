@@ -253,6 +253,10 @@ SIGNATURES: dict[str, list] = {
     "lap_decode_grammar_finish": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "lap_decode_grammar_draft": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp],
     "lap_decode_grammar_spec_finish": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "lap_decode_beam_words": [],
+    "lap_decode_beam_topn": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "lap_decode_beam_select": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "lap_decode_beam_reorder": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
 }
 
 _fn = {}
@@ -1839,3 +1843,67 @@ def decode_spec_accept(state, pval, pidx, draft, out, eos_token):
     if pval.numel() < S * _fn["lap_decode_lm_blocks"]() or pidx.numel() < S * _fn["lap_decode_lm_blocks"]():
         raise TypeError("decode_spec_accept: pval / pidx hold [lap_decode_lm_blocks()][S] partials")
     call("lap_decode_spec_accept", _p(state), _p(pval), _p(pidx), _p(draft), _p(out), S, cap, int(eos_token))
+
+
+# ---- beam search over the rows of one fused decode batch (csrc/decode_beam.hip; lap_amd/beam.py restates the rules)
+def decode_beam_init_words(N, early_stop, device):
+    """The beam buffer of a fresh decode of N beams (lap_hip.h: scores {0, -inf, ...}, nothing finished, parent = own index, the
+    early_stop flag, the reorder counter at zero): int32 [lap_decode_beam_words()].  A context copies it over its live buffer with
+    a device op inside the prefill part, so a captured graph starts every request from it."""
+    import numpy as np
+
+    if not 1 <= int(N) <= 8:
+        raise ValueError(f"decode_beam_init_words: 1 <= N <= 8, got {N}")
+    words = np.zeros(_fn["lap_decode_beam_words"](), dtype=np.int32)
+    scores = np.full(8, -np.inf, dtype=np.float32)
+    scores[0] = 0.0
+    words[0:8] = scores.view(np.int32)
+    words[16:24] = np.arange(8)
+    words[24] = 1 if early_stop else 0
+    return torch.from_numpy(words).to(device)
+
+
+def _beam_req(fn, state, beam, N):
+    _dreq(state, torch.int32, "state"); _dreq(beam, torch.int32, "beam")
+    if not 1 <= N <= 8:
+        raise ValueError(f"{fn}: 1 <= N <= 8 beams, got {N}")
+    if state.numel() < _fn["lap_decode_state_words"]() or beam.numel() < _fn["lap_decode_beam_words"]():
+        raise TypeError(f"{fn}: state int32 [lap_decode_state_words()], beam int32 [lap_decode_beam_words()]")
+
+
+def decode_beam_topn(state, beam, logits, cand_logp, cand_id, cap):
+    """cand_logp / cand_id [N, N]: the N best (log-probability, id) of every row of the f32 `logits` [N, V] that the LM head of the
+    step stored; id -1 where a row has fewer (lap_decode_beam_topn; `beam.row_topn`).  cap: the budget of the decode."""
+    _dreq(logits, torch.float32, "logits"); _dreq(cand_logp, torch.float32, "cand_logp"); _dreq(cand_id, torch.int32, "cand_id")
+    if logits.dim() != 2:
+        raise TypeError(f"decode_beam_topn: logits [N, V], got {tuple(logits.shape)}")
+    N, V = logits.shape
+    _beam_req("decode_beam_topn", state, beam, N)
+    if tuple(cand_logp.shape) != (N, N) or tuple(cand_id.shape) != (N, N):
+        raise TypeError(f"decode_beam_topn: cand_logp / cand_id [{N}, {N}], got {tuple(cand_logp.shape)}, {tuple(cand_id.shape)}")
+    call("lap_decode_beam_topn", _p(state), _p(beam), _p(logits), _p(cand_logp), _p(cand_id), N, V, int(cap))
+
+
+def decode_beam_select(state, beam, cand_logp, cand_id, out, logp, V, eos_token):
+    """The finish of a beam step (lap_decode_beam_select; `beam.beam_step`): the N best of the candidates become the beams in rank
+    order; out / logp [N, cap] are permuted by parent up to t and get column t; the beam buffer, the EOS words, t and done move."""
+    _dreq(cand_logp, torch.float32, "cand_logp"); _dreq(cand_id, torch.int32, "cand_id")
+    _dreq(out, torch.int32, "out"); _dreq(logp, torch.float32, "logp")
+    if out.dim() != 2 or tuple(logp.shape) != tuple(out.shape):
+        raise TypeError(f"decode_beam_select: out [N, cap] with logp beside it, got {tuple(out.shape)}, {tuple(logp.shape)}")
+    N, cap = out.shape
+    _beam_req("decode_beam_select", state, beam, N)
+    if tuple(cand_logp.shape) != (N, N) or tuple(cand_id.shape) != (N, N):
+        raise TypeError(f"decode_beam_select: cand_logp / cand_id [{N}, {N}], got {tuple(cand_logp.shape)}, {tuple(cand_id.shape)}")
+    call("lap_decode_beam_select", _p(state), _p(beam), _p(cand_logp), _p(cand_id), _p(out), _p(logp), N, int(V), cap, int(eos_token))
+
+
+def decode_beam_reorder(state, beam, gen):
+    """gen bf16 [depth, 2, N, cap, head_dim] (`DecodeCtx.gen`): row b of every layer's K and V becomes row parent[b], in place, at
+    the positions below t (lap_decode_beam_reorder); nothing moves when the parents are the identity."""
+    _dreq(gen, torch.bfloat16, "gen")
+    if gen.dim() != 5 or gen.shape[1] != 2 or gen.shape[4] % 8:
+        raise TypeError(f"decode_beam_reorder: gen [depth, 2, N, cap, head_dim], head_dim a multiple of 8, got {tuple(gen.shape)}")
+    depth, _, N, cap, HD = gen.shape
+    _beam_req("decode_beam_reorder", state, beam, N)
+    call("lap_decode_beam_reorder", _p(state), _p(beam), _p(gen), N, 2 * depth, cap, HD)

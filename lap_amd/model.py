@@ -694,7 +694,7 @@ class LAP:
     def sample_tokens(self, rng, observation, *, max_decoding_steps: int = 390, temperature: float = 0.0, collect=None,
                       decode: str = "eager", sampler: str = "host", decode_weights: str = "bf16", allowed_tokens=None,
                       return_logprobs: bool = False, num_samples=None, top_k=None, top_p=None, speculate=None, draft_tokens=None,
-                      grammar=None, jump_forward=None):
+                      grammar=None, jump_forward=None, num_beams=None, early_stop: bool = True):
         """lap.py:678-766 (LAP_AR serving mode): VLM-only prefill, then single-token decode until every sample has emitted
         EOS or `max_decoding_steps` tokens; returns int32 [B, max_decoding_steps] (zeros after the stop).
 
@@ -803,13 +803,25 @@ class LAP:
         t + r from the state the rows before it led to (lap_decode_grammar_spec_finish: the single-row finish's bits, row after
         row), so tokens and log-probabilities are those of the call without `jump_forward`, sampled or greedy, whatever the draft;
         `last_spec_stats` = (steps, drafts accepted).  Composes with return_logprobs, decode_weights and temperature > 0.  The
-        reference has no such option."""
+        reference has no such option.
+
+        num_beams: beam search.  None (default): everything above, unchanged.  num_beams=N, 1 <= N <= 8 (an observation of batch 1,
+        temperature 0, decode "fused" or "eager"; sampler="device", num_samples, top_k / top_p, speculate, grammar, jump_forward
+        and collect raise ValueError from `beam.check_num_beams`): the deterministic search for the most probable answer.  The
+        prefix is prefilled once and shared by N rows that advance in lockstep; at every step each alive beam offers its N most
+        probable tokens, and the N candidates with the largest sum of token log-probabilities become the beams, in rank order
+        (lap_amd/beam.py states the rules; csrc/decode_beam.hip runs them on the fused route, `decode="eager"` is a second
+        implementation on the host).  early_stop (default True): the search ends when the rank-0 beam has finished, which no alive
+        beam can pass under the sum score; False: it runs until every beam has finished or the budget is spent.  Returns the
+        rank-0 beam as int32 [1, max_decoding_steps] (with return_logprobs also its token log-probabilities);
+        `ar_decode.beam_decode_fused` / `beam_decode_eager` return all beams.  num_beams=1 is the greedy decode.  Composes with
+        allowed_tokens, decode_weights and return_logprobs.  The reference has no such option."""
         from lap_amd import ar_decode       # (it imports this module)
         return ar_decode.sample_tokens(self, rng, observation, max_decoding_steps=max_decoding_steps, temperature=temperature,
                                        collect=collect, decode=decode, sampler=sampler, decode_weights=decode_weights,
                                        allowed_tokens=allowed_tokens, return_logprobs=return_logprobs, num_samples=num_samples,
                                        top_k=top_k, top_p=top_p, speculate=speculate, draft_tokens=draft_tokens, grammar=grammar,
-                                       jump_forward=jump_forward)
+                                       jump_forward=jump_forward, num_beams=num_beams, early_stop=early_stop)
 
     DECODE_WEIGHTS = ("bf16", "fp8", "fp8_layers")
     last_spec_stats = None      # (verify steps, drafts accepted) of the last `sample_tokens(speculate=S)` or `(jump_forward=S)` request

@@ -135,11 +135,28 @@ class GraphedTokenDecoder:
     The step graph is captured on steps of S rows that are driven by device state alone (the automaton state, the reference
     buffer, the sampling words), so one capture serves greedy and sampled requests and any `draft_tokens`; a call returns what the
     decoder without it returns, log-probabilities included, and `last_stats` = (verify_steps, accepted).  Composes with sampling=,
-    weights= and logprobs=."""
+    weights= and logprobs=.
+
+    num_beams=N (1 <= N <= 8; batch_size 1, greedy: sampling=, num_samples=, filtering=, speculate=, grammar= and jump_forward= raise
+    ValueError from `beam.check_num_beams`), early_stop=: `sample_tokens`' beam search.  The prefill graph runs at B = 1, copies its
+    prefix to N rows and resets the beam buffer with a device copy; the step graph runs the beam step at B = N, so one capture
+    serves every request.  A call returns the rank-0 beam ([1, steps] tokens, with logprobs=True also its log-probabilities);
+    `last_beams` = (tokens [N, steps], logprobs [N, steps], scores [N]) of the call.  Composes with weights=, allowed_tokens= and
+    logprobs=."""
 
     def __init__(self, model: LAP, batch_size: int = 1, max_decoding_steps: int = 390, prompt_len: int | None = None,
                  steps_per_replay: int = 8, sampling: bool = False, weights: str = "bf16", allowed_tokens=None,
-                 logprobs: bool = False, num_samples=None, filtering: bool = False, speculate=None, grammar=None, jump_forward=None):
+                 logprobs: bool = False, num_samples=None, filtering: bool = False, speculate=None, grammar=None, jump_forward=None,
+                 num_beams=None, early_stop: bool = True):
+        self.NB = None
+        self.early_stop = bool(early_stop)
+        self.last_beams = None
+        if num_beams is not None:
+            from lap_amd.beam import check_num_beams
+
+            self.NB = check_num_beams(num_beams, batch_size, temperature=1.0 if sampling else 0.0, num_samples=num_samples,
+                                      top_k=0 if filtering else None, speculate=speculate, grammar=grammar, jump_forward=jump_forward)
+            ar_decode.check_fused_decode(model, self.NB)
         self.grammar = None
         host = None
         if grammar is not None:
@@ -202,12 +219,12 @@ class GraphedTokenDecoder:
 
     def _prefill(self):
         pre = ar_decode.prefill(self.model, self.obs)
-        if self.N is not None:
-            pre = ar_decode.replicate_prefill(pre, self.N)
+        if self.N is not None or self.NB is not None:
+            pre = ar_decode.replicate_prefill(pre, self.N or self.NB)
         if self.ctx is None:
             self.ctx = ar_decode.DecodeCtx(self.model, pre.B, pre.Pn, self.max_steps, self.sampling, self.weights,
                                            allowed=self.allowed, logprobs=self.logprobs, filtering=self.filtering, speculate=self.S,
-                                           grammar=self.grammar, jump_forward=self.J)
+                                           grammar=self.grammar, jump_forward=self.J, beams=self.NB, early_stop=self.early_stop)
         self.ctx.first_token(pre)
 
     def _steps(self):
@@ -262,6 +279,10 @@ class GraphedTokenDecoder:
             self.g_step.replay()
         if self.S is not None or self.J is not None:
             self.last_stats = self.ctx.stats()
+        if self.NB is not None:             # all beams are kept; the answer is the rank-0 beam, as a batch of 1
+            self.last_beams = self.ctx.beam_result()
+            tokens, logp, _ = self.last_beams
+            return (tokens[:1].clone(), logp[:1].clone()) if self.logprobs else tokens[:1].clone()
         if self.logprobs:
             return self.ctx.out.clone(), self.ctx.logp.clone()
         return self.ctx.out.clone()
@@ -450,7 +471,22 @@ class ARPolicy:
         if self._select not in ("sum", "mean"):
             raise ValueError(f"ARPolicy: select must be 'sum' or 'mean', got {self._select!r}")
         self._num_samples = self._sample_kwargs.get("num_samples")
-        self._logprobs = bool(self._sample_kwargs.get("return_logprobs", False)) or self._num_samples is not None
+        # sample_kwargs["num_beams"] = N selects beam search (greedy; decode "fused", the default here, or "eager"): the policy
+        # answers with the beam `sampling.select_best` picks under "select", reports all N under "candidates" in best-of-N's layout,
+        # and searches with early_stop=False under "mean" (a longer beam may then win).  "allowed_tokens" and "decode_weights" compose.
+        self._num_beams = self._sample_kwargs.pop("num_beams", None)
+        self._beam_scores = None        # the device scores of the last request's beams (-inf: a padding beam)
+        if self._num_beams is not None:
+            from lap_amd.beam import check_num_beams
+
+            kw = self._sample_kwargs
+            check_num_beams(self._num_beams, 1, decode=kw.setdefault("decode", "fused"), temperature=kw.get("temperature", 0.0),
+                            sampler=kw.get("sampler", "host"), num_samples=self._num_samples, top_k=kw.get("top_k"), top_p=kw.get("top_p"),
+                            speculate=kw.get("speculate"), grammar=kw.get("grammar"), jump_forward=kw.get("jump_forward"),
+                            collect=kw.get("collect"))
+            kw.pop("return_logprobs", None)
+        self._logprobs = (bool(self._sample_kwargs.get("return_logprobs", False)) or self._num_samples is not None
+                          or self._num_beams is not None)
         if self._num_samples is not None:
             self._sample_kwargs.setdefault("decode", "fused")
             ar_decode.check_num_samples(self._num_samples, 1, decode=self._sample_kwargs["decode"],
@@ -474,8 +510,9 @@ class ARPolicy:
                             temperature=self._sample_kwargs.get("temperature", 0.0), return_logprobs=self._logprobs,
                             num_samples=self._num_samples, top_k=self._sample_kwargs.get("top_k"), top_p=self._sample_kwargs.get("top_p"),
                             collect=self._sample_kwargs.get("collect"))
-        if use_graph and base.model.decode_supported(self._num_samples or 1):
+        if use_graph and base.model.decode_supported(self._num_samples or self._num_beams or 1):
             self._decoder = GraphedTokenDecoder(base.model, 1, self._sample_kwargs.get("max_decoding_steps", 390),
+                                                num_beams=self._num_beams, early_stop=self._select != "mean",
                                                 sampling=self._device_sampler and self._speculate is None, weights=weights,
                                                 allowed_tokens=self._sample_kwargs.get("allowed_tokens"),
                                                 logprobs=self._logprobs, num_samples=self._num_samples,
@@ -500,7 +537,10 @@ class ARPolicy:
         spec_stats = None
         if (self._decoder is not None and (temperature <= 0.0 or self._device_sampler)
                 and self._sample_kwargs.get("decode", "eager") in ("eager", "fused") and graph_compatible(self._decoder.obs, o)):
-            if self._speculate is not None:
+            if self._num_beams is not None:
+                self._decoder(o)
+                tokens, self._beam_scores = self._decoder.last_beams[:2], self._decoder.last_beams[2].cpu().numpy()
+            elif self._speculate is not None:
                 tokens = self._decoder(o, draft_tokens=self._prev_tokens)
                 spec_stats = self._decoder.last_stats
             elif self._jump is not None:
@@ -510,6 +550,8 @@ class ARPolicy:
             else:
                 tokens = (self._decoder(o, temperature=temperature, seed=self._calls, **self._filter) if self._device_sampler
                           else self._decoder(o))
+        elif self._num_beams is not None:
+            tokens = self._beams(o)
         elif self._drafting:
             tokens = base.model.sample_tokens(self._calls, o, draft_tokens=self._prev_tokens, **self._sample_kwargs)
             spec_stats = base.model.last_spec_stats
@@ -525,8 +567,10 @@ class ARPolicy:
 
             tokens, logp = (t.cpu().numpy() for t in tokens)
             eos = base.model.EOS_TOKEN
+            if self._num_beams is not None:       # a padding beam (fewer than N candidates ever existed) is no answer: -inf throughout
+                logp = np.where(np.isfinite(self._beam_scores)[:, None], logp, -np.inf)
             seq = sampling.sequence_logprob(tokens, logp, eos)
-            if self._num_samples is not None:     # the answer is one candidate, as a batch of 1; all of them are reported
+            if self._num_samples is not None or self._num_beams is not None:     # the answer is one candidate, as a batch of 1; all of them are reported
                 extra["candidates"] = {"tokens": tokens, "logprob": seq}
                 best = sampling.select_best(tokens, logp, eos, self._select)
                 tokens, logp, seq = tokens[best:best + 1], logp[best:best + 1], seq[best:best + 1]
@@ -541,6 +585,22 @@ class ARPolicy:
         if spec_stats is not None:
             out["policy_timing"] |= {"spec_steps": spec_stats[0], "spec_accepted": spec_stats[1]}
         return out
+
+    def _beams(self, o):
+        """All beams of a request off the graph: (tokens [N, steps], logprobs [N, steps]) through the route "decode" names."""
+        kw, m = self._sample_kwargs, self._base.model
+        N = self._num_beams
+        m_kw = dict(max_decoding_steps=kw.get("max_decoding_steps", 390), early_stop=self._select != "mean")
+        allowed = ar_decode.allowed_set(m, kw["allowed_tokens"]).ids if kw.get("allowed_tokens") is not None else None
+        weights = kw.get("decode_weights", "bf16")
+        with m._serving_weights():
+            if kw.get("decode", "fused") == "fused":
+                ar_decode.check_fused_decode(m, N)
+                tok, logp, scores = ar_decode.beam_decode_fused(m, o, N, weights=weights, allowed=allowed, **m_kw)
+            else:
+                tok, logp, scores = ar_decode.beam_decode_eager(m, o, N, allowed=allowed, **m_kw)
+        self._beam_scores = scores.cpu().numpy()
+        return tok, logp
 
     def infer(self, obs: dict, *, noise=None) -> dict:
         return self.infer_reasoning(obs)

@@ -27,6 +27,10 @@ sampling graph.
 rows, next to one sampled row with log-probabilities on the same kernels, and both prefill graphs (the N-row one ends with the copies).
 The fused best-of-N figure subtracts the plain batch-1 prefill, so the copies to N rows and the allocation of the N-row context are
 spread into its ms per token; the graphed figures subtract their own prefill graph and are the ones to quote.
+--num-beams N [N ...] adds beam search (`num_beams=N`) beside `num_samples=N` at the same N: both graphed, in this process, taking
+turns; ms per step of each (mean and [min, max]) after their own prefill graphs, their ratio, the device time of the three beam
+launches on their own (events round single launches; the reorder at half the budget with every row moving), and how many steps of
+a decode had a non-identity reorder.
 --speculate S [S ...] adds exact speculative decoding (`speculate=S`) for bf16 and every --weights value, in the same process as
 the plain graph of those weights: a GraphedTokenDecoder(speculate=S) called with the answer itself as the draft (full acceptance)
 and without a draft (zero acceptance, the price of a wrong guess), each as the mean and [min, max] of the timed repeats; ms per
@@ -74,6 +78,7 @@ ap.add_argument("--allowed", type=int, default=0, help="> 0: also measure constr
 ap.add_argument("--logprobs", action="store_true", help="also measure greedy decoding that returns token log-probabilities")
 ap.add_argument("--num-samples", type=int, default=0, help="N > 0: also measure best-of-N (N rows from one batch-1 prefill); "
                 "sampled at --temperature, or at 1.0 when that is 0")
+ap.add_argument("--num-beams", type=int, nargs="+", default=[], help="also measure beam search (num_beams=N) beside best-of-N at the same N")
 ap.add_argument("--top-k", type=int, default=0, help="with --temperature: also measure filtered sampled decoding (top_k)")
 ap.add_argument("--top-p", type=float, default=1.0, help="with --temperature: also measure filtered sampled decoding (top_p)")
 ap.add_argument("--grammar", choices=["verbose"], default=None, help="also measure grammar-constrained decoding (verbose-with-rotation)")
@@ -248,6 +253,52 @@ if a.num_samples > 0:   # N rows from one batch-1 prefill against one sampled ro
         "graphed_ms_per_token_over_one_row": round(per(t_ngraph, t_npre) / per(t_1graph, t_1pre), 4),
         "one_row_graphed_prefill_ms": round(t_1pre, 3), "graphed_prefill_ms": round(t_npre, 3),
         "distinct_rows": len({tuple(r) for r in ntok.tolist()})}}
+beams = {}
+if a.num_beams:     # the beam step against the num_samples=N step at equal batch width: graphed, one process, the decoders taking turns
+    def launch_us(fn, reset, n=50):
+        """Median device time of one launch of `fn` (events round it), `reset` before each; microseconds."""
+        ts = []
+        for _ in range(n + 5):
+            reset()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); fn(); e1.record()
+            e1.synchronize()
+            ts.append(e0.elapsed_time(e1) * 1e3)
+        return round(sorted(ts[5:])[n // 2], 2)
+
+    for NB in a.num_beams:
+        bdec = GraphedTokenDecoder(model, 1, N, num_beams=NB, logprobs=True).capture()
+        ndec = GraphedTokenDecoder(model, 1, N, sampling=True, num_samples=NB).capture()
+        runs = {"beam": [], "best_of": []}
+        pre = {"beam": timeit(lambda: bdec.g_prefill.replay(), a.reps), "best_of": timeit(lambda: ndec.g_prefill.replay(), a.reps)}
+        for _ in range(max(a.reps, 3)):     # in turns, so that drift hits both alike
+            runs["beam"].append(per(timeit(lambda: bdec(o), 1), pre["beam"]))
+            runs["best_of"].append(per(timeit(lambda: ndec(o, temperature=1.0, seed=1), 1), pre["best_of"]))
+        bdec(o)
+        reorders = bdec.ctx.beam_reorders()
+        ctx = bdec.ctx
+        st, bw = ctx.state.clone(), ctx.beam.clone()
+        st0, bw0 = ctx.state.clone(), ctx.beam_init.clone()
+        st0[0], st0[1] = N // 2, 0                                  # mid decode, not done
+        bw0[:NB] = torch.linspace(0, -1, NB).view(torch.int32) if NB > 1 else bw0[:NB]
+        bw0[16:16 + NB] = torch.roll(torch.arange(NB, dtype=torch.int32), 1)     # every row moves
+
+        def reset():
+            st.copy_(st0); bw.copy_(bw0)
+
+        out, lp = ctx.out.clone(), ctx.logp.clone()
+        mean = lambda xs: sum(xs) / len(xs)
+        beams[f"N{NB}"] = {
+            "beam_ms_per_step": round(mean(runs["beam"]), 4), "beam_ms_per_step_min_max": [round(min(runs["beam"]), 4), round(max(runs["beam"]), 4)],
+            "num_samples_ms_per_step": round(mean(runs["best_of"]), 4),
+            "num_samples_ms_per_step_min_max": [round(min(runs["best_of"]), 4), round(max(runs["best_of"]), 4)],
+            "beam_over_num_samples": round(mean(runs["beam"]) / mean(runs["best_of"]), 4),
+            "beam_prefill_ms": round(pre["beam"], 3), "num_samples_prefill_ms": round(pre["best_of"], 3),
+            "topn_us": launch_us(lambda: hip.decode_beam_topn(st, bw, ctx.logits, ctx.cand_logp, ctx.cand_id, N), reset),
+            "select_us": launch_us(lambda: hip.decode_beam_select(st, bw, ctx.cand_logp, ctx.cand_id, out, lp, cfg.vocab_size, -1), reset),
+            "reorder_us_at_half_budget_every_row_moving": launch_us(lambda: hip.decode_beam_reorder(st, bw, ctx.gen), reset),
+            "steps": N, "steps_with_a_non_identity_reorder": reorders}
+        del bdec, ndec
 speculative = {}
 if a.speculate:
     def spread(fn):
@@ -408,4 +459,4 @@ print(json.dumps({
     "algorithmic_bytes_per_token": bytes_tok, "floor_ms_per_token_at_6.29TBps": round(bytes_tok / 6.29e12 * 1e3, 3),
     "achieved_GBps_graphed": round(bytes_tok / (g_ms * 1e-3) / 1e9, 1),
     "share_of_6.29TBps": round(bytes_tok / (g_ms * 1e-3) / 6.29e12, 3), "down_proj_kwaves": a.kwaves} | sampled | ({"weights": quant} if quant else {})
-    | ({"allowed": a.allowed, "constrained": constrained} if constrained else {}) | logprobs | best_of | ({"speculate": speculative} if speculative else {}) | grammar_res))
+    | ({"allowed": a.allowed, "constrained": constrained} if constrained else {}) | logprobs | best_of | ({"beams": beams} if beams else {}) | ({"speculate": speculative} if speculative else {}) | grammar_res))
