@@ -232,6 +232,9 @@ def _sample_beams(model: LAP, observation, num_beams, early_stop, *, max_decodin
                         collect=collect)
     if draft_tokens is not None:
         raise ValueError("sample_tokens: draft_tokens needs speculate=S")
+    grammar_host = None
+    if grammar is not None:
+        grammar_host = check_grammar(grammar, model.config.vocab_size, model.EOS_TOKEN, allowed_tokens=allowed_tokens)
     check_decode_weights(decode_weights)
     if decode_weights != "bf16" and decode != "fused":
         raise ValueError(f"sample_tokens: decode_weights={decode_weights!r} runs on the fused decode kernels only: pass decode=\"fused\"")
@@ -240,13 +243,15 @@ def _sample_beams(model: LAP, observation, num_beams, early_stop, *, max_decodin
     if decode == "fused":
         check_fused_decode(model, N)
     allowed = allowed_set(model, allowed_tokens).ids if allowed_tokens is not None else None
+    if grammar is not None:
+        grammar = grammar_on_device(model, grammar, grammar_host)
     with model._serving_weights():
         if decode == "fused":
             tokens, logp, _ = beam_decode_fused(model, observation, N, max_decoding_steps=max_decoding_steps, early_stop=early_stop,
-                                                weights=decode_weights, allowed=allowed)
+                                                weights=decode_weights, allowed=allowed, grammar=grammar)
         else:
             tokens, logp, _ = beam_decode_eager(model, observation, N, max_decoding_steps=max_decoding_steps, early_stop=early_stop,
-                                                allowed=allowed)
+                                                allowed=allowed, grammar=grammar)
     return (tokens[:1].contiguous(), logp[:1].contiguous()) if return_logprobs else tokens[:1].contiguous()
 
 
@@ -417,10 +422,13 @@ def _sample_eager(model: LAP, rng, observation, *, max_decoding_steps: int, temp
     return (out, logp) if logprobs else out
 
 
-def beam_decode_eager(model: LAP, observation, N: int, *, max_decoding_steps: int, early_stop: bool = True, allowed=None, on_step=None):
+def beam_decode_eager(model: LAP, observation, N: int, *, max_decoding_steps: int, early_stop: bool = True, allowed=None, on_step=None,
+                      grammar=None):
     """Beam search on the eager step, the second implementation beside `beam_decode_fused` (call it under `_serving_weights`): the
     batch-1 prefill replicated to N rows, per-step f32 logits from the generic launches, `beam.beam_step` on the host in float64,
     `index_select` by parent on the generated K / V.  allowed: int32 device ids.  on_step: `beam.beam_search`'s hook.
+    grammar: a DeviceAutomaton (not with allowed): every row is masked to its state's set and stepped by `beam.grammar_beam_step`
+    on the host (`beam.grammar_beam_search`; on_step then also receives the states before the step).
     Returns (tokens int32 [N, cap], logp f32 [N, cap], scores f32 [N]) on the device, in rank order."""
     import numpy as np
 
@@ -447,23 +455,31 @@ def beam_decode_eager(model: LAP, observation, N: int, *, max_decoding_steps: in
             lg = lg.masked_fill(outside, float("-inf"))
         return lg.cpu().numpy()
 
-    def reorder(t, logits, scores, finished, res):
+    def reorder(t, logits, scores, finished, res, *states):
         if on_step is not None:
-            on_step(t, logits, scores, finished, res)
+            on_step(t, logits, scores, finished, res, *states)
         par = torch.from_numpy(res[0]).to(dev).long()
         state["gen"] = [(gk, gv) if gk is None else (gk.index_select(0, par), gv.index_select(0, par)) for gk, gv in state["gen"]]
 
-    tokens, logp, scores = bm.beam_search(logits_fn, N, max_decoding_steps, model.EOS_TOKEN, early_stop, on_step=reorder)
+    if grammar is not None:
+        if allowed is not None:
+            raise ValueError("grammar does not combine with allowed_tokens: the union of the automaton's edges replaces the set")
+        tokens, logp, scores, _ = bm.grammar_beam_search(logits_fn, N, max_decoding_steps, model.EOS_TOKEN, grammar.host, early_stop,
+                                                         on_step=reorder)
+    else:
+        tokens, logp, scores = bm.beam_search(logits_fn, N, max_decoding_steps, model.EOS_TOKEN, early_stop, on_step=reorder)
     return (torch.from_numpy(tokens).to(dev), torch.from_numpy(logp.astype(np.float32)).to(dev),
             torch.from_numpy(scores.astype(np.float32)).to(dev))
 
 
 def beam_decode_fused(model: LAP, observation, N: int, *, max_decoding_steps: int, early_stop: bool = True, weights: str = "bf16",
-                      allowed=None):
+                      allowed=None, grammar=None):
     """Beam search on the fused step (call it under `_serving_weights`): `replicate_prefill` to N rows and a `DecodeCtx(beams=N)`.
+    grammar: a DeviceAutomaton on the model's device (not with allowed): the beams stay inside the automaton.
     Returns `DecodeCtx.beam_result()`: (tokens int32 [N, cap], logp f32 [N, cap], scores f32 [N]) in rank order."""
     pre = replicate_prefill(prefill(model, observation), N)
-    ctx = DecodeCtx(model, N, pre.Pn, max_decoding_steps, weights=weights, allowed=allowed, beams=N, early_stop=early_stop)
+    ctx = DecodeCtx(model, N, pre.Pn, max_decoding_steps, weights=weights, allowed=allowed, beams=N, early_stop=early_stop,
+                    grammar=grammar)
     ctx.first_token(pre)
     n = DECODE_STEPS_PER_CHECK
     for _ in range((max_decoding_steps - 1 + n - 1) // n):
@@ -544,12 +560,16 @@ class DecodeCtx:
     the layers on the S positions, the plain SUBSET head over the union on the S rows, and lap_decode_grammar_spec_finish, which
     draws the rows in sequence with the single-row finish's bits and accepts the longest verified run.  Tokens and
     log-probabilities are those of the grammar context without it; `stats` reads the counters.
-    beams=N (B = N; greedy, not with filtering, speculate, grammar or jump_forward; composes with weights and allowed): the rows are
+    beams=N (B = N; greedy, not with filtering, speculate or jump_forward; composes with weights, and with allowed or grammar): the rows are
     the beams of one beam search (lap_amd/beam.py, csrc/decode_beam.hip).  The context owns the beam buffer (scores, finished,
     parent, the `early_stop` flag; reset by `first_token` with a device copy that a captured prefill replays), the [N, V] f32 logits
     of the step, the [N, N] candidates and `logp`.  Its LM head is the plain greedy one (plain / SUBSET / fp8), which stores its
     logits; lap_decode_beam_topn and lap_decode_beam_select finish the step, and `step` starts with lap_decode_beam_reorder, which
-    moves the generated K / V rows to the parents the last select chose.  `beam_result` hands out all beams."""
+    moves the generated K / V rows to the parents the last select chose.  `beam_result` hands out all beams.
+    beams=N with grammar=DeviceAutomaton: the beams are the most probable sentences of the automaton (`beam.grammar_beam_step`).  The
+    context also owns `gstate` [N] (every beam's automaton state) and `cand_next`; the head is the SUBSET head over the automaton's
+    union, lap_decode_beam_grammar_topn reads only the edges of every row's state and lap_decode_beam_grammar_select carries the
+    states along the parent permutation."""
 
     def __init__(self, model: LAP, B: int, Pn: int, cap: int, sampling: bool = False, weights: str = "bf16", allowed=None,
                  logprobs: bool = False, filtering: bool = False, speculate=None, grammar=None, jump_forward=None, beams=None,
@@ -629,11 +649,13 @@ class DecodeCtx:
         if self.beams is not None:
             self.beam_init = hip.decode_beam_init_words(B, early_stop, dev)
             self.beam = self.beam_init.clone()
-            self.logits = torch.empty((B, model.config.vocab_size), dtype=torch.float32, device=dev)
-            if allowed is not None:
-                self.logits.fill_(float("-inf"))
+            if grammar is None:         # (a grammar context has its logits already: -inf outside the union)
+                self.logits = torch.empty((B, model.config.vocab_size), dtype=torch.float32, device=dev)
+                if allowed is not None:
+                    self.logits.fill_(float("-inf"))
             self.cand_logp = torch.zeros((B, B), dtype=torch.float32, device=dev)
             self.cand_id = torch.full((B, B), -1, dtype=torch.int32, device=dev)
+            self.cand_next = torch.full((B, B), -1, dtype=torch.int32, device=dev) if grammar is not None else None
         self.prefix = None
         self.kinfo = None
 
@@ -714,6 +736,14 @@ class DecodeCtx:
             hi, lo, kw = m.W("llm/embed"), m.ps.w16lo("llm/embed"), {}
         if self.allowed is not None:      # the LM head streams the allowed rows only
             kw["ids"] = self.allowed
+        if self.beam is not None and self.grammar is not None:    # the head over the union, then the top-N over every row's state
+            g = self.grammar
+            hip.decode_lm_head(self.state, x, m.F("llm/final_norm"), hi, lo, self.pval, self.pidx, self.logits, **(kw | {"ids": g.union}))
+            hip.decode_beam_grammar_topn(self.state, self.beam, self.gstate, g.offsets, g.ids, g.next, self.logits, self.cand_logp,
+                                         self.cand_id, self.cand_next, self.cap)
+            hip.decode_beam_grammar_select(self.state, self.beam, self.gstate, self.cand_logp, self.cand_id, self.cand_next, self.out,
+                                           self.logp, m.config.vocab_size, m.EOS_TOKEN)
+            return
         if self.beam is not None:         # the plain head stores the logits, topn and select finish the step
             hip.decode_lm_head(self.state, x, m.F("llm/final_norm"), hi, lo, self.pval, self.pidx, self.logits, **kw)
             hip.decode_beam_topn(self.state, self.beam, self.logits, self.cand_logp, self.cand_id, self.cap)

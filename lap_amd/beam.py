@@ -1,5 +1,5 @@
 """Beam search over the rows of one fused LAP_AR decode batch, in plain numpy: the specification of csrc/decode_beam.hip
-(lap_decode_beam_topn / _select / _reorder) and the host half of the eager route of `LAP.sample_tokens(num_beams=N)`.
+(lap_decode_beam_topn / _select / _reorder and their grammar forms) and the host half of the eager route of `LAP.sample_tokens(num_beams=N)`.
 
 The rules (every number float64 unless said otherwise):
 * The N beams advance in lockstep, one token per step; `scores[b]` is the sum of beam b's token log-probabilities, `finished[b]`
@@ -16,6 +16,11 @@ The rules (every number float64 unless said otherwise):
 * A beam that emits `eos`, or whose parent was finished, is finished.
 * done: every beam is finished, or t + 1 >= cap, or (early_stop) the rank-0 beam is finished: scores never rise, so no alive
   beam can pass it under the sum score.
+
+Under a grammar (`grammar_beam_step` / `grammar_beam_search`; lap_decode_beam_grammar_topn / _grammar_select) beam b also carries the
+state states[b] of a `grammar.TokenAutomaton`, and its row is read with -inf outside `automaton.allowed(states[b])`: the
+log-probabilities are over that state's set, the rules above apply to the masked rows, and a beam's state moves along the edge of its
+token (a finished parent's and a padding beam's state stays).  A state outside [0, Q), or a segment outside [0, E], offers nothing.
 """
 from __future__ import annotations
 
@@ -105,6 +110,63 @@ def beam_search(logits_fn, N: int, cap: int, eos: int, early_stop: bool = True, 
     return tokens, logp, scores
 
 
+def grammar_masked(logits, states, automaton):
+    """f32 [N, V]: row b of `logits` with -inf outside `automaton.allowed(states[b])`; all -inf for a state outside [0, Q) or a
+    segment outside [0, E]: what `grammar_beam_step` hands to `beam_step`."""
+    lg = np.asarray(logits, dtype=np.float32)
+    masked = np.full(lg.shape, -np.inf, dtype=np.float32)
+    Q, E = automaton.num_states, automaton.num_edges
+    for b, q in enumerate(np.asarray(states).reshape(-1).tolist()):
+        if not 0 <= q < Q:
+            continue
+        lo, hi = int(automaton.offsets[q]), int(automaton.offsets[q + 1])
+        if lo < 0 or hi > E or hi < lo:
+            continue
+        ids = automaton.ids[lo:hi]
+        ids = ids[(ids >= 0) & (ids < lg.shape[1])]
+        masked[b, ids] = lg[b, ids]
+    return masked
+
+
+def grammar_beam_step(logits, scores, finished, states, automaton, t: int, cap: int, eos: int, early_stop: bool = True):
+    """`beam_step` of beams that are each in a state of `automaton` (states int [N]), on the rows of `grammar_masked`.  Returns
+    `beam_step`'s tuple and new_states int32 [N]: states[parent[r]] when that parent was finished or beam r is padding (score -inf;
+    its parent is its own index), else `automaton.step(states[parent[r]], token[r])`."""
+    states = np.asarray(states).reshape(-1).astype(np.int64)
+    finished = np.asarray(finished, dtype=bool)
+    if states.shape != np.asarray(scores).shape:
+        raise ValueError(f"grammar_beam_step: states [N] beside scores [N]; got {states.shape}, {np.asarray(scores).shape}")
+    res = beam_step(grammar_masked(logits, states, automaton), scores, finished, t, cap, eos, early_stop)
+    parent, token, _, new_scores = res[:4]
+    new_states = np.zeros(states.shape, dtype=np.int32)
+    for r in range(states.shape[0]):
+        q = int(states[parent[r]])
+        keep = bool(finished[parent[r]]) or not new_scores[r] > -np.inf
+        new_states[r] = q if keep else automaton.step(q, int(token[r]))
+    return res + (new_states,)
+
+
+def grammar_beam_search(logits_fn, N: int, cap: int, eos: int, automaton, early_stop: bool = True, on_step=None):
+    """`beam_search` under `automaton`: every beam starts in state 0 and `grammar_beam_step` moves them.  Returns (tokens int32
+    [N, cap], token_logp float64 [N, cap], scores float64 [N], states int32 [N]) in rank order.
+    on_step(t, masked_logits, scores, finished, result, states) is called after every step with the states before it."""
+    scores, finished = initial(N)
+    states = np.zeros((N,), dtype=np.int32)
+    tokens = np.zeros((N, cap), dtype=np.int32)
+    logp = np.zeros((N, cap))
+    t, done = 0, cap < 1
+    while not done:
+        logits = np.asarray(logits_fn(tokens[:, :t].copy()))
+        res = grammar_beam_step(logits, scores, finished, states, automaton, t, cap, eos, early_stop)
+        if on_step is not None:
+            on_step(t, grammar_masked(logits, states, automaton), scores, finished, res[:6], states)
+        parent, tok, lp, scores, finished, done, states = res
+        tokens, logp = tokens[parent], logp[parent]
+        tokens[:, t], logp[:, t] = tok, lp
+        t += 1
+    return tokens, logp, scores, states
+
+
 def step_gaps(logits, scores, finished):
     """(row_gap, select_gap) of a step in the float64 specification: the smallest distance, over the alive rows that contribute,
     between the N-th and the (N+1)-th log-probability of a row, and the distance between the N-th and the (N+1)-th candidate
@@ -149,8 +211,12 @@ def check_num_beams(num_beams, batch: int, *, decode: str = "fused", temperature
         raise ValueError("num_beams is deterministic: top_k / top_p must be None")
     if speculate is not None:
         raise ValueError("num_beams does not combine with speculate")
-    if grammar is not None:
-        raise ValueError("num_beams does not combine with grammar")
+    if grammar is not None:         # (the automaton itself is checked by `ar_decode.check_grammar`, which also rejects allowed_tokens)
+        from lap_amd.grammar import DeviceAutomaton, TokenAutomaton
+
+        if not isinstance(grammar.host if isinstance(grammar, DeviceAutomaton) else grammar, TokenAutomaton):
+            raise ValueError(f"num_beams combines with grammar= only as a grammar.TokenAutomaton (or its to_device form), got "
+                             f"{type(grammar).__name__}")
     if jump_forward is not None:
         raise ValueError("num_beams does not combine with jump_forward")
     if collect is not None:

@@ -7,7 +7,8 @@
 //   beam[24]      early_stop: done is also set when the rank-0 beam has finished
 //   beam[25]      steps whose parent permutation was not the identity (a counter for tools)
 // A decode starts from {0, -inf, ...}, nothing finished (`hip.decode_beam_init_words`; a device copy inside the prefill part).
-// Three kernels; each reads t = state[0] and done = state[1], returns at once when done is set, writes device state with plain
+// Three kernels (and, under a grammar, the two described where they stand: a topn over the edges of every row's automaton state and
+// the select that also moves that state); each reads t = state[0] and done = state[1], returns at once when done is set, writes device state with plain
 // per-lane stores, and never uses an id, a parent or a position outside its range as an address.
 //   topn     grid N, 1024 threads per row of stored f32 logits [N][V]: one pass forms the log-sum-exp over the entries > -inf
 //            (the pair (m, s) of csrc/decode.hip; a thread's entries in order, the lanes by a shfl_down tree, the waves in order)
@@ -33,6 +34,7 @@
 namespace {
 
 constexpr int BT = 256;                     // threads of the select and reorder blocks
+constexpr int GT = 256, GW = GT / 64;       // threads, waves of a grammar topn block
 constexpr int TT = 1024, TW = TT / 64;      // threads, waves of a topn block
 constexpr int TU = 8;                       // logits a topn thread loads before it works on them (independent loads in flight)
 constexpr int BEAM_MAX = 8;                 // rows of a fused decode
@@ -146,10 +148,119 @@ __global__ __launch_bounds__(TT) void beam_topn_kernel(const int* state, const i
   }
 }
 
+// One block of 256 threads per row, under a grammar: the row's candidates are the edges of the automaton state q = gstate[row] (the
+// CSR automaton of csrc/decode_grammar.hip), so the threads stride over that segment alone, gather logits[row][id] and form the
+// log-sum-exp over the segment in grammar_draw_row's order (a thread's entries in order, the lanes by a shfl_down tree, the four
+// waves in order).  A thread keeps its 8 best (logit, id, edge); N block-argmax rounds emit cand_logp, cand_id and cand_next =
+// next[edge].  q outside [0, Q), a segment outside [0, E] and an id outside [0, V) are never used as an address: such a row writes no
+// candidates (every id -1).  A finished row writes the one candidate (logp 0, id 0, next = its own state, which the select keeps).
+__global__ __launch_bounds__(GT) void beam_grammar_topn_kernel(const int* state, const int* beam, const int* gstate, const int* offsets,
+                                                               const int* ids, const int* next, int Q, int E, const float* logits, int V,
+                                                               int N, int cap, float* cand_logp, int* cand_id, int* cand_next) {
+  __shared__ float redv[GW], redm[GW], reds[GW], s_lse;
+  __shared__ int redi[GW], rede[GW];
+  if (state[1]) return;
+  const int t = state[0];
+  if (t < 0 || t >= cap) return;        // (the select kernel sets done)
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, row = blockIdx.x;
+  float* cl = cand_logp + row * N;
+  int* ci = cand_id + row * N;
+  int* cn = cand_next + row * N;
+  const float score = __int_as_float(beam[row]);
+  const int q = gstate[row];
+  if (!(score > -INFINITY) || beam[8 + row]) {      // (block-uniform) nothing, or the one candidate of a finished row
+    if (tid < N) {
+      const bool one = score > -INFINITY && tid == 0;
+      cl[tid] = one ? 0.f : -INFINITY;
+      ci[tid] = one ? 0 : -1;
+      cn[tid] = one ? q : -1;
+    }
+    return;
+  }
+  int lo = 0, hi = 0, bad = 0;
+  if (q >= 0 && q < Q) { lo = offsets[q]; hi = offsets[q + 1]; }
+  if (lo < 0 || hi > E || hi < lo) { bad = 1; lo = hi = 0; }
+  const float* x = logits + (long long)row * V;
+  float tv[BEAM_MAX];
+  int ti[BEAM_MAX], te[BEAM_MAX];
+#pragma unroll
+  for (int k = 0; k < BEAM_MAX; ++k) { tv[k] = -INFINITY; ti[k] = NO_ID; te[k] = -1; }
+  float m = -INFINITY, s = 0.f;
+  for (int e = lo + tid; e < hi; e += GT) {         // a thread's edges, hence its ids, ascend
+    const int id = ids[e];
+    if (id < 0 || id >= V) { bad = 1; continue; }
+    const float v = x[id];
+    if (!(v > -INFINITY)) continue;     // (-inf and NaN: outside the sum, no candidate)
+    lse_push(v, m, s);
+    if (better(v, id, tv[BEAM_MAX - 1], ti[BEAM_MAX - 1])) {
+      tv[BEAM_MAX - 1] = v; ti[BEAM_MAX - 1] = id; te[BEAM_MAX - 1] = e;
+#pragma unroll
+      for (int k = BEAM_MAX - 1; k > 0; --k) {
+        if (better(tv[k], ti[k], tv[k - 1], ti[k - 1])) {
+          const float fv = tv[k]; tv[k] = tv[k - 1]; tv[k - 1] = fv;
+          const int fi = ti[k]; ti[k] = ti[k - 1]; ti[k - 1] = fi;
+          const int fe = te[k]; te[k] = te[k - 1]; te[k - 1] = fe;
+        }
+      }
+    }
+  }
+  if (__syncthreads_or(bad)) {          // (block-uniform) a state, segment or id out of range: the row offers nothing
+    if (tid < N) { cl[tid] = -INFINITY; ci[tid] = -1; cn[tid] = -1; }
+    return;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float om = __shfl_down(m, o, 64), os = __shfl_down(s, o, 64);
+    lse_merge(om, os, m, s);
+  }
+  if (lane == 0) { redm[w] = m; reds[w] = s; }
+  __syncthreads();
+  if (tid == 0) {
+    for (int k = 1; k < GW; ++k) lse_merge(redm[k], reds[k], m, s);
+    s_lse = m > -INFINITY ? __fadd_rn(m, logf(s)) : -INFINITY;
+  }
+  __syncthreads();
+  const float lse = s_lse;
+  const bool usable = lse > -INFINITY && lse < INFINITY;        // (a NaN fails both)
+  for (int r = 0; r < N; ++r) {         // (block-uniform) round r: the best head of all threads' lists
+    float v = tv[0];
+    int i = ti[0], e = te[0];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(v, o, 64);
+      const int oi = __shfl_xor(i, o, 64), oe = __shfl_xor(e, o, 64);
+      if (better(ov, oi, v, i)) { v = ov; i = oi; e = oe; }
+    }
+    if (lane == 0) { redv[w] = v; redi[w] = i; rede[w] = e; }
+    __syncthreads();
+    v = redv[0]; i = redi[0]; e = rede[0];
+    for (int k = 1; k < GW; ++k)
+      if (better(redv[k], redi[k], v, i)) { v = redv[k]; i = redi[k]; e = rede[k]; }
+    if (e >= 0 && te[0] == e) {         // the one thread that owns edge e drops it
+#pragma unroll
+      for (int k = 0; k < BEAM_MAX - 1; ++k) { tv[k] = tv[k + 1]; ti[k] = ti[k + 1]; te[k] = te[k + 1]; }
+      tv[BEAM_MAX - 1] = -INFINITY; ti[BEAM_MAX - 1] = NO_ID; te[BEAM_MAX - 1] = -1;
+    }
+    if (tid == 0) {
+      const bool ok = usable && e >= 0;             // (e in [lo, hi), inside [0, E))
+      cl[r] = ok ? __fsub_rn(v, lse) : -INFINITY;
+      ci[r] = ok ? i : -1;
+      cn[r] = ok ? next[e] : -1;
+    }
+    __syncthreads();                    // (the partials are read before the next round writes them)
+  }
+}
+
+// GRAMMAR: the select of a grammar beam step.  cand_next[j] is the automaton state after candidate j; gstate[r] becomes the state of
+// beam r's parent when that parent had finished or beam r is padding (its parent is its own index), else the candidate's next
+// state.  The N old states are loaded before the barrier and stored after it.
+template <bool GRAMMAR>
 __global__ __launch_bounds__(BT) void beam_select_kernel(int* state, int* beam, const float* cand_logp, const int* cand_id, int N,
-                                                         int V, int* out, float* logp, int cap, int eos) {
+                                                         int V, int* out, float* logp, int cap, int eos, int* gstate,
+                                                         const int* cand_next) {
   __shared__ float c_s[BEAM_MAX * BEAM_MAX], c_lp[BEAM_MAX * BEAM_MAX], n_lp[BEAM_MAX], n_sc[BEAM_MAX];
   __shared__ int c_id[BEAM_MAX * BEAM_MAX], c_ok[BEAM_MAX * BEAM_MAX], n_par[BEAM_MAX], n_tok[BEAM_MAX], n_fin[BEAM_MAX];
+  __shared__ int n_nx[BEAM_MAX], n_keep[BEAM_MAX];
   const int tid = threadIdx.x;
   if (state[1]) return;
   const int t = state[0];
@@ -170,6 +281,9 @@ __global__ __launch_bounds__(BT) void beam_select_kernel(int* state, int* beam, 
     c_s[tid] = sc; c_lp[tid] = lp; c_id[tid] = id; c_ok[tid] = ok;
   }
   if (tid < BEAM_MAX) { n_par[tid] = tid; n_tok[tid] = 0; n_lp[tid] = 0.f; n_sc[tid] = -INFINITY; n_fin[tid] = 1; }
+  if constexpr (GRAMMAR) {
+    if (tid < BEAM_MAX) { n_nx[tid] = 0; n_keep[tid] = 1; }
+  }
   __syncthreads();
   if (tid < NN && c_ok[tid]) {
     const int b = tid / N, id = c_id[tid];
@@ -183,9 +297,15 @@ __global__ __launch_bounds__(BT) void beam_select_kernel(int* state, int* beam, 
     if (rank < N) {
       n_par[rank] = b; n_tok[rank] = id; n_lp[rank] = c_lp[tid]; n_sc[rank] = sc;
       n_fin[rank] = (beam[8 + b] || id == eos) ? 1 : 0;
+      if constexpr (GRAMMAR) { n_nx[rank] = cand_next[tid]; n_keep[rank] = beam[8 + b] ? 1 : 0; }
     }
   }
   __syncthreads();
+  int old_q = 0;
+  if constexpr (GRAMMAR) {
+    if (tid < N) old_q = gstate[n_par[tid]];        // (n_par in [0, N)) every old state is in a register ...
+    __syncthreads();                                // ... before the first is overwritten below
+  }
   int par[BEAM_MAX];
   bool ident = true;
 #pragma unroll
@@ -212,6 +332,7 @@ __global__ __launch_bounds__(BT) void beam_select_kernel(int* state, int* beam, 
     beam[8 + tid] = n_fin[tid];
     beam[16 + tid] = n_par[tid];
     state[8 + tid] = n_fin[tid];
+    if constexpr (GRAMMAR) gstate[tid] = n_keep[tid] ? old_q : n_nx[tid];
   }
   if (tid == 0) {
     int all = 1;
@@ -266,7 +387,31 @@ extern "C" int lap_decode_beam_topn(const int* state, const int* beam, const flo
 extern "C" int lap_decode_beam_select(int* state, int* beam, const float* cand_logp, const int* cand_id, int* out, float* logp, int N,
                                       int V, int cap, int eos_token, void* stream) {
   if (!state || !beam || !cand_logp || !cand_id || !out || !logp || N < 1 || N > BEAM_MAX || V < 1 || cap < 1) return LAP_ERR_ARG;
-  hipLaunchKernelGGL(beam_select_kernel, dim3(1), dim3(BT), 0, S_, state, beam, cand_logp, cand_id, N, V, out, logp, cap, eos_token);
+  hipLaunchKernelGGL(beam_select_kernel<false>, dim3(1), dim3(BT), 0, S_, state, beam, cand_logp, cand_id, N, V, out, logp, cap, eos_token,
+                     (int*)nullptr, (const int*)nullptr);
+  LAP_CHECK_LAUNCH();
+  return LAP_OK;
+}
+
+extern "C" int lap_decode_beam_grammar_topn(const int* state, const int* beam, const int* gstate, const int* offsets, const int* ids,
+                                            const int* next, int Q, int E, const float* logits, float* cand_logp, int* cand_id,
+                                            int* cand_next, int N, int V, int cap, void* stream) {
+  if (!state || !beam || !gstate || !offsets || !ids || !next || !logits || !cand_logp || !cand_id || !cand_next || Q < 1 || E < 1 ||
+      E > (1 << 30) || N < 1 || N > BEAM_MAX || V < 1 || V > (1 << 30) || cap < 1)
+    return LAP_ERR_ARG;
+  hipLaunchKernelGGL(beam_grammar_topn_kernel, dim3(N), dim3(GT), 0, S_, state, beam, gstate, offsets, ids, next, Q, E, logits, V, N, cap,
+                     cand_logp, cand_id, cand_next);
+  LAP_CHECK_LAUNCH();
+  return LAP_OK;
+}
+
+extern "C" int lap_decode_beam_grammar_select(int* state, int* beam, int* gstate, const float* cand_logp, const int* cand_id,
+                                              const int* cand_next, int* out, float* logp, int N, int V, int cap, int eos_token,
+                                              void* stream) {
+  if (!state || !beam || !gstate || !cand_logp || !cand_id || !cand_next || !out || !logp || N < 1 || N > BEAM_MAX || V < 1 || cap < 1)
+    return LAP_ERR_ARG;
+  hipLaunchKernelGGL(beam_select_kernel<true>, dim3(1), dim3(BT), 0, S_, state, beam, cand_logp, cand_id, N, V, out, logp, cap, eos_token,
+                     gstate, cand_next);
   LAP_CHECK_LAUNCH();
   return LAP_OK;
 }

@@ -257,6 +257,8 @@ SIGNATURES: dict[str, list] = {
     "lap_decode_beam_topn": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "lap_decode_beam_select": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "lap_decode_beam_reorder": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "lap_decode_beam_grammar_topn": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "lap_decode_beam_grammar_select": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
 }
 
 _fn = {}
@@ -1907,3 +1909,43 @@ def decode_beam_reorder(state, beam, gen):
     depth, _, N, cap, HD = gen.shape
     _beam_req("decode_beam_reorder", state, beam, N)
     call("lap_decode_beam_reorder", _p(state), _p(beam), _p(gen), N, 2 * depth, cap, HD)
+
+
+def _beam_cands(fn, N, cand_logp, cand_id, cand_next):
+    _dreq(cand_logp, torch.float32, "cand_logp"); _dreq(cand_id, torch.int32, "cand_id"); _dreq(cand_next, torch.int32, "cand_next")
+    if tuple(cand_logp.shape) != (N, N) or tuple(cand_id.shape) != (N, N) or tuple(cand_next.shape) != (N, N):
+        raise TypeError(f"{fn}: cand_logp / cand_id / cand_next [{N}, {N}], got {tuple(cand_logp.shape)}, {tuple(cand_id.shape)}, "
+                        f"{tuple(cand_next.shape)}")
+
+
+def decode_beam_grammar_topn(state, beam, gstate, offsets, ids, nxt, logits, cand_logp, cand_id, cand_next, cap):
+    """`decode_beam_topn` under a grammar (lap_decode_beam_grammar_topn; `beam.grammar_beam_step`): row b offers the N best edges of
+    its automaton state gstate[b] (int32 [N]) from the f32 `logits` [N, V] that the SUBSET head over the automaton's union stored,
+    with log-probabilities over that state's set; cand_next [N, N]: the state every candidate's edge leads to.  offsets, ids, nxt:
+    the int32 device CSR of `grammar.TokenAutomaton.to_device`."""
+    _dreq(logits, torch.float32, "logits"); _dreq(gstate, torch.int32, "gstate")
+    if logits.dim() != 2:
+        raise TypeError(f"decode_beam_grammar_topn: logits [N, V], got {tuple(logits.shape)}")
+    N, V = logits.shape
+    _beam_req("decode_beam_grammar_topn", state, beam, N)
+    _automaton_req("decode_beam_grammar_topn", offsets, ids, nxt)
+    if gstate.numel() != N:
+        raise TypeError(f"decode_beam_grammar_topn: gstate [{N}], got {tuple(gstate.shape)}")
+    _beam_cands("decode_beam_grammar_topn", N, cand_logp, cand_id, cand_next)
+    call("lap_decode_beam_grammar_topn", _p(state), _p(beam), _p(gstate), _p(offsets), _p(ids), _p(nxt), offsets.numel() - 1, ids.numel(),
+         _p(logits), _p(cand_logp), _p(cand_id), _p(cand_next), N, V, int(cap))
+
+
+def decode_beam_grammar_select(state, beam, gstate, cand_logp, cand_id, cand_next, out, logp, V, eos_token):
+    """`decode_beam_select` under a grammar (lap_decode_beam_grammar_select): also gstate[r] = the state of beam r after its token
+    (its parent's old state when that parent had finished or beam r is padding)."""
+    _dreq(out, torch.int32, "out"); _dreq(logp, torch.float32, "logp"); _dreq(gstate, torch.int32, "gstate")
+    if out.dim() != 2 or tuple(logp.shape) != tuple(out.shape):
+        raise TypeError(f"decode_beam_grammar_select: out [N, cap] with logp beside it, got {tuple(out.shape)}, {tuple(logp.shape)}")
+    N, cap = out.shape
+    _beam_req("decode_beam_grammar_select", state, beam, N)
+    if gstate.numel() != N:
+        raise TypeError(f"decode_beam_grammar_select: gstate [{N}], got {tuple(gstate.shape)}")
+    _beam_cands("decode_beam_grammar_select", N, cand_logp, cand_id, cand_next)
+    call("lap_decode_beam_grammar_select", _p(state), _p(beam), _p(gstate), _p(cand_logp), _p(cand_id), _p(cand_next), _p(out), _p(logp),
+         N, int(V), cap, int(eos_token))

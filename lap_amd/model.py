@@ -806,7 +806,7 @@ class LAP:
         reference has no such option.
 
         num_beams: beam search.  None (default): everything above, unchanged.  num_beams=N, 1 <= N <= 8 (an observation of batch 1,
-        temperature 0, decode "fused" or "eager"; sampler="device", num_samples, top_k / top_p, speculate, grammar, jump_forward
+        temperature 0, decode "fused" or "eager"; sampler="device", num_samples, top_k / top_p, speculate, jump_forward
         and collect raise ValueError from `beam.check_num_beams`): the deterministic search for the most probable answer.  The
         prefix is prefilled once and shared by N rows that advance in lockstep; at every step each alive beam offers its N most
         probable tokens, and the N candidates with the largest sum of token log-probabilities become the beams, in rank order
@@ -815,7 +815,10 @@ class LAP:
         beam can pass under the sum score; False: it runs until every beam has finished or the budget is spent.  Returns the
         rank-0 beam as int32 [1, max_decoding_steps] (with return_logprobs also its token log-probabilities);
         `ar_decode.beam_decode_fused` / `beam_decode_eager` return all beams.  num_beams=1 is the greedy decode.  Composes with
-        allowed_tokens, decode_weights and return_logprobs.  The reference has no such option."""
+        allowed_tokens, decode_weights and return_logprobs, and with `grammar` (not with allowed_tokens): every beam is then in a state
+        of the automaton and offers its N most probable edges, with log-probabilities over that state's set, so the answer is the most
+        probable sentence of the format among the beams kept (`beam.grammar_beam_step`; lap_decode_beam_grammar_topn / _select).  The
+        reference has no such option."""
         from lap_amd import ar_decode       # (it imports this module)
         return ar_decode.sample_tokens(self, rng, observation, max_decoding_steps=max_decoding_steps, temperature=temperature,
                                        collect=collect, decode=decode, sampler=sampler, decode_weights=decode_weights,

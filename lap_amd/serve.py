@@ -137,12 +137,13 @@ class GraphedTokenDecoder:
     decoder without it returns, log-probabilities included, and `last_stats` = (verify_steps, accepted).  Composes with sampling=,
     weights= and logprobs=.
 
-    num_beams=N (1 <= N <= 8; batch_size 1, greedy: sampling=, num_samples=, filtering=, speculate=, grammar= and jump_forward= raise
+    num_beams=N (1 <= N <= 8; batch_size 1, greedy: sampling=, num_samples=, filtering=, speculate= and jump_forward= raise
     ValueError from `beam.check_num_beams`), early_stop=: `sample_tokens`' beam search.  The prefill graph runs at B = 1, copies its
     prefix to N rows and resets the beam buffer with a device copy; the step graph runs the beam step at B = N, so one capture
     serves every request.  A call returns the rank-0 beam ([1, steps] tokens, with logprobs=True also its log-probabilities);
     `last_beams` = (tokens [N, steps], logprobs [N, steps], scores [N]) of the call.  Composes with weights=, allowed_tokens= and
-    logprobs=."""
+    logprobs=, and with grammar= (not with allowed_tokens=): the beams are then the most probable sentences of the automaton, every
+    beam's automaton state lives in the context and is zeroed inside the prefill graph, and one capture serves every request."""
 
     def __init__(self, model: LAP, batch_size: int = 1, max_decoding_steps: int = 390, prompt_len: int | None = None,
                  steps_per_replay: int = 8, sampling: bool = False, weights: str = "bf16", allowed_tokens=None,
@@ -473,7 +474,8 @@ class ARPolicy:
         self._num_samples = self._sample_kwargs.get("num_samples")
         # sample_kwargs["num_beams"] = N selects beam search (greedy; decode "fused", the default here, or "eager"): the policy
         # answers with the beam `sampling.select_best` picks under "select", reports all N under "candidates" in best-of-N's layout,
-        # and searches with early_stop=False under "mean" (a longer beam may then win).  "allowed_tokens" and "decode_weights" compose.
+        # and searches with early_stop=False under "mean" (a longer beam may then win).  "allowed_tokens" and "decode_weights" compose,
+        # and so does "grammar" (on the device by now; not with "allowed_tokens"): the beams are sentences of the automaton.
         self._num_beams = self._sample_kwargs.pop("num_beams", None)
         self._beam_scores = None        # the device scores of the last request's beams (-inf: a padding beam)
         if self._num_beams is not None:
@@ -596,9 +598,9 @@ class ARPolicy:
         with m._serving_weights():
             if kw.get("decode", "fused") == "fused":
                 ar_decode.check_fused_decode(m, N)
-                tok, logp, scores = ar_decode.beam_decode_fused(m, o, N, weights=weights, allowed=allowed, **m_kw)
+                tok, logp, scores = ar_decode.beam_decode_fused(m, o, N, weights=weights, allowed=allowed, grammar=kw.get("grammar"), **m_kw)
             else:
-                tok, logp, scores = ar_decode.beam_decode_eager(m, o, N, allowed=allowed, **m_kw)
+                tok, logp, scores = ar_decode.beam_decode_eager(m, o, N, allowed=allowed, grammar=kw.get("grammar"), **m_kw)
         self._beam_scores = scores.cpu().numpy()
         return tok, logp
 
@@ -611,7 +613,7 @@ class ARPolicy:
 
 def create_trained_policy_ar(*args, sample_kwargs: dict | None = None, language_action_format="verbose_eef_with_rotation",
                              ar_graph: bool = False, grammar: bool = False, grammar_limits: dict | None = None, jump_forward=None,
-                             **kwargs) -> ARPolicy:
+                             num_beams=None, **kwargs) -> ARPolicy:
     """policy_config_adapter.py:157-160 with the AR output stack [DetokenizeReasoning, CoTOutputs(language_action_format)]:
     generated ids -> text -> [dx, dy, dz, droll, dpitch, dyaw, gripper] (the language action describes the whole chunk as
     one delta, output_transforms.py:75-104; `Unnormalize` has no `actions` statistics to apply to such deltas and is left out
@@ -638,7 +640,9 @@ def create_trained_policy_ar(*args, sample_kwargs: dict | None = None, language_
     jump_forward=S (2 <= S <= 8; with grammar=True or an automaton in sample_kwargs; the same as sample_kwargs={"jump_forward": S}):
     the constrained answer is decoded on steps of S rows on which the tokens the grammar forces, and what the previous request's
     answer drafts, ride along (`LAP.sample_tokens`); tokens and log-probabilities are unchanged, at any temperature, and
-    "policy_timing" gains "spec_steps" and "spec_accepted"."""
+    "policy_timing" gains "spec_steps" and "spec_accepted".
+    num_beams=N (the same as sample_kwargs={"num_beams": N}): beam search; with grammar=True the answer is the most probable sentence
+    of the format among the N beams kept (`beam.grammar_beam_step`), so it always parses."""
     from lap_amd import policy_io as pio
 
     base = create_trained_policy(*args, use_graph=False, **kwargs)
@@ -649,5 +653,7 @@ def create_trained_policy_ar(*args, sample_kwargs: dict | None = None, language_
                                                          **(grammar_limits or {}))
     if jump_forward is not None:
         sample_kwargs = dict(sample_kwargs or {}) | {"jump_forward": jump_forward}
+    if num_beams is not None:
+        sample_kwargs = dict(sample_kwargs or {}) | {"num_beams": num_beams}
     base._output_transform = pio.compose([pio.DetokenizeReasoning(tok), pio.CoTOutputs(language_action_format=language_action_format)])
     return ARPolicy(base, sample_kwargs=sample_kwargs, use_graph=ar_graph)

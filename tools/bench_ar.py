@@ -44,6 +44,11 @@ and lap_decode_grammar_finish, each from a captured graph of back-to-back launch
 head piece and single-character pieces with ids in order of first use, which gives the automaton the shape a real tokenizer gives
 it.  The automaton needs a real EOS id (the model's is set to 1 for this part), so after "gripper" the sentence may start again and a
 row ends only when it draws EOS there; the grammar figure is per token actually decoded, which the result reports.
+--grammar verbose together with --num-beams N [N ...] adds grammar-constrained beam search (`num_beams=N` + `grammar=`) on the same
+automaton, beside the plain beam search and `grammar=` with `num_samples=N` at the same N: the three graphed decoders take turns
+in this process; ms per step actually decoded of each (mean and [min, max] of at least seven repeats), the steps each decoded,
+the device time of lap_decode_beam_grammar_topn (every row in the state with the most edges) and lap_decode_beam_grammar_select
+on their own, and whether every finished beam is a sentence of the automaton.
 --jump-forward S [S ...] (with --grammar verbose) adds jump-forward grammar decoding (`grammar=` + `jump_forward=S`), graphed at B = 1
 on the automaton of the same synthetic word graph WITHOUT the restart after "gripper", so the greedy answer is one sentence that
 ends in its EOS: ms per answer (the call minus the prefill graph) of `grammar=` alone and of every S, without a reference (only
@@ -56,6 +61,8 @@ import json
 import os
 import sys
 import time
+
+import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -266,6 +273,7 @@ if a.num_beams:     # the beam step against the num_samples=N step at equal batc
             ts.append(e0.elapsed_time(e1) * 1e3)
         return round(sorted(ts[5:])[n // 2], 2)
 
+    one_launch_us = launch_us       # (the grammar part below reuses the name for its own table)
     for NB in a.num_beams:
         bdec = GraphedTokenDecoder(model, 1, N, num_beams=NB, logprobs=True).capture()
         ndec = GraphedTokenDecoder(model, 1, N, sampling=True, num_samples=NB).capture()
@@ -394,8 +402,50 @@ if a.grammar:
         "grammar_finish_us": launches(lambda: hip.decode_grammar_finish(ctx.state, None, ctx.gstate, dg.offsets, dg.ids, dg.next,
                                                                         ctx.logits, ctx.out, -1)),
         "launches_per_graph": n_l}
+    gbeams = {}
+    if a.num_beams:     # grammar + beams beside the plain beam step and the grammar best-of-N step at the same N: graphed, in turns
+        for NB in a.num_beams:
+            trio = {"grammar_beam": GraphedTokenDecoder(model, 1, N, num_beams=NB, grammar=auto, logprobs=True).capture(),
+                    "plain_beam": GraphedTokenDecoder(model, 1, N, num_beams=NB, logprobs=True).capture(),
+                    "grammar_num_samples": GraphedTokenDecoder(model, 1, N, sampling=True, num_samples=NB, grammar=auto).capture()}
+            call = {k: ((lambda d=d: d(o, temperature=1.0, seed=1)) if k == "grammar_num_samples" else (lambda d=d: d(o)))
+                    for k, d in trio.items()}
+            bpre = {k: timeit(lambda d=d: (d.g_prefill.replay()), a.reps) for k, d in trio.items()}
+            bruns = {k: [] for k in trio}
+            for _ in range(max(a.reps, 7)):
+                for k, d in trio.items():
+                    t = timeit(call[k], 1)
+                    bruns[k].append((t - bpre[k]) / max(int(d.ctx.state[0]) - 1, 1))
+            gb = trio["grammar_beam"]
+            gb(o)
+            btok = gb.last_beams[0].cpu().numpy()
+            bctx = gb.ctx
+            st, bw, gq = bctx.state.clone(), bctx.beam.clone(), bctx.gstate.clone()
+            st0, bw0 = bctx.state.clone(), bctx.beam_init.clone()
+            st0[0], st0[1] = N // 2, 0
+            bw0[:NB] = torch.linspace(0, -1, NB).view(torch.int32) if NB > 1 else bw0[:NB]
+            big = int(np.argmax(np.diff(auto.offsets)))             # every row in the state with the most edges
+
+            def greset():
+                st.copy_(st0); bw.copy_(bw0); gq.fill_(big)
+
+            gout, glp = bctx.out.clone(), bctx.logp.clone()
+            row = {}
+            for k in trio:
+                row |= {f"{k}_ms_per_step": round(sum(bruns[k]) / len(bruns[k]), 4),
+                        f"{k}_ms_per_step_min_max": [round(min(bruns[k]), 4), round(max(bruns[k]), 4)],
+                        f"{k}_steps_decoded": int(trio[k].ctx.state[0]), f"{k}_prefill_ms": round(bpre[k], 3)}
+            row |= {"grammar_beam_over_plain_beam": round(row["grammar_beam_ms_per_step"] / row["plain_beam_ms_per_step"], 4),
+                    "grammar_topn_us_at_the_largest_state": one_launch_us(lambda: hip.decode_beam_grammar_topn(
+                        st, bw, gq, dg.offsets, dg.ids, dg.next, bctx.logits, bctx.cand_logp, bctx.cand_id, bctx.cand_next, N), greset),
+                    "grammar_select_us": one_launch_us(lambda: hip.decode_beam_grammar_select(
+                        st, bw, gq, bctx.cand_logp, bctx.cand_id, bctx.cand_next, gout, glp, cfg.vocab_size, -1), greset),
+                    "largest_state_edges": int(np.diff(auto.offsets).max()),
+                    "finished_beams_accepted": bool(all(auto.accepts(r) for r in btok if 1 in r.tolist()))}
+            gbeams[f"N{NB}"] = row
+            del trio, gb
     model.EOS_TOKEN = -1
-    grammar_res = {"grammar": {
+    grammar_res = ({"grammar_beams": gbeams} if gbeams else {}) | {"grammar": {
         "format": "verbose_with_rotation", "Q": auto.num_states, "E": auto.num_edges, "union": int(auto.union().shape[0]),
         "grammar_graphed_ms_per_token": g_res[0], "grammar_graphed_ms_per_token_min_max": g_res[1], "grammar_tokens_decoded": g_res[2],
         "allowed_union_graphed_ms_per_token": a_res[0], "allowed_union_graphed_ms_per_token_min_max": a_res[1],
