@@ -15,6 +15,7 @@ from lap_amd.joint_layers import llm_fwd
 from lap_amd.loss import lm_logits
 from lap_amd.model import LAP, _gen
 from lap_amd.observation import preprocess_observation
+from lap_amd.score import check_score_args, check_score_ctx
 from lap_amd.speculate import check_jump_forward, check_speculate
 
 DECODE_STEPS_PER_CHECK = 8      # fused steps between two host reads of the device stop flag (eager `decode="fused"`)
@@ -535,6 +536,39 @@ def _sample_fused(model: LAP, observation, *, max_decoding_steps: int, collect=N
     return (ctx.out, ctx.logp) if logprobs else ctx.out
 
 
+class ScoreResult(NamedTuple):
+    """What `score_tokens` returns for N candidates."""
+    logp: list                      # N f32 tensors: the log-probability of every given token
+    total: torch.Tensor             # f32 [N]: their sums
+    greedy: list                    # N int32 tensors: the argmax id at every position
+
+
+def score_tokens(model: LAP, observation, tokens, *, rows: int = 8, temperature: float = 0.0, decode_weights: str = "bf16",
+                 allowed_tokens=None, max_decoding_steps: int = 390) -> ScoreResult:
+    """`LAP.score_tokens` (documented there): every argument is checked before any device work."""
+    seqs, S, _ = check_score_args(tokens, rows, max_decoding_steps, batch=observation.tokenized_prompt.shape[0])
+    check_decode_weights(decode_weights)
+    check_fused_decode(model, S)
+    hip.sampling_words(0, temperature)      # (rejects a temperature whose inverse is not finite before any work)
+    allowed = allowed_set(model, allowed_tokens).ids if allowed_tokens is not None else None
+    with model._serving_weights():
+        pre = prefill(model, observation)
+        ctx = DecodeCtx(model, 1, pre.Pn, max_decoding_steps, weights=decode_weights, allowed=allowed, score=S)
+        ctx.set_score_temperature(temperature)
+        logp, greedy = [], []
+        for ids in seqs:                    # one prefill, one context: the state is reset and the generated cache overwritten
+            ctx.set_candidate(ids)
+            ctx.first_token(pre)
+            for _ in range((len(ids) - 1 + S - 1) // S):
+                ctx.step()
+            lp, gr = ctx.score_result()
+            if lp.numel() != len(ids):
+                raise RuntimeError(f"score_tokens: scored {lp.numel()} of {len(ids)} tokens")
+            logp.append(lp)
+            greedy.append(gr)
+    return ScoreResult(logp, torch.stack([lp.sum() for lp in logp]), greedy)
+
+
 class DecodeCtx:
     """One fused decode of `model` (B rows, `Pn` prefix keys, `cap` = max_decoding_steps): the device state, the token output,
     the fixed-capacity generated K/V cache of every layer ([depth, 2, B, cap, head_dim] bf16, 7.2 MB per sample at 390 steps
@@ -569,12 +603,23 @@ class DecodeCtx:
     beams=N with grammar=DeviceAutomaton: the beams are the most probable sentences of the automaton (`beam.grammar_beam_step`).  The
     context also owns `gstate` [N] (every beam's automaton state) and `cand_next`; the head is the SUBSET head over the automaton's
     union, lap_decode_beam_grammar_topn reads only the edges of every row's state and lap_decode_beam_grammar_select carries the
-    states along the parent permutation."""
+    states along the parent permutation.
+    score=S (1 <= S <= 8; B = 1; composes with weights and allowed, not with sampling, filtering, speculate, grammar, jump_forward
+    or beams): the context scores a GIVEN sequence instead of decoding one (lap_amd/score.py, csrc/decode_score.hip).  The
+    arrangement is that of speculate=S; the candidate lives in the reference buffer (`set_candidate`), `logp` [1, cap] receives the
+    log-probability of every given token and `greedy` [1, cap] the argmax id at its position; `out` stays zero.  `first_token`
+    scores token 0 from the prefill's last row, every `step` the next min(S, length - t) tokens on one pass over the weights; the
+    context is done when all are scored.  `set_score_temperature` sets the temperature of z; `stats` reads the counters."""
 
     def __init__(self, model: LAP, B: int, Pn: int, cap: int, sampling: bool = False, weights: str = "bf16", allowed=None,
                  logprobs: bool = False, filtering: bool = False, speculate=None, grammar=None, jump_forward=None, beams=None,
-                 early_stop: bool = True):
+                 early_stop: bool = True, score=None):
         check_decode_weights(weights)
+        self.score = None
+        if score is not None:
+            self.score = check_score_ctx(score, B, sampling=sampling, filtering=filtering, speculate=speculate, grammar=grammar,
+                                         jump_forward=jump_forward, beams=beams)
+            logprobs = True
         self.beams = None
         if beams is not None:
             from lap_amd.beam import check_num_beams
@@ -596,7 +641,7 @@ class DecodeCtx:
         self.S = None
         if speculate is not None:
             self.S = check_speculate(speculate, B, return_logprobs=logprobs, temperature=1.0 if sampling else 0.0)
-        R = self.S or self.J or B       # rows of a step's activations
+        R = self.S or self.J or self.score or B     # rows of a step's activations
         if filtering and not sampling:
             raise ValueError("DecodeCtx: filtering needs sampling=True (the filters are part of the device sampler)")
         if allowed is not None and (allowed.dtype != torch.int32 or not allowed.is_cuda or allowed.dim() != 1):
@@ -620,15 +665,20 @@ class DecodeCtx:
         self.attn_scratch = hip.decode_attn_scratch(R, Pn, cap, dev)
         self.pval, self.pidx = hip.decode_lm_partials(R, dev)
         # speculate: the reference sequence {length, ids[cap]} and the S - 1 drafted tokens of the step
-        self.ref = hip.decode_spec_ref(cap, dev) if R != B else None
-        self.draft = torch.full((R - 1,), -1, dtype=torch.int32, device=dev) if R != B else None
+        # score: the same buffer holds the candidate, and nothing is drafted
+        self.ref = hip.decode_spec_ref(cap, dev) if R != B or self.score else None
+        self.draft = torch.full((R - 1,), -1, dtype=torch.int32, device=dev) if R != B and not self.score else None
         # the sampling words {seed low, seed high, bits of 1 / temperature, 0} of the sampling LM head (zeros: greedy); None:
         # the context decodes on the greedy LM head
         self.sampling = hip.decode_sampling(dev) if sampling else None
         # logprobs: the log-probability of every token of `out` beside it (f32 [B, cap], zeros where nothing was written) and the
         # LM head's log-sum-exp partials; None: the context launches the heads without them
         self.logp = torch.zeros((B, cap), dtype=torch.float32, device=dev) if logprobs else None
-        self.plp = hip.decode_lm_logp_partials(B, dev) if logprobs and grammar is None and self.beams is None else None
+        self.plp = hip.decode_lm_logp_partials(R, dev) if logprobs and grammar is None and self.beams is None else None
+        # score: the argmax id at every scored position beside `logp`, and the words that carry the temperature to the TARGET head
+        # (zeros: z = logit; `set_score_temperature`)
+        self.greedy = torch.zeros((B, cap), dtype=torch.int32, device=dev) if self.score else None
+        self.score_words = hip.decode_sampling(dev) if self.score else None
         # filtering: the filter words {top_k, bits of top_p, 0, 0} (neutral until `set_filter`) and the f32 logits of the step, which
         # keep -inf outside an allowed set (the constrained head writes the allowed columns only)
         self.filter = hip.decode_filter(dev) if filtering else None
@@ -678,6 +728,28 @@ class DecodeCtx:
             raise ValueError("this decode context was built without filtering")
         hip.decode_set_filter(self.filter, top_k, top_p)
 
+    def set_candidate(self, ids):
+        """The sequence the next `first_token` + `step`s score (any integer sequence of 1 .. cap ids): a host-to-device copy."""
+        if self.score is None:
+            raise ValueError("this decode context was built without score")
+        n = len(ids)
+        if not 1 <= n <= self.cap:
+            raise ValueError(f"set_candidate: a sequence of 1 <= length <= {self.cap} ids, got length {n}")
+        hip.decode_set_spec_ref(self.ref, ids)
+
+    def set_score_temperature(self, temperature: float):
+        """The temperature the next candidates are scored at (0: z = logit): a host-to-device copy."""
+        if self.score is None:
+            raise ValueError("this decode context was built without score")
+        hip.decode_set_sampling(self.score_words, 0, temperature)
+
+    def score_result(self):
+        """(logp f32 [n], greedy int32 [n]) of the n tokens scored so far (a host read of t): fresh tensors."""
+        if self.score is None:
+            raise ValueError("this decode context was built without score")
+        n = int(self.state[0].item())
+        return self.logp[0, :n].clone(), self.greedy[0, :n].clone()
+
     def set_draft(self, ids):
         """The reference sequence the next decode drafts from (any integer sequence, truncated to `cap`; None: no draft, every
         verify step then emits one token): a host-to-device copy; captured graphs keep the buffer's address."""
@@ -711,6 +783,8 @@ class DecodeCtx:
         hip.decode_init(self.state, self.plen, self.out)
         if self.logp is not None:
             self.logp.zero_()
+        if self.greedy is not None:
+            self.greedy.zero_()
         if self.gstate is not None:       # every request starts in state 0 (a device op: the prefill graph captures it)
             self.gstate.zero_()
         if self.beam is not None:         # every request starts from {0, -inf, ...} (a device copy: the prefill graph captures it)
@@ -736,6 +810,12 @@ class DecodeCtx:
             hi, lo, kw = m.W("llm/embed"), m.ps.w16lo("llm/embed"), {}
         if self.allowed is not None:      # the LM head streams the allowed rows only
             kw["ids"] = self.allowed
+        if self.score is not None:        # the TARGET head on the rows of x (one: token 0), then the finish that writes their logp / greedy
+            hip.decode_lm_head_score(self.state, self.score_words, self.ref, x, m.F("llm/final_norm"), hi, lo, self.pval, self.pidx,
+                                     self.plp, logits, **kw)
+            hip.decode_score_finish(self.state, self.pval, self.pidx, self.plp, self.ref, self.logp.view(-1), self.greedy.view(-1),
+                                    x.shape[0])
+            return
         if self.beam is not None and self.grammar is not None:    # the head over the union, then the top-N over every row's state
             g = self.grammar
             hip.decode_lm_head(self.state, x, m.F("llm/final_norm"), hi, lo, self.pval, self.pidx, self.logits, **(kw | {"ids": g.union}))
@@ -791,10 +871,12 @@ class DecodeCtx:
         v = m.v
         NH, HD, KV = v.num_heads, v.head_dim, v.num_kv_heads
         rows, lo, hi = m.ps.embed_rows()
-        rows_of_one = bool(self.S or self.J)        # the rows are S positions of one sequence
+        rows_of_one = bool(self.S or self.J or (self.score or 0) >= 2)      # the rows are S >= 2 positions of one sequence
         if self.beam is not None:         # the generated K / V of every beam become those of the parent the last select chose
             hip.decode_beam_reorder(self.state, self.beam, self.gen)
-        if rows_of_one:
+        if self.score:                    # row r feeds the candidate's ids[t-1+r]  (score=1: the plain B = 1 layers)
+            hip.decode_score_embed(self.state, rows, lo, hi, self.ref, self.x, math.sqrt(v.width))
+        elif rows_of_one:
             hip.decode_spec_draft(self.state, self.ref, self.out, self.draft)
             if self.J:
                 g = self.grammar

@@ -493,6 +493,16 @@ struct LmLogP : Base {
   float* plp;                          // partials [gridDim.x][B][3] = {m, s, z of the block's best candidate}
 };
 
+// P = LmScoreP<LmP> / LmScoreP<LmP8>: the TARGET instances' arguments (teacher-forced scoring, csrc/decode_score.hip).  A TARGET
+// instance is the LOGP instance of the same rows whose third plp word is the z of a GIVEN id, row b's target cand[1 + t + b] of the
+// candidate buffer {length, ids[cap]}, instead of the z of the row's best candidate.
+template <class Base>
+struct LmScoreP : LmLogP<Base> {
+  const int* cand; int cap;            // the candidate {length, ids[cap]}; length is clamped to [0, cap]
+};
+template <class P> struct lm_is_target : std::false_type {};
+template <class Base> struct lm_is_target<LmScoreP<Base>> : std::true_type {};
+
 // The row dot product of the LM head.  Every head (full or subset, greedy or sampling, bf16 or fp8) runs this one statement of
 // it, so the logit of vocabulary row j is the same bits in all of them by construction; tests/test_decode_bits_gpu.py pins
 // those bits to a recorded fixture.  The logits of rows f0 and f1 (f1 == f0: one row) for all B rows of `sx` are wave-uniform
@@ -601,7 +611,8 @@ __device__ __forceinline__ void lse_merge(float m2, float s2, float& m, float& s
 }
 
 // LOGP, after lm_block_partials (which leaves the waves' bests in sv / si): the block's (m, s) of every row from its four
-// waves' pairs in wave order, and the noise-free z of the candidate that lm_block_partials chose.
+// waves' pairs in wave order, and the noise-free z of the candidate that lm_block_partials chose.  TARGET: the z of the row's
+// target instead, from the wave that met it (the others hold -inf; a maximum, so the order does not matter).
 template <int B, class P>
 __device__ __forceinline__ void lm_block_logp(const P& p, int lane, int w, float lm, float ls, float lz, const float (*sv)[B],
                                               const int (*si)[B]) {
@@ -613,7 +624,8 @@ __device__ __forceinline__ void lm_block_logp(const P& p, int lane, int w, float
     float v = sv[0][b], m = slp[0][b][0], s = slp[0][b][1], z = slp[0][b][2];
     int i = si[0][b];
     for (int k = 1; k < 4; ++k) {
-      if (better(sv[k][b], si[k][b], v, i)) { v = sv[k][b]; i = si[k][b]; z = slp[k][b][2]; }
+      if constexpr (lm_is_target<P>::value) z = fmaxf(z, slp[k][b][2]);
+      else if (better(sv[k][b], si[k][b], v, i)) { v = sv[k][b]; i = si[k][b]; z = slp[k][b][2]; }
       lse_merge(slp[k][b][0], slp[k][b][1], m, s);
     }
     float* o = p.plp + ((long long)blockIdx.x * B + b) * 3;
@@ -634,9 +646,15 @@ __device__ __forceinline__ void lm_block_logp(const P& p, int lane, int w, float
 // LOGP (SAMPLE instances only; p.samp may then be NULL: greedy): lane b also keeps row b's running (m, s) over z and the z of
 // its best candidate, and the block writes them to p.plp (lm_block_logp); pval / pidx / logits are those of the instance without
 // it, bit for bit.  A row whose id is outside [0, V) enters neither; the single row of an odd last unit enters once.
+// TARGET (P = LmScoreP<.>, a LOGP instance): lane b keeps the z of row b's target tg = cand[1 + t + b] instead of the z of its best
+// candidate, and no noise is drawn: pval / pidx are the greedy head's, (m, s) the LOGP head's at the same inv_t.  The target is
+// only ever compared with the rows a unit runs, never used as an address: one outside [0, V), outside the subset or at t + b >=
+// length meets no row and leaves -inf.  The block that owns the target's unit writes its z, every other block -inf.
 template <int B, bool SAMPLE, bool SUBSET, class P, bool LOGP = false>
 __global__ __launch_bounds__(256) void dec_lm_head_kernel(P p) {
   static_assert(SAMPLE || !LOGP, "LOGP: the lane-b-owns-row-b form only");
+  constexpr bool TARGET = lm_is_target<P>::value;
+  static_assert(LOGP || !TARGET, "TARGET: a LOGP instance");
   __shared__ __attribute__((aligned(16))) bf16 sx[B * DEC_D];
   __shared__ float red[4];
   __shared__ float sv[4][B];
@@ -669,6 +687,11 @@ __global__ __launch_bounds__(256) void dec_lm_head_kernel(P p) {
     step = (uint32_t)p.state[0];
   }
   float lm = -INFINITY, ls = 0.f, lz = -INFINITY;      // LOGP: lane b's (m, s) of row b and the z of its best candidate
+  int tg = -1;                         // TARGET: lane b's target id, -1 when row b has none
+  if constexpr (TARGET) {
+    const int j = p.state[0] + lane, len = min(p.cand[0], p.cap);
+    if (lane < B && j >= 0 && j < len) tg = p.cand[1 + j];
+  }
   for (int u = SUBSET ? blockIdx.x + w * gridDim.x : blockIdx.x * 4 + w; u < units; u += gridDim.x * 4) {
     int f0, f1;
     if (SUBSET) {
@@ -691,13 +714,17 @@ __global__ __launch_bounds__(256) void dec_lm_head_kernel(P p) {
         if (inv_t != 0.f) { z0 = __builtin_fmaf(y0, inv_t, 0.0f); z1 = __builtin_fmaf(y1, inv_t, 0.0f); }
         lse_push(z0, lm, ls);
         if (f1 != f0) lse_push(z1, lm, ls);
+        if constexpr (TARGET) {
+          if (f0 == tg) lz = z0;
+          if (f1 != f0 && f1 == tg) lz = z1;
+        }
       }
-      if (inv_t != 0.f) {
+      if (!TARGET && inv_t != 0.f) {
         if (SUBSET) lap_sampling::gumbel_scores_at(y0, y1, inv_t, seed_lo, seed_hi, step, (uint32_t)lane, (uint32_t)f0, (uint32_t)f1, y0, y1);
         else lap_sampling::gumbel_scores(y0, y1, inv_t, seed_lo, seed_hi, step, (uint32_t)lane, (uint32_t)u, y0, y1);
       }
-      if (better(y0, f0, lbv, lbi)) { lbv = y0; lbi = f0; if constexpr (LOGP) lz = z0; }
-      if (f1 != f0 && better(y1, f1, lbv, lbi)) { lbv = y1; lbi = f1; if constexpr (LOGP) lz = z1; }
+      if (better(y0, f0, lbv, lbi)) { lbv = y0; lbi = f0; if constexpr (LOGP && !TARGET) lz = z0; }
+      if (f1 != f0 && better(y1, f1, lbv, lbi)) { lbv = y1; lbi = f1; if constexpr (LOGP && !TARGET) lz = z1; }
     }
   }
   lm_block_partials<B, SAMPLE>(p, lane, w, bv, bi, lbv, lbi, sv, si);
@@ -910,7 +937,8 @@ int launch_lm_head(const P& p, int B, void* stream) {
 // plp != NULL: the LOGP instances (the sampling form of the kernel, which is the greedy head while sampling is NULL or inv_t == 0).
 int lm_head_impl(const int* state, const int* sampling, bool sample, const void* x, const float* gamma, const void* hi, const void* lo,
                  const float* wscale, bool f8, int B, int D, int V, float eps, float* logits, float* pval, int* pidx, void* stream,
-                 bool subset = false, const int* ids = nullptr, int n = 0, float* plp = nullptr) {
+                 bool subset = false, const int* ids = nullptr, int n = 0, float* plp = nullptr, const int* cand = nullptr,
+                 int cand_cap = 0) {
   if (!state || (sample && !sampling) || !gamma || !hi || !pval || !pidx || B < 1 || B > DEC_MAXB || D != DEC_D || V < 2 ||
       !aligned16(x) || !aligned16(hi) || (lo && !aligned16(lo)) || (f8 && (!wscale || !f8_k_ok(D, 1))) ||
       (subset && (!ids || n < 1 || n > V))) return LAP_ERR_ARG;
@@ -918,6 +946,19 @@ int lm_head_impl(const int* state, const int* sampling, bool sample, const void*
   p.state = state; p.x = (const bf16*)x; p.gamma = gamma; p.eps = eps; p.hi = (const bf16*)hi; p.lo = f8 ? nullptr : (const bf16*)lo;
   p.V = V; p.D = D; p.logits = logits; p.pval = pval; p.pidx = pidx; p.samp = sampling; p.ids = ids; p.n = n;
   p.wscale = wscale;
+  if (cand) {      // the TARGET instances (plp is theirs too)
+    if (!plp || cand_cap < 1) return LAP_ERR_ARG;
+    LmScoreP<LmP> q{};
+    LmScoreP<LmP8> q8{};
+    static_cast<LmP&>(q) = p; static_cast<LmP8&>(q8) = p;
+    q.plp = q8.plp = plp; q.cand = q8.cand = cand; q.cap = q8.cap = cand_cap;
+    switch ((f8 ? 2 : 0) | (subset ? 1 : 0)) {
+      case 0: return launch_lm_head<true, false, LmScoreP<LmP>, true>(q, B, stream);
+      case 1: return launch_lm_head<true, true, LmScoreP<LmP>, true>(q, B, stream);
+      case 2: return launch_lm_head<true, false, LmScoreP<LmP8>, true>(q8, B, stream);
+      default: return launch_lm_head<true, true, LmScoreP<LmP8>, true>(q8, B, stream);
+    }
+  }
   if (plp) {
     LmLogP<LmP> q{};
     LmLogP<LmP8> q8{};
@@ -1118,6 +1159,24 @@ extern "C" int lap_decode_finish_lp(int* state, const float* pval, const int* pi
   hipLaunchKernelGGL(dec_finish_kernel<true>, dim3(1), dim3(256), 0, S_, state, pval, pidx, LM_BLOCKS, out, cap, B, eos_token, plp, logp);
   LAP_CHECK_LAUNCH();
   return LAP_OK;
+}
+
+// ---- teacher-forced scoring (lap_amd/score.py; the embed and finish kernels are csrc/decode_score.hip): the LOGP heads whose third
+// plp word is the z of the target cand[1 + t + b] of row b.  sampling NULL or inv_t == 0: z = logit; ids != NULL: the SUBSET form.
+extern "C" int lap_decode_lm_head_score(const int* state, const int* sampling, const int* cand, int cap, const void* x,
+                                        const float* gamma, const void* hi, const void* lo, const int* ids, int n, int B, int D, int V,
+                                        float eps, float* logits, float* pval, int* pidx, float* plp, void* stream) {
+  if (!plp || !cand) return LAP_ERR_ARG;
+  return lm_head_impl(state, sampling, false, x, gamma, hi, lo, nullptr, false, B, D, V, eps, logits, pval, pidx, stream, ids != nullptr,
+                      ids, n, plp, cand, cap);
+}
+
+extern "C" int lap_decode_lm_head_score_fp8(const int* state, const int* sampling, const int* cand, int cap, const void* x,
+                                            const float* gamma, const void* w8, const float* wscale, const int* ids, int n, int B, int D,
+                                            int V, float eps, float* logits, float* pval, int* pidx, float* plp, void* stream) {
+  if (!plp || !cand || !wscale) return LAP_ERR_ARG;
+  return lm_head_impl(state, sampling, false, x, gamma, w8, nullptr, wscale, true, B, D, V, eps, logits, pval, pidx, stream,
+                      ids != nullptr, ids, n, plp, cand, cap);
 }
 
 // ---- speculative decoding (lap_amd/speculate.py; the draft, embed and accept kernels are csrc/decode_spec.hip): the QKV and

@@ -250,6 +250,10 @@ SIGNATURES: dict[str, list] = {
     "lap_decode_spec_qkv": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp],
     "lap_decode_spec_attention": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _ll, _i, _i, _i, _i, _vp],
     "lap_decode_spec_accept": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "lap_decode_score_embed": [_vp, _vp, _i, _i, _vp, _i, _vp, _i, _i, _f, _vp],
+    "lap_decode_lm_head_score": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp],
+    "lap_decode_lm_head_score_fp8": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp],
+    "lap_decode_score_finish": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
     "lap_decode_grammar_finish": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "lap_decode_grammar_draft": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp],
     "lap_decode_grammar_spec_finish": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
@@ -1845,6 +1849,75 @@ def decode_spec_accept(state, pval, pidx, draft, out, eos_token):
     if pval.numel() < S * _fn["lap_decode_lm_blocks"]() or pidx.numel() < S * _fn["lap_decode_lm_blocks"]():
         raise TypeError("decode_spec_accept: pval / pidx hold [lap_decode_lm_blocks()][S] partials")
     call("lap_decode_spec_accept", _p(state), _p(pval), _p(pidx), _p(draft), _p(out), S, cap, int(eos_token))
+
+
+# ---- teacher-forced scoring of one given sequence (csrc/decode_score.hip; lap_amd/score.py restates the quantity).  The candidate
+# buffer is `decode_spec_ref`'s {length, ids[cap]}, filled by `decode_set_spec_ref`.
+def _score_cand(cand):
+    _dreq(cand, torch.int32, "cand")
+    if cand.dim() != 1 or cand.numel() < 2:
+        raise TypeError(f"cand: the candidate buffer int32 [1 + cap] of decode_spec_ref, got shape {tuple(cand.shape)}")
+    return cand.numel() - 1
+
+
+def decode_score_embed(state, table, row_lo, row_hi, cand, x, scale):
+    """x [S, D]: row r embeds the candidate's ids[t-1+r]; a row at or past its length is zero (lap_decode_score_embed)."""
+    cap = _score_cand(cand)
+    _dreq(state, torch.int32, "state"); _dreq(x, torch.bfloat16, "x"); _dreq(table, torch.float32, "table")
+    call("lap_decode_score_embed", _p(state), _p(table), int(row_lo), int(row_hi), _p(cand), cap, _p(x), x.shape[0], x.shape[1],
+         float(scale))
+
+
+def decode_lm_head_score(state, sampling, cand, x, gamma, hi, lo, pval, pidx, plp, logits=None, eps=1e-6, wscale=None, ids=None):
+    """`decode_lm_head_lp` of the same arguments whose third plp word is the z of row b's target, the candidate's ids[t + b], in
+    the block that owns it (-inf elsewhere), and whose pval / pidx are the greedy head's; `sampling` only carries the temperature
+    (None: z = logit) (lap_decode_lm_head_score / _fp8)."""
+    cap = _score_cand(cand)
+    _dreq(state, torch.int32, "state"); _dreq(x, torch.bfloat16, "x"); _dreq(gamma, torch.float32, "gamma")
+    _dreq(pval, torch.float32, "pval"); _dreq(pidx, torch.int32, "pidx"); _dreq(plp, torch.float32, "plp")
+    if sampling is not None:
+        _dreq(sampling, torch.int32, "sampling")
+        if sampling.numel() < _fn["lap_decode_sampling_words"]():
+            raise TypeError("sampling: int32 [lap_decode_sampling_words()]")
+    if logits is not None:
+        _dreq(logits, torch.float32, "logits")
+    B, D = x.shape
+    nblk = _fn["lap_decode_lm_blocks"]()
+    if pval.numel() < B * nblk or pidx.numel() < B * nblk or plp.numel() < 3 * B * nblk:
+        raise TypeError("decode_lm_head_score: pval / pidx hold [lap_decode_lm_blocks()][B] partials, plp [lap_decode_lm_blocks()][B][3]")
+    if logits is not None and logits.numel() < B * hi.shape[0]:
+        raise TypeError("decode_lm_head_score: logits holds f32 [B, V]")
+    n = 0
+    if ids is not None:
+        _ids_req(ids, hi.shape[0])
+        n = ids.numel()
+    if wscale is not None:
+        _f8req(hi, wscale, "hi")
+        if lo is not None:
+            raise TypeError("decode_lm_head_score: the fp8 table is one plane (lo must be None)")
+        call("lap_decode_lm_head_score_fp8", _p(state), _p(sampling), _p(cand), cap, _p(x), _p(gamma), _p(hi), _p(wscale), _p(ids), n,
+             B, D, hi.shape[0], float(eps), _p(logits), _p(pval), _p(pidx), _p(plp))
+        return
+    _dreq(hi, torch.bfloat16, "hi")
+    if lo is not None:
+        _dreq(lo, torch.bfloat16, "lo")
+    call("lap_decode_lm_head_score", _p(state), _p(sampling), _p(cand), cap, _p(x), _p(gamma), _p(hi), _p(lo), _p(ids), n, B, D,
+         hi.shape[0], float(eps), _p(logits), _p(pval), _p(pidx), _p(plp))
+
+
+def decode_score_finish(state, pval, pidx, plp, cand, logp, greedy, S):
+    """The finish of a score step of S rows: logp[t + r] and greedy[t + r] for r < n = min(S, length - t), t += n, done = t >=
+    length, and the two counters (lap_decode_score_finish).  logp f32 / greedy int32 hold cap entries each."""
+    cap = _score_cand(cand)
+    _dreq(state, torch.int32, "state"); _dreq(pval, torch.float32, "pval"); _dreq(pidx, torch.int32, "pidx")
+    _dreq(plp, torch.float32, "plp"); _dreq(logp, torch.float32, "logp"); _dreq(greedy, torch.int32, "greedy")
+    S = int(S)
+    nblk = _fn["lap_decode_lm_blocks"]()
+    if not 1 <= S <= 8 or pval.numel() < S * nblk or pidx.numel() < S * nblk or plp.numel() < 3 * S * nblk:
+        raise TypeError("decode_score_finish: 1 <= S <= 8 rows of partials [lap_decode_lm_blocks()][S] and plp [..][S][3]")
+    if logp.numel() != cap or greedy.numel() != cap:
+        raise TypeError(f"decode_score_finish: logp / greedy of {logp.numel()} / {greedy.numel()} entries beside a candidate buffer of {cap}")
+    call("lap_decode_score_finish", _p(state), _p(pval), _p(pidx), _p(plp), _p(cand), _p(logp), _p(greedy), S, cap)
 
 
 # ---- beam search over the rows of one fused decode batch (csrc/decode_beam.hip; lap_amd/beam.py restates the rules)

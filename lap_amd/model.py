@@ -826,6 +826,27 @@ class LAP:
                                        top_k=top_k, top_p=top_p, speculate=speculate, draft_tokens=draft_tokens, grammar=grammar,
                                        jump_forward=jump_forward, num_beams=num_beams, early_stop=early_stop)
 
+    def score_tokens(self, observation, tokens, *, rows: int = 8, temperature: float = 0.0, decode_weights: str = "bf16",
+                     allowed_tokens=None, max_decoding_steps: int = 390):
+        """Teacher-forced scoring: the log-probability of GIVEN answers under the serving kernels, instead of a decode.
+
+        tokens: one integer sequence, or a list of N sequences, each with 1 <= length <= max_decoding_steps (they need not end
+        with the EOS token; every given token is scored).  The observation (batch 1) is prefilled once and every candidate is
+        scored against that prefix.  Returns `ar_decode.ScoreResult(logp, total, greedy)`: per candidate the f32 log-probability
+        of every token, logp[i] = z[tokens[i]] - logsumexp(z) over the logits that follow tokens[:i], their sum in `total` (f32
+        [N]), and the argmax id at every position (`greedy[i] == tokens[i]` is the token accuracy of the answer as served).
+        temperature 0: z = logit, the convention of `sample_tokens(return_logprobs=True)` on a greedy decode, whose numbers this
+        reproduces bit for bit for its own answer; otherwise z = float32(logit * float32(1 / temperature)).  allowed_tokens: the
+        softmax and the argmax run over that set, as in a constrained decode; a token outside it scores -inf.  decode_weights as
+        in `sample_tokens`, so the same answer can be scored under "bf16", "fp8_layers" and "fp8".
+        rows = S, 1 <= S <= 8: a step scores S consecutive positions on one pass over the weights (the verify step of
+        `speculate=S` with a draft that is always right: csrc/decode_score.hip, the TARGET LM heads of csrc/decode.hip), so L tokens
+        cost 1 + ceil((L - 1) / S) passes; the numbers do not depend on S.  The steps are launched eagerly (no graph capture).
+        lap_amd/score.py states the quantity and the argument checks (ValueError).  The reference has no such entry point."""
+        from lap_amd import ar_decode       # (it imports this module)
+        return ar_decode.score_tokens(self, observation, tokens, rows=rows, temperature=temperature, decode_weights=decode_weights,
+                                      allowed_tokens=allowed_tokens, max_decoding_steps=max_decoding_steps)
+
     DECODE_WEIGHTS = ("bf16", "fp8", "fp8_layers")
     last_spec_stats = None      # (verify steps, drafts accepted) of the last `sample_tokens(speculate=S)` or `(jump_forward=S)` request
 

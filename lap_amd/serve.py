@@ -418,10 +418,12 @@ class ARPolicy:
     ids of `LAP.sample_tokens` (+ the model-level state) instead of an action chunk; decoding them to text / actions is
     the job of the output transforms, which take exactly this dict."""
 
-    def __init__(self, base: Policy, *, sample_kwargs: dict | None = None, use_graph: bool = False):
+    def __init__(self, base: Policy, *, sample_kwargs: dict | None = None, use_graph: bool = False, tokenizer=None):
         if not hasattr(base.model, "sample_tokens"):
             raise AssertionError("Model must have a sample_tokens method")
         self._base = base
+        # the tokenizer `score` encodes answer strings with: the one given, else the input stack's (None: ids only)
+        self._tokenizer = tokenizer
         self._sample_kwargs = dict(sample_kwargs or {})
         self._calls = 0
         # use_graph: greedy requests of the captured shapes replay a GraphedTokenDecoder (B = 1); anything else, and models whose
@@ -604,6 +606,54 @@ class ARPolicy:
         self._beam_scores = scores.cpu().numpy()
         return tok, logp
 
+    def score(self, obs: dict, answers, *, select: str = "sum", rows: int = 8) -> dict:
+        """Rank GIVEN answers for the request `obs` instead of generating one (`LAP.score_tokens`: the prefix is prefilled once,
+        every answer is scored teacher-forced on the serving kernels, `rows` positions per pass over the weights).
+        answers: strings, tokenised with the policy's tokenizer the way a training target is (cleaned, no BOS) and with the EOS
+        appended, as a generated answer ends; or integer id sequences, taken as they are.  One answer or a list of them.
+        sample_kwargs["decode_weights"], ["allowed_tokens"], ["temperature"] and ["max_decoding_steps"] apply; nothing else does.
+        Returns {"logp_sum", "logp_mean", "token_accuracy"} (float64 [N]: the sum of an answer's token log-probabilities up to and
+        including its first EOS (`sampling.sequence_logprob`), that sum per counted token, and the share of positions where the
+        served model's argmax is the given token), "token_logprobs" (N arrays), "tokens" (N arrays: the ids that were scored),
+        "best" (the index `sampling.select_best` picks under `select`: the largest sum or mean, the lowest index among ties) and
+        "policy_timing".  The scoring steps are launched eagerly: they are not captured into the policy's graphs."""
+        from lap_amd import policy_io as pio, sampling
+
+        if select not in ("sum", "mean"):
+            raise ValueError(f"ARPolicy.score: select must be 'sum' or 'mean', got {select!r}")
+        t0 = time.perf_counter()
+        base = self._base
+        model = base.model
+        if isinstance(answers, str) or (len(answers) > 0 and not isinstance(answers[0], str) and np.ndim(answers[0]) == 0):
+            answers = [answers]
+        if len(answers) == 0:
+            raise ValueError("ARPolicy.score: answers is empty (0 answers)")
+        seqs = []
+        for a in answers:
+            if isinstance(a, str):
+                tok = self._tokenizer or next((t.tokenizer for t in base._transforms if isinstance(t, pio.TokenizePromptAndReasoning)), None)
+                if tok is None:
+                    raise ValueError("ARPolicy.score: an answer string needs the policy's tokenizer (a policy without transforms "
+                                     "takes token id sequences)")
+                a = list(tok.encode(a.strip().replace("_", " ").replace("\n", " "), add_bos=False, add_eos=False)) + [model.EOS_TOKEN]
+            seqs.append(a)
+        inputs = base._input_transform(dict(obs)) if base._has_transforms else obs
+        o, _ = base._to_observation(inputs)
+        kw = self._sample_kwargs
+        res = model.score_tokens(o, seqs, rows=rows, temperature=kw.get("temperature", 0.0), decode_weights=kw.get("decode_weights", "bf16"),
+                                 allowed_tokens=kw.get("allowed_tokens"), max_decoding_steps=kw.get("max_decoding_steps", 390))
+        eos = model.EOS_TOKEN
+        tokens = [np.asarray(s, dtype=np.int32).reshape(-1) for s in seqs]
+        logp = [lp.cpu().numpy() for lp in res.logp]
+        greedy = [g.cpu().numpy() for g in res.greedy]
+        total = np.array([sampling.sequence_logprob(t[None], lp[None], eos)[0] for t, lp in zip(tokens, logp)])
+        count = np.array([int(sampling._counted(t[None], eos).sum()) for t in tokens])
+        mean = total / count
+        acc = np.array([float((g == t).mean()) for g, t in zip(greedy, tokens)])
+        best = int(np.argmax(total if select == "sum" else mean))       # (sampling.select_best's rule on rows of their own lengths)
+        return {"logp_sum": total, "logp_mean": mean, "token_accuracy": acc, "token_logprobs": logp, "tokens": tokens, "best": best,
+                "policy_timing": {"infer_ms": (time.perf_counter() - t0) * 1e3}}
+
     def infer(self, obs: dict, *, noise=None) -> dict:
         return self.infer_reasoning(obs)
 
@@ -642,7 +692,9 @@ def create_trained_policy_ar(*args, sample_kwargs: dict | None = None, language_
     answer drafts, ride along (`LAP.sample_tokens`); tokens and log-probabilities are unchanged, at any temperature, and
     "policy_timing" gains "spec_steps" and "spec_accepted".
     num_beams=N (the same as sample_kwargs={"num_beams": N}): beam search; with grammar=True the answer is the most probable sentence
-    of the format among the N beams kept (`beam.grammar_beam_step`), so it always parses."""
+    of the format among the N beams kept (`beam.grammar_beam_step`), so it always parses.
+    The policy's `score(obs, answers)` ranks GIVEN answer strings (or id sequences) for a request with this tokenizer
+    (`LAP.score_tokens`)."""
     from lap_amd import policy_io as pio
 
     base = create_trained_policy(*args, use_graph=False, **kwargs)
@@ -656,4 +708,4 @@ def create_trained_policy_ar(*args, sample_kwargs: dict | None = None, language_
     if num_beams is not None:
         sample_kwargs = dict(sample_kwargs or {}) | {"num_beams": num_beams}
     base._output_transform = pio.compose([pio.DetokenizeReasoning(tok), pio.CoTOutputs(language_action_format=language_action_format)])
-    return ARPolicy(base, sample_kwargs=sample_kwargs, use_graph=ar_graph)
+    return ARPolicy(base, sample_kwargs=sample_kwargs, use_graph=ar_graph, tokenizer=tok)

@@ -31,6 +31,9 @@ spread into its ms per token; the graphed figures subtract their own prefill gra
 turns; ms per step of each (mean and [min, max]) after their own prefill graphs, their ratio, the device time of the three beam
 launches on their own (events round single launches; the reorder at half the budget with every row moving), and how many steps of
 a decode had a non-identity reorder.
+--score S [S ...] adds teacher-forced scoring (`LAP.score_tokens(rows=S)`) of the bf16 graph's own answer for bf16 and every
+--weights value: ms per scored token and per step next to the plain decode lines of the same process, and the answer's total
+log-probability under each weight format.
 --speculate S [S ...] adds exact speculative decoding (`speculate=S`) for bf16 and every --weights value, in the same process as
 the plain graph of those weights: a GraphedTokenDecoder(speculate=S) called with the answer itself as the draft (full acceptance)
 and without a draft (zero acceptance, the price of a wrong guess), each as the mean and [min, max] of the timed repeats; ms per
@@ -91,6 +94,7 @@ ap.add_argument("--top-p", type=float, default=1.0, help="with --temperature: al
 ap.add_argument("--grammar", choices=["verbose"], default=None, help="also measure grammar-constrained decoding (verbose-with-rotation)")
 ap.add_argument("--jump-forward", type=int, nargs="+", default=[], help="with --grammar: also measure grammar + jump_forward at these step widths")
 ap.add_argument("--speculate", type=int, nargs="+", default=[], help="also measure exact speculative decoding at these verify-step widths")
+ap.add_argument("--score", type=int, nargs="+", default=[], help="also measure teacher-forced scoring (score_tokens) at these rows per step")
 a = ap.parse_args()
 if a.jump_forward and not a.grammar:
     ap.error("--jump-forward needs --grammar")
@@ -342,6 +346,29 @@ if a.speculate:
                 "break_even_draft_acceptance_rate": round((step_ms / plain_ms - 1) / (S - 1), 3),
                 "tokens_equal_plain_graph": bool(torch.equal(full_tok, answer) and torch.equal(zero_tok, answer))}
         speculative[wname] = rows
+scoring = {}
+if a.score:
+    # the candidate is the bf16 graph's own answer (--tokens ids); score_tokens launches its steps eagerly, so the line to compare
+    # with is the eagerly launched fused decode of this process (fused_ms_per_token), with the graphed one beside it
+    cand = got[0].tolist()
+    for wname in dict.fromkeys(["bf16", *a.weights]):
+        t_wfused = t_fused if wname == "bf16" else timeit(
+            lambda: model.sample_tokens(0, o, max_decoding_steps=N, decode="fused", decode_weights=wname), a.reps)
+        rows = {"fused_ms_per_token": round(per(t_wfused, t_pre), 3), "graphed_ms_per_token_bf16": round(g_ms, 3)}
+        for S in a.score:
+            sc = lambda: model.score_tokens(o, cand, rows=S, decode_weights=wname, max_decoding_steps=N)
+            ms = [timeit(sc, 1) for _ in range(max(a.reps, 3))]
+            t_sc = sum(ms) / len(ms)
+            steps = (N - 1 + S - 1) // S
+            res = sc()
+            rows[f"S{S}"] = {
+                "ms_per_scored_token": round(per(t_sc, t_pre), 3),
+                "ms_per_scored_token_min_max": [round(per(min(ms), t_pre), 3), round(per(max(ms), t_pre), 3)],
+                "step_ms": round((t_sc - t_pre) / steps, 3), "steps": steps, "total_ms": round(t_sc, 3),
+                "speedup_vs_fused_decode": round(per(t_wfused, t_pre) / per(t_sc, t_pre), 3),
+                "total_logp": round(float(res.total[0]), 4),
+                "token_accuracy": round(float((res.greedy[0] == got[0]).float().mean()), 4)}
+        scoring[wname] = rows
 grammar_res = {}
 if a.grammar:
     from lap_amd import grammar as G, lang_actions as LA
@@ -509,4 +536,5 @@ print(json.dumps({
     "algorithmic_bytes_per_token": bytes_tok, "floor_ms_per_token_at_6.29TBps": round(bytes_tok / 6.29e12 * 1e3, 3),
     "achieved_GBps_graphed": round(bytes_tok / (g_ms * 1e-3) / 1e9, 1),
     "share_of_6.29TBps": round(bytes_tok / (g_ms * 1e-3) / 6.29e12, 3), "down_proj_kwaves": a.kwaves} | sampled | ({"weights": quant} if quant else {})
-    | ({"allowed": a.allowed, "constrained": constrained} if constrained else {}) | logprobs | best_of | ({"beams": beams} if beams else {}) | ({"speculate": speculative} if speculative else {}) | grammar_res))
+    | ({"allowed": a.allowed, "constrained": constrained} if constrained else {}) | logprobs | best_of | ({"beams": beams} if beams else {}) | ({"speculate": speculative} if speculative else {})
+    | ({"score": scoring} if scoring else {}) | grammar_res))
