@@ -84,6 +84,17 @@ __device__ __forceinline__ void rope_rotate(float x1, float x2, float sn, float 
   r2 = __fadd_rn(__fmul_rn(x2, cs), __fmul_rn(x1, sn));
 }
 
+// Action-chunk inpainting (the Euler tails of serve_skinny.hip and elementwise.hip; not in the reference): a frozen row's value at
+// flow time t' is t' noise + (1 - t') known, as two rounded products and one rounded sum: fadd_rn(fmul_rn(t', noise),
+// fmul_rn(1 - t', known)).  Written with plain operators under `fp contract(off)`: the pragma reaches the operators of this body
+// only, and through the headers' __fmul_rn / __fadd_rn the compiler still fused the sum with one product.  The same three f32
+// operations on the host give the same bits.  t' == 0, the last step, gives `known` itself.
+__device__ __forceinline__ float inpaint_mix(float n, float k, float tp, float omtp) {
+#pragma clang fp contract(off)
+  const float a = tp * n, b = omtp * k;
+  return tp == 0.f ? k : a + b;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

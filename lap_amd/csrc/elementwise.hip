@@ -563,6 +563,16 @@ __global__ __launch_bounds__(256) void axpy_kernel(float* __restrict__ x, const 
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i < n) x[i] += dt * v[i];
 }
+// The Euler step with action-chunk inpainting (serve_skinny.hip `Inpaint`; the tail of the generic / partials routes and of pi0):
+// a row flagged in `mask` is set to t' noise + (1 - t') known (common.hpp inpaint_mix); every other element takes axpy_kernel's update.
+__global__ __launch_bounds__(256) void euler_inpaint_kernel(float* __restrict__ x, const float* __restrict__ v, float dt,
+                                                            const float* __restrict__ noise, const float* __restrict__ known,
+                                                            const unsigned char* __restrict__ mask, float tp, float omtp, int ad, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  if (mask[i / ad]) x[i] = inpaint_mix(noise[i], known[i], tp, omtp);
+  else x[i] += dt * v[i];
+}
 
 // ---------------------------------------------------------------- train-time image augmentation
 // models/model_adapter.py:118-151: augmax.Chain(RandomCrop(95 %), Resize(full), Rotate(+-5 deg), ColorJitter(0.2, 0.2, 0.2))
@@ -888,6 +898,17 @@ extern "C" int lap_mse_fwd_bwd(const float* v, const float* u, const float* coef
 extern "C" int lap_axpy_f32(float* x, const float* v, float dt, long long n, void* stream) {
   if (n <= 0) return LAP_ERR_ARG;
   hipLaunchKernelGGL(axpy_kernel, flat_grid(n), dim3(256), 0, S_, x, v, dt, n);
+  LAP_CHECK_LAUNCH();
+  return LAP_OK;
+}
+extern "C" int lap_euler_inpaint_f32(float* x, const float* v, float dt, const float* noise, const float* known, const unsigned char* mask,
+                                     float t_next, float one_minus_t_next, int rows, int action_dim, void* stream) {
+  if (!x || !v || !noise || !known || !mask || noise == x || known == x || rows <= 0 || action_dim <= 0 || t_next < 0.f || t_next > 1.f ||
+      one_minus_t_next < 0.f || one_minus_t_next > 1.f)
+    return LAP_ERR_ARG;
+  const long long n = (long long)rows * action_dim;
+  if (n >= (1ll << 31) - 256) return LAP_ERR_ARG;      // (an action chunk: the kernel indexes with int)
+  hipLaunchKernelGGL(euler_inpaint_kernel, flat_grid(n), dim3(256), 0, S_, x, v, dt, noise, known, mask, t_next, one_minus_t_next, action_dim, (int)n);
   LAP_CHECK_LAUNCH();
   return LAP_OK;
 }

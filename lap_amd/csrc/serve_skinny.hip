@@ -80,16 +80,35 @@ __global__ __launch_bounds__(256) void embed_actions_kernel(const float* __restr
   out[gid] = f2bf(a + b[c]);
 }
 
+// Action-chunk inpainting (not in the reference): the rows flagged in `mask` (one byte per action row, 0 / 1) are held on the known
+// trajectory, x_t = t' noise + (1 - t') known with t' the time AFTER this step (common.hpp inpaint_mix), instead of taking the
+// Euler update.
+struct Inpaint {
+  const float* noise;
+  const float* known;
+  const unsigned char* mask;
+  float tp, omtp;     // t', 1 - t': rounded from float64 on the host
+};
+
 // final adaptive RMSNorm (final_norm_1, gemma.py:525-527) -> action_out_proj in f32 (lap.py:298-299, 661-667) -> Euler
-// update x_t += dt * v_t (lap.py:669-672).  One wave per row; W_out f32 [ad][D].
-template <int NCH>
+// update x_t += dt * v_t (lap.py:669-672).  One wave per row; W_out f32 [ad][D].  INP: a frozen row (Inpaint) gets the
+// interpolation instead, and without `vout` its wave does nothing else; a free row runs the code of INP = false.
+template <int NCH, bool INP>
 __global__ __launch_bounds__(256) void final_norm_out_euler_kernel(const bf16* __restrict__ x, const bf16* __restrict__ mod, int mod_ld, int rps,
                                                                    const float* __restrict__ w, const float* __restrict__ b,
                                                                    float* __restrict__ xt, float* __restrict__ vout, int rows, int D, int ad,
-                                                                   float dt, float eps) {
+                                                                   float dt, float eps, Inpaint ip) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int row = blockIdx.x * 4 + wv;
   if (row >= rows) return;
+  bool frozen = false;
+  if constexpr (INP) {
+    frozen = ip.mask[row] != 0;
+    if (frozen && !vout) {
+      for (int a = lane; a < ad; a += 64) xt[row * ad + a] = inpaint_mix(ip.noise[row * ad + a], ip.known[row * ad + a], ip.tp, ip.omtp);
+      return;
+    }
+  }
   float v[NCH][8];
   float ss = 0.f;
 #pragma unroll
@@ -128,7 +147,8 @@ __global__ __launch_bounds__(256) void final_norm_out_euler_kernel(const bf16* _
     if (lane == 0) {
       const float vt = acc + b[a];
       if (vout) vout[row * ad + a] = vt;
-      xt[row * ad + a] += dt * vt;
+      if (INP && frozen) xt[row * ad + a] = inpaint_mix(ip.noise[row * ad + a], ip.known[row * ad + a], ip.tp, ip.omtp);
+      else xt[row * ad + a] += dt * vt;
     }
   }
 }
@@ -154,12 +174,12 @@ __device__ __forceinline__ float wave_sum_dpp_(float v) {
   return v;
 }
 
-template <int NCH, int AD>
+template <int NCH, int AD, bool INP>
 __global__ __launch_bounds__(64) void final_euler_embed_kernel(const bf16* __restrict__ x, const bf16* __restrict__ mod, int mod_ld, int rps,
                                                                const float* __restrict__ w, const float* __restrict__ b,
                                                                float* __restrict__ xt, float* __restrict__ vout, int rows, int D,
                                                                float dt, float eps, const float* __restrict__ w_in,
-                                                               const float* __restrict__ b_in, bf16* __restrict__ tokens) {
+                                                               const float* __restrict__ b_in, bf16* __restrict__ tokens, Inpaint ip) {
   // One wave per block: 50 rows on 50 CUs.  The launch is a chain of memory round trips (the row the denoise chain just wrote
   // device-scope, the modulation row, both projections' weights, x_t): everything that does not depend on the row is requested
   // FIRST, so the round trips overlap instead of queueing behind the reductions (separately: 12.2 + 4.9 us per Euler step).
@@ -171,6 +191,12 @@ __global__ __launch_bounds__(64) void final_euler_embed_kernel(const bf16* __res
   bf16x8 xr[NCH], sc[NCH], sh[NCH];
   f32x4 wo[AD][NCH][2];
   float bo[AD], xo[AD];
+  // INP: the row's flag, its noise and its known values are requested up front with the rest; the flag FIRST, since vector loads
+  // return in order and the branch on it must not wait behind the weights.  A frozen row (wave uniform: one row per wave) takes the
+  // interpolation as its new x_t and embeds THAT; without `vout` it skips the norm and the projection.
+  float nz[AD], kn[AD];
+  bool frozen = false;
+  if constexpr (INP) frozen = ip.mask[row] != 0;
 #pragma unroll
   for (int q = 0; q < NCH; ++q) {
     const int c = (lane + 64 * q) * 8;      // (D = 512 NCH: every chunk is inside the row)
@@ -185,46 +211,58 @@ __global__ __launch_bounds__(64) void final_euler_embed_kernel(const bf16* __res
   }
 #pragma unroll
   for (int a = 0; a < AD; ++a) { bo[a] = b[a]; xo[a] = xt[row * AD + a]; }
+  if constexpr (INP) {
+#pragma unroll
+    for (int a = 0; a < AD; ++a) { nz[a] = ip.noise[row * AD + a]; kn[a] = ip.known[row * AD + a]; }
+  }
   __builtin_amdgcn_sched_barrier(0);
 
-  float v[NCH][8];
-  float ss = 0.f;
-#pragma unroll
-  for (int q = 0; q < NCH; ++q)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { v[q][e] = (float)xr[q][e]; ss += v[q][e] * v[q][e]; }
-  ss = wave_sum_dpp_(ss);
-  const float r = 1.0f / sqrtf(ss / (float)D + eps);
-#pragma unroll
-  for (int q = 0; q < NCH; ++q)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[q][e] = round_bf16(v[q][e] * r * round_bf16(1.0f + (float)sc[q][e]) + (float)sh[q][e]);
   float xn[AD];
+  if (INP && frozen) {
 #pragma unroll
-  for (int a0 = 0; a0 < AD; a0 += AB) {
-    float acc[AB];
-#pragma unroll
-    for (int k = 0; k < AB; ++k) {
-      acc[k] = 0.f;
-      if (a0 + k >= AD) continue;
-#pragma unroll
-      for (int q = 0; q < NCH; ++q)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[k] += v[q][e] * wo[a0 + k][q][0][e] + v[q][4 + e] * wo[a0 + k][q][1][e];
+    for (int a = 0; a < AD; ++a) {
+      xn[a] = inpaint_mix(nz[a], kn[a], ip.tp, ip.omtp);
+      if (lane == 0) xt[row * AD + a] = xn[a];
     }
+  }
+  if (!(INP && frozen && !vout)) {
+    float v[NCH][8];
+    float ss = 0.f;
 #pragma unroll
-    for (int k = 0; k < AB; ++k) acc[k] = wave_sum_dpp_(acc[k]);
+    for (int q = 0; q < NCH; ++q)
 #pragma unroll
-    for (int k = 0; k < AB; ++k) {
-      const int a = a0 + k;
-      if (a >= AD) continue;
-      const float vt = acc[k] + bo[a];
-      float xv = xo[a];
-      xv += dt * vt;
-      xn[a] = xv;
-      if (lane == 0) {
-        if (vout) vout[row * AD + a] = vt;
-        xt[row * AD + a] = xv;
+      for (int e = 0; e < 8; ++e) { v[q][e] = (float)xr[q][e]; ss += v[q][e] * v[q][e]; }
+    ss = wave_sum_dpp_(ss);
+    const float r = 1.0f / sqrtf(ss / (float)D + eps);
+#pragma unroll
+    for (int q = 0; q < NCH; ++q)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[q][e] = round_bf16(v[q][e] * r * round_bf16(1.0f + (float)sc[q][e]) + (float)sh[q][e]);
+#pragma unroll
+    for (int a0 = 0; a0 < AD; a0 += AB) {
+      float acc[AB];
+#pragma unroll
+      for (int k = 0; k < AB; ++k) {
+        acc[k] = 0.f;
+        if (a0 + k >= AD) continue;
+#pragma unroll
+        for (int q = 0; q < NCH; ++q)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) acc[k] += v[q][e] * wo[a0 + k][q][0][e] + v[q][4 + e] * wo[a0 + k][q][1][e];
+      }
+#pragma unroll
+      for (int k = 0; k < AB; ++k) acc[k] = wave_sum_dpp_(acc[k]);
+#pragma unroll
+      for (int k = 0; k < AB; ++k) {
+        const int a = a0 + k;
+        if (a >= AD) continue;
+        const float vt = acc[k] + bo[a];
+        if (lane == 0 && vout) vout[row * AD + a] = vt;
+        if (INP && frozen) continue;      // (`vout` of a frozen row: x_t and xn are the interpolation's)
+        float xv = xo[a];
+        xv += dt * vt;
+        xn[a] = xv;
+        if (lane == 0) xt[row * AD + a] = xv;
       }
     }
   }
@@ -336,31 +374,39 @@ extern "C" int lap_serve_embed_actions(const float* x_t, const float* w_in, cons
   return LAP_OK;
 }
 
-extern "C" int lap_serve_final_euler_embed(const void* x, const void* mod, int mod_ld, int rows_per_sample, const float* w_out,
-                                           const float* b_out, float* x_t, float* v_t, int rows, int D, int action_dim, float dt,
-                                           float eps, const float* w_in, const float* b_in, void* tokens, void* stream) {
+namespace {
+bool inpaint_ok(const Inpaint& ip, const float* x_t) {
+  return ip.noise && ip.known && ip.mask && ip.noise != x_t && ip.known != x_t && ip.tp >= 0.f && ip.tp <= 1.f && ip.omtp >= 0.f && ip.omtp <= 1.f;
+}
+
+template <bool INP>
+int final_euler_embed(const void* x, const void* mod, int mod_ld, int rows_per_sample, const float* w_out, const float* b_out, float* x_t,
+                      float* v_t, int rows, int D, int action_dim, float dt, float eps, const float* w_in, const float* b_in, void* tokens,
+                      const Inpaint& ip, void* stream) {
   if (!x || !mod || !w_out || !b_out || !x_t || rows <= 0 || rows_per_sample <= 0 || D <= 0 || (D & 7) || (mod_ld & 7)) return LAP_ERR_ARG;
   if (action_dim != 7 && action_dim != 8) return LAP_ERR_ARG;      // (the projection weights of a row live in registers: 8 x D / 64 x 2 f32x4)
   if (tokens && (!w_in || !b_in)) return LAP_ERR_ARG;
   if (D != 1024) return LAP_ERR_ARG;                               // LAP-3B's action expert
   const dim3 grid(rows);
-#define GO(A) hipLaunchKernelGGL((final_euler_embed_kernel<2, A>), grid, dim3(64), 0, S_, (const bf16*)x, (const bf16*)mod, mod_ld, \
-                                 rows_per_sample, w_out, b_out, x_t, v_t, rows, D, dt, eps, w_in, b_in, (bf16*)tokens)
+  if (INP && !inpaint_ok(ip, x_t)) return LAP_ERR_ARG;
+#define GO(A) hipLaunchKernelGGL((final_euler_embed_kernel<2, A, INP>), grid, dim3(64), 0, S_, (const bf16*)x, (const bf16*)mod, mod_ld, \
+                                 rows_per_sample, w_out, b_out, x_t, v_t, rows, D, dt, eps, w_in, b_in, (bf16*)tokens, ip)
   if (action_dim == 7) GO(7); else GO(8);
 #undef GO
   LAP_CHECK_LAUNCH();
   return LAP_OK;
 }
 
-extern "C" int lap_serve_final_euler(const void* x, const void* mod, int mod_ld, int rows_per_sample, const float* w_out,
-                                     const float* b_out, float* x_t, float* v_t, int rows, int D, int action_dim, float dt,
-                                     float eps, void* stream) {
+template <bool INP>
+int final_euler(const void* x, const void* mod, int mod_ld, int rows_per_sample, const float* w_out, const float* b_out, float* x_t,
+                float* v_t, int rows, int D, int action_dim, float dt, float eps, const Inpaint& ip, void* stream) {
   if (!x || !mod || !w_out || !b_out || !x_t || rows <= 0 || rows_per_sample <= 0 || D <= 0 || (D & 7) || action_dim <= 0 || (mod_ld & 7))
     return LAP_ERR_ARG;
   const int nch = (D / 8 + 63) / 64;
   const dim3 grid((rows + 3) / 4);
-#define GO(N) hipLaunchKernelGGL(final_norm_out_euler_kernel<N>, grid, dim3(256), 0, S_, (const bf16*)x, (const bf16*)mod, mod_ld, \
-                                 rows_per_sample, w_out, b_out, x_t, v_t, rows, D, action_dim, dt, eps)
+  if (INP && !inpaint_ok(ip, x_t)) return LAP_ERR_ARG;
+#define GO(N) hipLaunchKernelGGL((final_norm_out_euler_kernel<N, INP>), grid, dim3(256), 0, S_, (const bf16*)x, (const bf16*)mod, mod_ld, \
+                                 rows_per_sample, w_out, b_out, x_t, v_t, rows, D, action_dim, dt, eps, ip)
   switch (nch) {
     case 1: GO(1); break;
     case 2: GO(2); break;
@@ -371,4 +417,35 @@ extern "C" int lap_serve_final_euler(const void* x, const void* mod, int mod_ld,
 #undef GO
   LAP_CHECK_LAUNCH();
   return LAP_OK;
+}
+}  // namespace
+
+extern "C" int lap_serve_final_euler_embed(const void* x, const void* mod, int mod_ld, int rows_per_sample, const float* w_out,
+                                           const float* b_out, float* x_t, float* v_t, int rows, int D, int action_dim, float dt,
+                                           float eps, const float* w_in, const float* b_in, void* tokens, void* stream) {
+  return final_euler_embed<false>(x, mod, mod_ld, rows_per_sample, w_out, b_out, x_t, v_t, rows, D, action_dim, dt, eps, w_in, b_in, tokens,
+                                  Inpaint{}, stream);
+}
+
+extern "C" int lap_serve_final_euler_embed_inpaint(const void* x, const void* mod, int mod_ld, int rows_per_sample, const float* w_out,
+                                                   const float* b_out, float* x_t, float* v_t, int rows, int D, int action_dim, float dt,
+                                                   float eps, const float* w_in, const float* b_in, void* tokens, const float* noise,
+                                                   const float* known, const unsigned char* mask, float t_next, float one_minus_t_next,
+                                                   void* stream) {
+  return final_euler_embed<true>(x, mod, mod_ld, rows_per_sample, w_out, b_out, x_t, v_t, rows, D, action_dim, dt, eps, w_in, b_in, tokens,
+                                 Inpaint{noise, known, mask, t_next, one_minus_t_next}, stream);
+}
+
+extern "C" int lap_serve_final_euler(const void* x, const void* mod, int mod_ld, int rows_per_sample, const float* w_out,
+                                     const float* b_out, float* x_t, float* v_t, int rows, int D, int action_dim, float dt,
+                                     float eps, void* stream) {
+  return final_euler<false>(x, mod, mod_ld, rows_per_sample, w_out, b_out, x_t, v_t, rows, D, action_dim, dt, eps, Inpaint{}, stream);
+}
+
+extern "C" int lap_serve_final_euler_inpaint(const void* x, const void* mod, int mod_ld, int rows_per_sample, const float* w_out,
+                                             const float* b_out, float* x_t, float* v_t, int rows, int D, int action_dim, float dt,
+                                             float eps, const float* noise, const float* known, const unsigned char* mask, float t_next,
+                                             float one_minus_t_next, void* stream) {
+  return final_euler<true>(x, mod, mod_ld, rows_per_sample, w_out, b_out, x_t, v_t, rows, D, action_dim, dt, eps,
+                           Inpaint{noise, known, mask, t_next, one_minus_t_next}, stream);
 }

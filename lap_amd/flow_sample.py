@@ -3,6 +3,8 @@ action expert against the cached prefix.  A denoise step runs on one of four rou
 chain (the expert's layers as one persistent launch), skinny (five fused launches per layer), partials (split-K slabs + fused
 consumers), generic (the layer loop of the train step; A/B tests); pi0 has a sampler of its own on the generic loop.
 The weights are read through the model (`W`, `F`), as `LAP._serving_weights` presents them.
+`inpaint=(known, mask)` (real-time chunking; the reference has no such option) holds the flagged action rows on a known trajectory:
+every route then ends its steps on the inpainting form of its Euler tail, and nothing else changes.
 """
 from __future__ import annotations
 
@@ -32,9 +34,48 @@ class Denoise(NamedTuple):
     kinfo: torch.Tensor             # ... of the prefix and suffix keys
     pos: torch.Tensor
     collect: dict | None
+    inp: "Inpaint | None" = None    # frozen rows (`sample_actions(inpaint=...)`): the steps then end on the inpainting tails
 
 
-def sample_actions(model: LAP, rng, observation, *, num_steps: int = 10, noise=None, collect=None, fused=True):
+class Inpaint(NamedTuple):
+    """Action-chunk inpainting, as the Euler tails take it: rows are the B * S action rows."""
+    noise: torch.Tensor             # f32 [B * S, ad]: the call's noise, kept beside its working copy x_t
+    known: torch.Tensor             # f32 [B * S, ad], model space
+    mask: torch.Tensor              # uint8 [B * S], 1 = frozen
+    times: list                     # per step (t', 1 - t') of `inpaint_times`
+
+
+def inpaint_times(nsteps: int):
+    """Per Euler step k the flow time AFTER it, t' = (nsteps - 1 - k) / nsteps, and 1 - t', both in float64 (python floats); the
+    kernels take them rounded to f32.  The last step's t' is 0 exactly: a frozen row of the result is `known` bit for bit."""
+    return [((nsteps - 1 - k) / nsteps, 1.0 - (nsteps - 1 - k) / nsteps) for k in range(nsteps)]
+
+
+def check_inpaint(inpaint, B: int, S: int, ad: int, device):
+    """`inpaint=(known, mask)` of `sample_actions` -> (known f32 [B, S, ad], mask uint8 [B, S]) on `device`, or ValueError: wrong
+    shapes (a batch mismatch included), non-finite `known`, mask values other than 0 / 1.  The values are not looked at while a
+    stream is being captured (that would synchronise): `serve.GraphedSampler` checks every request before it copies it in."""
+    try:
+        known, mask = inpaint
+    except (TypeError, ValueError):
+        raise ValueError("inpaint: expected None or a pair (known, mask)") from None
+    known, mask = torch.as_tensor(known), torch.as_tensor(mask)
+    if tuple(known.shape) != (B, S, ad):
+        raise ValueError(f"inpaint: known has shape {tuple(known.shape)}, expected [batch, action_horizon, action_dim] = {(B, S, ad)} (model space)")
+    if tuple(mask.shape) != (B, S):
+        raise ValueError(f"inpaint: mask has shape {tuple(mask.shape)}, expected [batch, action_horizon] = {(B, S)}")
+    if known.is_complex() or mask.is_complex():
+        raise ValueError(f"inpaint: known and mask must be real, got {known.dtype} / {mask.dtype}")
+    capturing = torch.device(device).type == "cuda" and torch.cuda.is_current_stream_capturing()
+    if not capturing:
+        if not bool(torch.isfinite(known).all()):
+            raise ValueError("inpaint: known has non-finite values")
+        if not bool(((mask == 0) | (mask == 1)).all()):
+            raise ValueError("inpaint: mask values must be 0 or 1")
+    return known.to(device, torch.float32).contiguous(), mask.to(device, torch.uint8).contiguous()
+
+
+def sample_actions(model: LAP, rng, observation, *, num_steps: int = 10, noise=None, collect=None, fused=True, inpaint=None):
     """`LAP.sample_actions` (documented there), with the weights as `_serving_weights` presents them (merged when the model has adapters)."""
     cfg, dev = model.config, model.device
     model.comm.wait_unit("small")
@@ -47,17 +88,24 @@ def sample_actions(model: LAP, rng, observation, *, num_steps: int = 10, noise=N
         raise ValueError(f"fused={fused!r}")
     if noise is None:
         noise = torch.randn((B, S, ad), generator=_gen(rng, dev), device=dev, dtype=torch.float32)
-    x_t = noise.to(dev, torch.float32).contiguous().clone()
-    x0, Pn, _ = model._embed_prefix(obs, False, tower=prefill.siglip_fwd_serve)
-    infos = model._serve_infos(obs, S)
-    if not cfg.pi05:
-        return _sample_actions_pi0(model, obs, x_t, x0, Pn, infos, num_steps, collect)
-    qinfo_p, kinfo_p, ppos, qinfo_s, kinfo_all, pos_all = infos
+    noise = noise.to(dev, torch.float32).contiguous()
+    x_t = noise.clone()
     dt = -1.0 / num_steps
     nsteps, t = 0, 1.0
     while t >= -dt / 2:  # lap.py:669-674 loop condition, unrolled on the host (the time grid is data independent)
         nsteps += 1
         t += dt
+    inp = None
+    if inpaint is not None:     # (at t = 1 a frozen row IS its noise: step 0 reads x_t as it stands)
+        known, mask = check_inpaint(inpaint, B, S, ad, dev)
+        if tuple(noise.shape) != (B, S, ad):
+            raise ValueError(f"inpaint: noise has shape {tuple(noise.shape)}, expected {(B, S, ad)}")
+        inp = Inpaint(noise.view(B * S, ad), known.view(B * S, ad), mask.view(B * S), inpaint_times(nsteps))
+    x0, Pn, _ = model._embed_prefix(obs, False, tower=prefill.siglip_fwd_serve)
+    infos = model._serve_infos(obs, S)
+    if not cfg.pi05:
+        return _sample_actions_pi0(model, obs, x_t, x0, Pn, infos, num_steps, collect, inp)
+    qinfo_p, kinfo_p, ppos, qinfo_s, kinfo_all, pos_all = infos
     # the adaRMS condition depends on the denoise time only: all steps' modulations in one pass over the adaRMS bank —
     # and on nothing else, so they are computed ONCE per (step count, parameter version) and kept: a captured sampler
     # (serve.GraphedSampler warms up before it captures) holds no time-MLP kernels at all (-0.25 ms per chunk)
@@ -80,7 +128,7 @@ def sample_actions(model: LAP, rng, observation, *, num_steps: int = 10, noise=N
         prefill.llm_prefill(model, x0, ppos, qinfo_p, kinfo_p, B, Pn, cache, kv_events=kv_events)
     else:
         llm_fwd(model, x0, None, None, ppos, qinfo_p, kinfo_p, B, Pn, 0, False, cache_out=cache)
-    d = Denoise(x_t, mods, dt, B, S, Pn, cache, rope_tab, qinfo_s, kinfo_all, pos_all, collect)
+    d = Denoise(x_t, mods, dt, B, S, Pn, cache, rope_tab, qinfo_s, kinfo_all, pos_all, collect, inp)
     chain = (fused == "skinny" and model.serve_chain and not overlap and dev.type == "cuda" and model.v.depth <= hip.CHAIN_MAX_DEPTH
              and hip.serve_chain_ok(B, S, model.e.width, model.e.mlp_dim, model.v.num_heads, model.v.head_dim, model.v.num_kv_heads, Pn))
     if chain:
@@ -128,9 +176,13 @@ def _step_chain(model: LAP, d: Denoise, step, x1, *, chain):
     final = (xf1, mod_slot(model, mod, 2 * v.depth), 0, S, model.F("act/out_w"), model.F("act/out_b"), d.x_t.view(B * S, ad), d.dt, v_t)
     if fuse_tail:
         x1 = torch.empty((B * S, e.width), dtype=torch.bfloat16, device=model.device) if step + 1 < d.mods.shape[0] else None
-        hip.serve_final_euler_embed(*final, w_in=model.F("act/in_w"), b_in=model.F("act/in_b"), tokens=x1)
+        embed = dict(w_in=model.F("act/in_w"), b_in=model.F("act/in_b"), tokens=x1)
+        if d.inp is None:
+            hip.serve_final_euler_embed(*final, **embed)
+        else:
+            hip.serve_final_euler_embed_inpaint(*final[:-1], *_frozen(d, step), v_out=v_t, **embed)
     else:
-        hip.serve_final_euler(*final)
+        _final_euler(d, step, final)
     if d.collect is not None:
         d.collect[f"v_t/{step}"] = v_t.view(B, S, ad)
     return x1
@@ -145,18 +197,31 @@ def _step_skinny(model: LAP, d: Denoise, step, _x1, *, start, kv_events):
     main = torch.cuda.current_stream() if side else None
     if side:
         model._den.wait_event(start)
-        for tns in (d.x_t, d.mods, d.rope_tab, d.qinfo, d.kinfo):
+        for tns in (d.x_t, d.mods, d.rope_tab, d.qinfo, d.kinfo, *(d.inp[:3] if d.inp is not None else ())):
             tns.record_stream(model._den)
     with (torch.cuda.stream(model._den) if side else contextlib.nullcontext()):
         x1 = hip.serve_embed_actions(d.x_t.view(B * S, ad), model.F("act/in_w"), model.F("act/in_b"))
         xf1 = expert_denoise_skinny(model, x1, mod, d.qinfo, d.kinfo, B, d.Pn, S, d.cache, d.rope_tab, kv_events=kv_events if side else None)
         v_t = torch.empty((B * S, ad), dtype=torch.float32, device=model.device) if d.collect is not None else None
-        hip.serve_final_euler(xf1, mod_slot(model, mod, 2 * model.v.depth), 0, S, model.F("act/out_w"), model.F("act/out_b"),
-                              d.x_t.view(B * S, ad), d.dt, v_t)
+        _final_euler(d, step, (xf1, mod_slot(model, mod, 2 * model.v.depth), 0, S, model.F("act/out_w"), model.F("act/out_b"),
+                               d.x_t.view(B * S, ad), d.dt, v_t))
     if side:
         main.wait_stream(model._den)
     if d.collect is not None:
         d.collect[f"v_t/{step}"] = v_t.view(B, S, ad)
+
+
+def _frozen(d: Denoise, step):
+    """(noise, known, mask, (t', 1 - t')) of step `step` for the inpainting tails."""
+    return d.inp.noise, d.inp.known, d.inp.mask, d.inp.times[step]
+
+
+def _final_euler(d: Denoise, step, final):
+    """`serve_final_euler` on `final` = (its arguments ..., v_out), or its inpainting form when rows are frozen."""
+    if d.inp is None:
+        hip.serve_final_euler(*final)
+    else:
+        hip.serve_final_euler_inpaint(*final[:-1], *_frozen(d, step), v_out=final[-1])
 
 
 def _step_partials(model: LAP, d: Denoise, step, _x1):
@@ -179,10 +244,13 @@ def _euler_f32(model: LAP, d: Denoise, step, pre1):
     v_t = model._lin32(hip.cast_bf16_to_f32(pre1), "act/out_w", "act/out_b")
     if d.collect is not None:
         d.collect[f"v_t/{step}"] = v_t.view(d.x_t.shape).clone()
-    hip.axpy_f32(d.x_t, v_t, d.dt)
+    if d.inp is None:
+        hip.axpy_f32(d.x_t, v_t, d.dt)
+    else:
+        hip.euler_inpaint_f32(d.x_t.view(v_t.shape), v_t, d.dt, *_frozen(d, step))
 
 
-def _sample_actions_pi0(model: LAP, obs, x_t, x0, Pn, infos, num_steps, collect):
+def _sample_actions_pi0(model: LAP, obs, x_t, x0, Pn, infos, num_steps, collect, inp=None):
     """`sample_actions` for pi0 (`pi05=False`): the suffix is [state token | action tokens mixed with the time embedding], embedded anew
     at every Euler step; the expert's layers run on the generic layer loop (plain norms and residuals) against the prefix cache.
     Functional path: no fused serving kernels, no hipGraph chain (no registry config of the reference is pi0)."""
@@ -203,7 +271,10 @@ def _sample_actions_pi0(model: LAP, obs, x_t, x0, Pn, infos, num_steps, collect)
         v_t = model._lin32(hip.cast_bf16_to_f32(pre1), "act/out_w", "act/out_b")
         if collect is not None:
             collect[f"v_t/{step}"] = v_t.view(B, S, ad).clone()
-        hip.axpy_f32(x_t, v_t, dt)
+        if inp is None:
+            hip.axpy_f32(x_t, v_t, dt)
+        else:
+            hip.euler_inpaint_f32(x_t.view(B * S, ad), v_t, dt, inp.noise, inp.known, inp.mask, inp.times[step])
         t += dt
         step += 1
     return x_t

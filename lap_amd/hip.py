@@ -194,6 +194,8 @@ SIGNATURES: dict[str, list] = {
     "lap_panel_gemm_pf": [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _f, _i, _i, _i, _i, _i, _vp, _i, _vp, _ll, _vp],
     "lap_panel_gemm": [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _f, _i, _i, _i, _i, _i, _vp, _i, _vp],
     "lap_serve_final_euler": [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp],
+    "lap_serve_final_euler_inpaint": [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _f, _f, _vp],
+    "lap_serve_final_euler_embed_inpaint": [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp],
     "lap_ce_chunk_update": [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "lap_ce_chunk_update_argmax": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "lap_token_metrics": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp],
@@ -212,6 +214,7 @@ SIGNATURES: dict[str, list] = {
     "lap_swish_bwd": [_vp, _vp, _vp, _ll, _vp],
     "lap_mse_fwd_bwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
     "lap_axpy_f32": [_vp, _vp, _f, _ll, _vp],
+    "lap_euler_inpaint_f32": [_vp, _vp, _f, _vp, _vp, _vp, _f, _f, _i, _i, _vp],
     "lap_lora_down": [_vp, _i, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _f, _vp],
     "lap_lora_up_add": [_vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _f, _vp],
     "lap_lora_wgrad": [_vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _ll, _vp],
@@ -1291,6 +1294,47 @@ def serve_final_euler_embed(x, mod, mod_ld, rps, w_out, b_out, x_t, dt, v_out=No
     rows, D = x.shape
     call("lap_serve_final_euler_embed", _p(x), _p(mod), mod_ld, rps, _p(w_out), _p(b_out), _p(x_t), _p(v_out), rows, D, w_out.shape[0], float(dt), float(eps),
          _p(w_in), _p(b_in), _p(tokens))
+
+
+def _inpaint_args(x_t, noise, known, mask, t_next):
+    """Checked (noise, known, mask, t', 1 - t') of the inpainting tails: x_t f32 [rows, ad]; noise, known like it; mask uint8 [rows]."""
+    _req(x_t, torch.float32, "x_t")
+    if x_t.dim() != 2 or not x_t.is_contiguous():
+        raise ValueError(f"x_t: expected a contiguous [rows, action_dim] tensor, got {tuple(x_t.shape)}")
+    for name, t in (("noise", noise), ("known", known)):
+        _req(t, torch.float32, name)
+        if t.shape != x_t.shape or not t.is_contiguous():
+            raise ValueError(f"{name}: expected a contiguous {tuple(x_t.shape)} tensor, got {tuple(t.shape)}")
+    _req(mask, torch.uint8, "mask")
+    if mask.dim() != 1 or mask.shape[0] != x_t.shape[0] or not mask.is_contiguous():
+        raise ValueError(f"mask: expected a contiguous [{x_t.shape[0]}] tensor (one flag per row), got {tuple(mask.shape)}")
+    tp, omtp = (float(t) for t in t_next)
+    return _p(noise), _p(known), _p(mask), tp, omtp
+
+
+def serve_final_euler_inpaint(x, mod, mod_ld, rps, w_out, b_out, x_t, dt, noise, known, mask, t_next, v_out=None, eps=1e-6):
+    """serve_final_euler with the rows flagged in `mask` (uint8 [rows]) set to t' noise + (1 - t') known, `t_next` = (t', 1 - t')
+    rounded from float64 (`flow_sample.inpaint_times`); the free rows are bit-identical to serve_final_euler.  Not in the reference."""
+    rows, D = x.shape
+    call("lap_serve_final_euler_inpaint", _p(x), _p(mod), mod_ld, rps, _p(w_out), _p(b_out), _p(x_t), _p(v_out), rows, D, w_out.shape[0], float(dt),
+         float(eps), *_inpaint_args(x_t, noise, known, mask, t_next))
+
+
+def serve_final_euler_embed_inpaint(x, mod, mod_ld, rps, w_out, b_out, x_t, dt, noise, known, mask, t_next, v_out=None, eps=1e-6,
+                                    w_in=None, b_in=None, tokens=None):
+    """serve_final_euler_embed with frozen rows as in serve_final_euler_inpaint; a frozen row's interpolation is what `tokens` embeds."""
+    rows, D = x.shape
+    call("lap_serve_final_euler_embed_inpaint", _p(x), _p(mod), mod_ld, rps, _p(w_out), _p(b_out), _p(x_t), _p(v_out), rows, D, w_out.shape[0],
+         float(dt), float(eps), _p(w_in), _p(b_in), _p(tokens), *_inpaint_args(x_t, noise, known, mask, t_next))
+
+
+def euler_inpaint_f32(x_t, v, dt, noise, known, mask, t_next):
+    """axpy_f32 on x_t, v [rows, ad] with the frozen rows of serve_final_euler_inpaint (the same expression: the same bits)."""
+    _req(v, torch.float32, "v")
+    if v.shape != x_t.shape or not v.is_contiguous():
+        raise ValueError(f"v: expected a contiguous {tuple(x_t.shape)} tensor, got {tuple(v.shape)}")
+    args = _inpaint_args(x_t, noise, known, mask, t_next)
+    call("lap_euler_inpaint_f32", _p(x_t), _p(v), float(dt), *args, x_t.shape[0], x_t.shape[1])
 
 
 def serve_set_variant(feature_tiles: int):

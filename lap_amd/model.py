@@ -645,13 +645,23 @@ class LAP:
 
     # ================================================================== serving
     @torch.no_grad()
-    def sample_actions(self, rng, observation, *, num_steps: int = 10, noise=None, collect=None, fused=True):
+    def sample_actions(self, rng, observation, *, num_steps: int = 10, noise=None, collect=None, fused=True, inpaint=None):
         """lap.py:605-675: prefix prefill once -> per-layer K/V kept in HBM -> `num_steps` Euler steps of the action
         expert attending to [cached prefix | fresh suffix] as two key segments (the reference concatenates, gemma.py:228-230).
         `fused`: True = the fastest denoise-step kernels the shapes allow ("skinny" fused projections for the LAP-3B action
-        expert, else "partials" = split-K partial slabs + fused consumers); False = the generic layer path (A/B tests)."""
+        expert, else "partials" = split-K partial slabs + fused consumers); False = the generic layer path (A/B tests).
+        `inpaint` (NOT in the reference, whose sampler has no such option): None, or `(known, mask)` for real-time chunking by
+        inpainting — `known` f32 [B, S, action_dim] in MODEL space (normalised, padded to action_dim) and `mask` [B, S] of 0 / 1, one
+        flag per action row, 1 = frozen.  With t = 1 noise, t = 0 data, a frozen row is set after Euler step k of n to
+        t' noise + (1 - t') known, t' = (n - 1 - k) / n (float64 on the host, passed as two f32; evaluated as two rounded products and
+        a rounded sum), so it stays on the known trajectory while the free rows, which update as always, attend to it; the last
+        step has t' = 0 and a frozen row of the result is `known` bit for bit.  Frozen rows stay in the sequence as action tokens: no
+        attention kernel changes.  `collect` still records the model's v_t for every row.  Wrong shapes, a batch mismatch, non-finite
+        `known` or mask values other than 0 / 1 raise ValueError.  `lap_amd.chunking.shift_chunk` builds the pair from the previous
+        chunk; that is meaningful only when the action representation does not depend on the new observation's frame."""
         with self._serving_weights():
-            return self._sample_actions(rng, observation, num_steps=num_steps, noise=noise, collect=collect, fused=fused)
+            kw = {} if inpaint is None else {"inpaint": inpaint}
+            return self._sample_actions(rng, observation, num_steps=num_steps, noise=noise, collect=collect, fused=fused, **kw)
 
     def _sample_actions(self, rng, observation, **kw):      # on the weights as they are (outside `_serving_weights`: base + adapters)
         from lap_amd import flow_sample     # (it imports this module)

@@ -4,7 +4,8 @@ openpi.serving.websocket_policy_server, absent submodule: [UPSTREAM-RECALL] SURV
 Protocol: after the websocket handshake the server sends one binary frame with the msgpack-numpy packed policy metadata;
 then, per request, the client sends a packed observation dict and receives the packed result of `policy.infer(obs)` plus
 `server_timing` ({"infer_ms", "prev_total_ms"}).  An exception inside `infer` is reported as a text frame with the traceback
-followed by a close frame with code 1011.  `GET /healthz` answers a plain `200 OK`.
+followed by a close frame with code 1011.  `GET /healthz` answers a plain `200 OK`.  The request dict reaches `infer` untouched:
+an `"inpaint"` key in it (real-time chunking, `serve.Policy`) is the policy's to read, and requests without it are served as ever.
 
 The `websockets` package is not part of this image, so the RFC 6455 subset the protocol needs (handshake, masked client
 frames, fragmentation, ping / pong / close, unmasked server frames) is implemented on asyncio streams directly.  Requests are
