@@ -610,6 +610,7 @@ int set_lds(K kernel, int bytes) {
 }
 
 #include "attention_serve.hpp"
+#include "attention_serve_shared.hpp"
 #include "serve_chain.hpp"
 #include "serve_chain_tp.hpp"
 
@@ -803,6 +804,38 @@ extern "C" int lap_attention_serve(const lap_attn_fwd_args* a, void* stream) {
   p.lpart = a->scratch + (long long)a->nsplit * a->B * a->q_len[1] * a->NH * a->HD;
   p.B = a->B; p.NH = a->NH; p.NKV = a->NKV;
   return launch_serve(p, (hipStream_t)stream);
+}
+
+// Best-of-N flow sampling: lap_attention_serve for N = a->B candidates of one observation whose cached prefix exists once.
+extern "C" int lap_attention_serve_shared(const lap_attn_fwd_args* a, int form, void* stream) {
+  if (!a || !check_common(a->B, a->NH, a->NKV, a->HD, a->q_len, a->k_len)) return LAP_ERR_ARG;
+  if (a->HD != 256 || a->q_len[0] != 0 || a->q_len[1] < 1 || a->q_len[1] > 64 || a->lse || !a->q[1] || !a->o[1]) return LAP_ERR_ARG;
+  if (a->B > SS_MAX_N || a->k_len[0] < 1 || a->k_len[1] < 1 || (form != 0 && form != 1)) return LAP_ERR_ARG;
+  AttnP p = {};
+  for (int s = 0; s < 2; ++s) {
+    p.q[s] = (const bf16*)a->q[s]; p.o[s] = (bf16*)a->o[s];
+    p.k[s] = (const bf16*)a->k[s]; p.v[s] = (const bf16*)a->v[s];
+    p.qlen[s] = a->q_len[s]; p.klen[s] = a->k_len[s];
+    p.q_rs[s] = a->q_rs[s] ? a->q_rs[s] : a->NH * a->HD;
+    p.o_rs[s] = a->o_rs[s] ? a->o_rs[s] : a->NH * a->HD;
+    p.kv_rs[s] = a->kv_rs[s] ? a->kv_rs[s] : a->NKV * a->HD;
+    if ((p.q_rs[s] | p.o_rs[s] | p.kv_rs[s]) & 7) return LAP_ERR_ARG;
+    if (p.q_rs[s] < a->NH * a->HD || p.o_rs[s] < a->NH * a->HD || p.kv_rs[s] < a->NKV * a->HD) return LAP_ERR_ARG;
+    if (!p.k[s] || !p.v[s]) return LAP_ERR_ARG;
+    if ((long long)p.klen[s] * p.kv_rs[s] * 2 >= 0x7fffffffLL) return LAP_ERR_ARG;
+  }
+  if ((a->qinfo == nullptr) != (a->kinfo == nullptr)) return LAP_ERR_ARG;
+  p.qinfo = a->qinfo; p.kinfo = a->kinfo; p.scale = a->scale;
+  if (!(a->scale > 0.f)) return LAP_ERR_ARG;
+  // the runs of lap_attention_serve at batch N: the caller passes ITS cap
+  if (a->nsplit < 1 || a->nsplit != lap_attention_serve_splits(a->k_len[0], a->k_len[1], a->B, a->NH, a->q_len[1])) return LAP_ERR_ARG;
+  const long long need = (long long)a->nsplit * a->B * a->q_len[1] * a->NH * (a->HD + 1);
+  if (!a->scratch || a->scratch_floats < need) return LAP_ERR_ARG;
+  p.nsplit = a->nsplit; p.hsplit = 1;
+  p.part = a->scratch;
+  p.lpart = a->scratch + (long long)a->nsplit * a->B * a->q_len[1] * a->NH * a->HD;
+  p.B = a->B; p.NH = a->NH; p.NKV = a->NKV;
+  return launch_serve_shared(p, form, (hipStream_t)stream);
 }
 
 // ---- the denoise step's 18 layers in one persistent launch (serve_chain.hpp)

@@ -5,6 +5,9 @@ consumers), generic (the layer loop of the train step; A/B tests); pi0 has a sam
 The weights are read through the model (`W`, `F`), as `LAP._serving_weights` presents them.
 `inpaint=(known, mask)` (real-time chunking; the reference has no such option) holds the flagged action rows on a known trajectory:
 every route then ends its steps on the inpainting form of its Euler tail, and nothing else changes.
+`num_samples=N` (best-of-N; not in the reference either) draws N candidate chunks of ONE observation from one batch-1 prefill
+(`_sample_candidates`): the steps run on N * S rows, and on the skinny route the attention reads the single prefix cache
+(`hip.attention_serve_shared`); `select=` then picks one on the device (`hip.action_select`, specified by `action_select.py`).
 """
 from __future__ import annotations
 
@@ -15,6 +18,7 @@ from typing import NamedTuple
 import torch
 
 from lap_amd import hip, prefill
+from lap_amd.action_select import check_select
 from lap_amd.joint_layers import llm_fwd, mod_slot
 from lap_amd.model import LAP, _gen
 from lap_amd.observation import preprocess_observation
@@ -35,6 +39,7 @@ class Denoise(NamedTuple):
     pos: torch.Tensor
     collect: dict | None
     inp: "Inpaint | None" = None    # frozen rows (`sample_actions(inpaint=...)`): the steps then end on the inpainting tails
+    shared: bool = False            # B candidates of ONE observation: `cache` holds the prefix once (`_sample_candidates`, skinny route)
 
 
 class Inpaint(NamedTuple):
@@ -75,13 +80,34 @@ def check_inpaint(inpaint, B: int, S: int, ad: int, device):
     return known.to(device, torch.float32).contiguous(), mask.to(device, torch.uint8).contiguous()
 
 
-def sample_actions(model: LAP, rng, observation, *, num_steps: int = 10, noise=None, collect=None, fused=True, inpaint=None):
+def check_num_samples(num_samples, B: int, pi05: bool) -> int:
+    """`num_samples=` of `sample_actions` -> N (None = 1), or ValueError: not an integer in 1 .. 8, or N > 1 with a batch of
+    observations or with pi0 (whose suffix carries the state token: no shared-prefix route)."""
+    if num_samples is None:
+        return 1
+    if isinstance(num_samples, bool) or not isinstance(num_samples, int) or not 1 <= num_samples <= 8:
+        raise ValueError(f"num_samples: expected an integer in 1 .. 8, got {num_samples!r}")
+    if num_samples > 1 and B != 1:
+        raise ValueError(f"num_samples = {num_samples} draws candidates for ONE observation: got a batch of {B}")
+    if num_samples > 1 and not pi05:
+        raise ValueError("num_samples > 1 needs pi05=True (the pi0 sampler has no candidate route)")
+    return num_samples
+
+
+def sample_actions(model: LAP, rng, observation, *, num_steps: int = 10, noise=None, collect=None, fused=True, inpaint=None,
+                   num_samples=None, select=None, coherence=None, share_prefix=True, _select_out=None):
     """`LAP.sample_actions` (documented there), with the weights as `_serving_weights` presents them (merged when the model has adapters)."""
     cfg, dev = model.config, model.device
     model.comm.wait_unit("small")
     obs = preprocess_observation(observation, train=False, image_keys=cfg.image_keys, image_resolution=cfg.image_resolution)
     B = obs.tokenized_prompt.shape[0]
     S, ad = model.action_horizon, model.action_dim
+    N = check_num_samples(num_samples, B, cfg.pi05)
+    mode, coh = check_select(select, coherence, S, ad)
+    if N > 1:
+        return _sample_candidates(model, rng, obs, N, num_steps, noise, collect, fused, inpaint, mode, coh, share_prefix, _select_out)
+    if mode is not None:
+        raise ValueError(f"select={select!r} chooses among candidates: it needs num_samples > 1")
     if fused is True:
         fused = "skinny" if hip.serve_supported(model.e.width, model.v.head_dim, model.e.mlp_dim, model.v.num_heads) else "partials"
     if fused not in (False, "skinny", "partials"):
@@ -143,6 +169,76 @@ def sample_actions(model: LAP, rng, observation, *, num_steps: int = 10, noise=N
     return x_t
 
 
+def _sample_candidates(model: LAP, rng, obs, N, num_steps, noise, collect, fused, inpaint, mode, coh, share_prefix, select_out):
+    """`sample_actions(num_samples=N > 1)`: N candidate chunks of one observation.  The prefix is prefilled ONCE at batch 1 (the fast
+    prefill and its K / V events as in the plain call); the Euler steps run on N * S rows with S rows per sample — the rope table, the
+    info words and the positions are the batch-1 ones N times — on the skinny, partials or generic route, never on the chain.
+    share_prefix (skinny route only): the attention reads the single cache (`hip.attention_serve_shared`); otherwise, and on the
+    other routes, the cache is replicated N times behind the prefill and `hip.attention_fwd` runs at batch N: same bits.
+    Returns [N, S, ad], or with `mode` the selected chunk [1, S, ad]."""
+    dev = model.device
+    S, ad = model.action_horizon, model.action_dim
+    if fused is True:
+        fused = "skinny" if hip.serve_supported(model.e.width, model.v.head_dim, model.e.mlp_dim, model.v.num_heads) else "partials"
+    if fused not in (False, "skinny", "partials"):
+        raise ValueError(f"fused={fused!r}")
+    if noise is None:
+        noise = torch.randn((N, S, ad), generator=_gen(rng, dev), device=dev, dtype=torch.float32)
+    noise = torch.as_tensor(noise).to(dev, torch.float32).contiguous()
+    if tuple(noise.shape) != (N, S, ad):
+        raise ValueError(f"num_samples: noise has shape {tuple(noise.shape)}, expected [num_samples, action_horizon, action_dim] = {(N, S, ad)}")
+    x_t = noise.clone()
+    dt = -1.0 / num_steps
+    nsteps, t = 0, 1.0
+    while t >= -dt / 2:
+        nsteps += 1
+        t += dt
+    inp = None
+    if inpaint is not None:     # one (known, mask) for every candidate
+        known, mask = check_inpaint(inpaint, 1, S, ad, dev)
+        inp = Inpaint(noise.view(N * S, ad), known.expand(N, S, ad).reshape(N * S, ad), mask.expand(N, S).reshape(N * S), inpaint_times(nsteps))
+    if coh is not None:
+        coh = tuple(torch.as_tensor(c).to(dev, torch.float32).contiguous() for c in coh)
+    x0, Pn, _ = model._embed_prefix(obs, False, tower=prefill.siglip_fwd_serve)
+    qinfo_p, kinfo_p, ppos, qinfo_s, kinfo_all, pos_all = model._serve_infos(obs, S)
+    rep = lambda w: w.expand(N, w.shape[1]).contiguous()
+    qinfo_s, kinfo_all, pos_all = rep(qinfo_s), rep(kinfo_all), rep(pos_all)
+    mods = serve_mods(model, nsteps, dt)
+    rope_tab = hip.rope_table(pos_all, N, S, pos_all.shape[1], pos_all.shape[1] - S, model.v.head_dim) if fused else None
+    shared = bool(share_prefix) and fused == "skinny"
+    cache = []
+    fast_prefill = model.serve_fusions and collect is None and model.gemm_dtype == "bf16"
+    # step 0 beside the prefill, as in the plain call: only where the steps read the prefill's own cache tensors
+    overlap = fast_prefill and shared and model.serve_overlap and dev.type == "cuda" and nsteps > 1
+    kv_events = [] if overlap else None
+    start = None
+    if overlap:
+        if model._den is None:
+            model._den = torch.cuda.Stream(dev)
+        start = torch.cuda.Event()
+        start.record()
+    if fast_prefill:
+        prefill.llm_prefill(model, x0, ppos, qinfo_p, kinfo_p, 1, Pn, cache, kv_events=kv_events)
+    else:
+        llm_fwd(model, x0, None, None, ppos, qinfo_p, kinfo_p, 1, Pn, 0, False, cache_out=cache)
+    if not shared:
+        cache = [(k.repeat(N, 1), v.repeat(N, 1)) for k, v in cache]
+    d = Denoise(x_t, mods, dt, N, S, Pn, cache, rope_tab, qinfo_s, kinfo_all, pos_all, collect, inp, shared)
+    if fused == "skinny":
+        route = functools.partial(_step_skinny, start=start, kv_events=kv_events)
+    else:
+        route = _step_partials if fused == "partials" else _step_generic
+    for step in range(nsteps):
+        route(model, d, step, None)
+    if mode is None:
+        return x_t
+    scores, index, best = hip.action_select(x_t, mode, *(coh or ()))
+    for out in (collect, select_out):
+        if out is not None:
+            out.update(candidates=x_t, scores=scores, index=index)
+    return best.view(1, S, ad)
+
+
 def _chain_setup(model: LAP, d: Denoise):
     """The one-launch chain's barrier counters, weights (packed images or the row-major ones) and scratch -> (weights, tp)."""
     v, e = model.v, model.e
@@ -201,7 +297,8 @@ def _step_skinny(model: LAP, d: Denoise, step, _x1, *, start, kv_events):
             tns.record_stream(model._den)
     with (torch.cuda.stream(model._den) if side else contextlib.nullcontext()):
         x1 = hip.serve_embed_actions(d.x_t.view(B * S, ad), model.F("act/in_w"), model.F("act/in_b"))
-        xf1 = expert_denoise_skinny(model, x1, mod, d.qinfo, d.kinfo, B, d.Pn, S, d.cache, d.rope_tab, kv_events=kv_events if side else None)
+        xf1 = expert_denoise_skinny(model, x1, mod, d.qinfo, d.kinfo, B, d.Pn, S, d.cache, d.rope_tab, kv_events=kv_events if side else None,
+                                    shared=d.shared)
         v_t = torch.empty((B * S, ad), dtype=torch.float32, device=model.device) if d.collect is not None else None
         _final_euler(d, step, (xf1, mod_slot(model, mod, 2 * model.v.depth), 0, S, model.F("act/out_w"), model.F("act/out_b"),
                                d.x_t.view(B * S, ad), d.dt, v_t))
@@ -309,11 +406,12 @@ def expert_denoise_partials(model: LAP, x1, mod, pos, qinfo, kinfo, B, Pn, S, ca
     return h   # slot 2L is final_norm_1: h == final adaRMS norm of the last layer's output
 
 
-def expert_denoise_skinny(model: LAP, x1, mod, qinfo, kinfo, B, Pn, S, cache, rope_tab, kv_events=None):
+def expert_denoise_skinny(model: LAP, x1, mod, qinfo, kinfo, B, Pn, S, cache, rope_tab, kv_events=None, shared=False):
     """The same 18 layers on the skinny-M fused projections (csrc/serve_skinny.hip): five launches per layer —
     [adaRMS + qkv + RoPE/split] -> attention -> [out-proj + gated residual] -> [adaRMS + gate|up + GeGLU] ->
     [down-proj + gated residual] — with no f32 partial slabs in between.  Returns the last layer's residual stream
-    (the final adaRMS norm is part of lap_serve_final_euler)."""
+    (the final adaRMS norm is part of lap_serve_final_euler).  `shared`: the B samples are candidates of one observation and `cache`
+    holds its prefix once."""
     v, e = model.v, model.e
     NH, HD, KV = v.num_heads, v.head_dim, v.num_kv_heads
     We = e.width
@@ -327,8 +425,11 @@ def expert_denoise_skinny(model: LAP, x1, mod, qinfo, kinfo, B, Pn, S, cache, ro
         if kv_events is not None:     # running beside the prefill (first denoise step): layer l's cache is ready at its event
             torch.cuda.current_stream().wait_event(kv_events[l])
             ck.record_stream(torch.cuda.current_stream()); cv.record_stream(torch.cuda.current_stream())
-        o, _ = hip.attention_fwd([None, q], [ck, k], [cv, vv], [0, S], [Pn, S], B, NH, KV, HD, qinfo, kinfo, need_lse=False)
-        xa = hip.serve_proj_residual(o[1], model.W(p + "wo1"), x, slot(2 * l)[:, 2 * We:], 0, S)
+        if shared:
+            o1 = hip.attention_serve_shared(q, k, vv, ck, cv, B, S, Pn, NH, KV, HD, qinfo, kinfo)
+        else:
+            o1 = hip.attention_fwd([None, q], [ck, k], [cv, vv], [0, S], [Pn, S], B, NH, KV, HD, qinfo, kinfo, need_lse=False)[0][1]
+        xa = hip.serve_proj_residual(o1, model.W(p + "wo1"), x, slot(2 * l)[:, 2 * We:], 0, S)
         act = hip.serve_gate_up(xa, slot(2 * l + 1), 0, S, model.W(p + "wgu1"))
         x = hip.serve_proj_residual(act, model.W(p + "wd1"), xa, slot(2 * l + 1)[:, 2 * We:], 0, S)
     return x

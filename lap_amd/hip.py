@@ -170,6 +170,7 @@ SIGNATURES: dict[str, list] = {
     "lap_attention_fwd": [C.POINTER(AttnFwdArgs), _vp],
     "lap_attention_serve_splits": [_i, _i, _i, _i, _i],
     "lap_attention_serve": [C.POINTER(AttnFwdArgs), _vp],
+    "lap_attention_serve_shared": [C.POINTER(AttnFwdArgs), _i, _vp],
     "lap_attention_bwd": [C.POINTER(AttnBwdArgs), _vp],
     "lap_attention_set_variant": [_i],
     "lap_rope_table": [_vp, _vp, _i, _i, _i, _i, _i, _vp],
@@ -215,6 +216,7 @@ SIGNATURES: dict[str, list] = {
     "lap_mse_fwd_bwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
     "lap_axpy_f32": [_vp, _vp, _f, _ll, _vp],
     "lap_euler_inpaint_f32": [_vp, _vp, _f, _vp, _vp, _vp, _f, _f, _i, _i, _vp],
+    "lap_action_select": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "lap_lora_down": [_vp, _i, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _f, _vp],
     "lap_lora_up_add": [_vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _f, _vp],
     "lap_lora_wgrad": [_vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _ll, _vp],
@@ -860,6 +862,45 @@ def attention_fwd(q, k, v, q_len, k_len, B, NH, NKV, HD, qinfo=None, kinfo=None,
     return outs, lse
 
 
+SERVE_SHARED_FORM = int(__import__("os").environ.get("LAP_SERVE_SHARED_FORM", "0"))     # A/B switch: 0 = resident image, 1 = one unit per block
+
+
+def attention_serve_shared(q, k, v, prefix_k, prefix_v, N, S, Pn, NH, NKV, HD, qinfo=None, kinfo=None, scale=1.0, o_out=None, form=None):
+    """The denoise-step attention of N candidate chunks of ONE observation (csrc/attention_serve_shared.hpp): q bf16 [N*S, NH*HD] and
+    the fresh k / v bf16 [N*S, NKV*HD] are per candidate, prefix_k / prefix_v bf16 [Pn, NKV*HD] exist ONCE; qinfo [N, S] / kinfo
+    [N, Pn + S] are the info words of a batch of N (the caller replicates the batch-1 words).  Returns o bf16 [N*S, NH*HD], bit-equal
+    to `attention_fwd` on the prefix replicated N times.  ValueError on shapes the kernel does not take (HD != 256, S > 64, N > 8, ...)."""
+    if HD != 256 or not 1 <= S <= 64 or not 1 <= N <= 8 or Pn < 1 or NH < 1 or NKV < 1 or NH % NKV or not scale > 0:
+        raise ValueError(f"attention_serve_shared: HD = {HD} (256), S = {S} (1..64), N = {N} (1..8), Pn = {Pn} (>= 1), NH = {NH}, NKV = {NKV}, scale = {scale}")
+    for nm, t, shape in (("q", q, (N * S, NH * HD)), ("k", k, (N * S, NKV * HD)), ("v", v, (N * S, NKV * HD)),
+                         ("prefix_k", prefix_k, (Pn, NKV * HD)), ("prefix_v", prefix_v, (Pn, NKV * HD))):
+        if t is None or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"attention_serve_shared: {nm} must be contiguous {shape}, got {None if t is None else tuple(t.shape)}")
+        _req(t, torch.bfloat16, nm)
+    if (qinfo is None) != (kinfo is None):
+        raise ValueError("attention_serve_shared: qinfo and kinfo go together")
+    for nm, inf, n in (("qinfo", qinfo, N * S), ("kinfo", kinfo, N * (Pn + S))):
+        if inf is not None and (inf.dtype != torch.int32 or not inf.is_contiguous() or inf.numel() != n or not inf.is_cuda):
+            raise ValueError(f"attention_serve_shared: {nm} must be a contiguous cuda int32 tensor of {n} words")
+    o = torch.empty((N * S, NH * HD), dtype=torch.bfloat16, device=q.device) if o_out is None else o_out
+    if tuple(o.shape) != (N * S, NH * HD) or o.dtype != torch.bfloat16 or not o.is_contiguous():
+        raise ValueError("attention_serve_shared: o_out must be a packed bf16 [N*S, NH*HD] tensor")
+    ns = _fn["lap_attention_serve_splits"](Pn, S, N, NH, S)
+    if not 0 < ns <= 16:
+        raise ValueError(f"attention_serve_shared: {Pn} + {S} keys do not fit the serving attention's key runs")
+    a = AttnFwdArgs()
+    a.q[1], a.o[1] = _p(q), _p(o)
+    a.k[0], a.v[0], a.k[1], a.v[1] = _p(prefix_k), _p(prefix_v), _p(k), _p(v)
+    a.q_len[1], a.k_len[0], a.k_len[1] = S, Pn, S
+    a.qinfo, a.kinfo = _p(qinfo), _p(kinfo)
+    a.scale, a.nsplit = float(scale), ns
+    scratch = torch.empty(ns * N * S * NH * (HD + 1), dtype=torch.float32, device=q.device)
+    a.scratch, a.scratch_floats = _p(scratch), scratch.numel()
+    a.B, a.NH, a.NKV, a.HD = N, NH, NKV, HD
+    _chk(_fn["lap_attention_serve_shared"](C.byref(a), SERVE_SHARED_FORM if form is None else int(form), _stream()), "lap_attention_serve_shared")
+    return o
+
+
 def attention_bwd(q, k, v, o, d_o, lse, q_len, k_len, B, NH, NKV, HD, qinfo=None, kinfo=None, stop_q1_to_k0=False,
                   scale=1.0, q_rs=(0, 0), kv_rs=(0, 0), dq_out=None, dk_out=None, dv_out=None):
     """Gradients are written with the same row strides as q / k / v (pass dq_out/dk_out/dv_out views of a fused
@@ -1026,6 +1067,41 @@ def axpy_f32(x, v, dt):
 
 
 # ------------------------------------------------ split-K partials + fused consumers (batch-1 denoise step)
+SELECT_MODES = {"medoid": 0, "coherence": 1}
+
+
+def action_select(cand, mode, known=None, weights=None, scores=None, index=None, best=None):
+    """lap_action_select (lap_amd/action_select.py is the specification): cand f32 [N, S, ad] -> (scores f32 [N], index int32 [1],
+    best f32 [S, ad] = a bit copy of cand[index]); mode "medoid", or "coherence" with known f32 [S, ad] and weights f32 [S].
+    One launch, nothing read back: the outputs may be the caller's persistent buffers (graph capture)."""
+    if mode not in SELECT_MODES:
+        raise ValueError(f"action_select: mode must be 'medoid' or 'coherence', got {mode!r}")
+    if cand.dim() != 3 or not cand.is_contiguous():
+        raise ValueError(f"action_select: cand must be contiguous [N, S, action_dim], got {tuple(cand.shape)}")
+    _req(cand, torch.float32, "cand")
+    N, S, ad = cand.shape
+    if not 1 <= N <= 64 or S < 1 or ad < 1 or S * ad > 4096:
+        raise ValueError(f"action_select: N = {N} (1..64), S * action_dim = {S * ad} (1..4096)")
+    if mode == "coherence":
+        if known is None or weights is None:
+            raise ValueError("action_select: mode 'coherence' needs known and weights")
+        if tuple(known.shape) != (S, ad) or tuple(weights.shape) != (S,) or not known.is_contiguous() or not weights.is_contiguous():
+            raise ValueError(f"action_select: known / weights have shapes {tuple(known.shape)} / {tuple(weights.shape)}, expected {(S, ad)} / {(S,)}")
+        _req(known, torch.float32, "known"); _req(weights, torch.float32, "weights")
+    else:
+        known = weights = None
+    dev = cand.device
+    scores = torch.empty(N, dtype=torch.float32, device=dev) if scores is None else scores
+    index = torch.empty(1, dtype=torch.int32, device=dev) if index is None else index
+    best = torch.empty((S, ad), dtype=torch.float32, device=dev) if best is None else best
+    for nm, t, shape, dt in (("scores", scores, (N,), torch.float32), ("index", index, (1,), torch.int32), ("best", best, (S, ad), torch.float32)):
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"action_select: {nm} must be contiguous {shape}, got {tuple(t.shape)}")
+        _req(t, dt, nm)
+    call("lap_action_select", _p(cand), _p(known), _p(weights), _p(scores), _p(index), _p(best), N, S, ad, SELECT_MODES[mode])
+    return scores, index, best
+
+
 def linear_partials(x, wt, scratch, ksplit=None, tile=6):
     """Raw f32 partial products of y = x @ wt^T, [ksplit, M, N] in `scratch` (a 1-D f32 tensor); returns (view, ksplit)."""
     M, K = x.shape

@@ -645,7 +645,8 @@ class LAP:
 
     # ================================================================== serving
     @torch.no_grad()
-    def sample_actions(self, rng, observation, *, num_steps: int = 10, noise=None, collect=None, fused=True, inpaint=None):
+    def sample_actions(self, rng, observation, *, num_steps: int = 10, noise=None, collect=None, fused=True, inpaint=None,
+                       num_samples=None, select=None, coherence=None, share_prefix=True, **internal):
         """lap.py:605-675: prefix prefill once -> per-layer K/V kept in HBM -> `num_steps` Euler steps of the action
         expert attending to [cached prefix | fresh suffix] as two key segments (the reference concatenates, gemma.py:228-230).
         `fused`: True = the fastest denoise-step kernels the shapes allow ("skinny" fused projections for the LAP-3B action
@@ -658,9 +659,19 @@ class LAP:
         step has t' = 0 and a frozen row of the result is `known` bit for bit.  Frozen rows stay in the sequence as action tokens: no
         attention kernel changes.  `collect` still records the model's v_t for every row.  Wrong shapes, a batch mismatch, non-finite
         `known` or mask values other than 0 / 1 raise ValueError.  `lap_amd.chunking.shift_chunk` builds the pair from the previous
-        chunk; that is meaningful only when the action representation does not depend on the new observation's frame."""
+        chunk; that is meaningful only when the action representation does not depend on the new observation's frame.
+        `num_samples=N` (1 .. 8; NOT in the reference either): N candidate chunks of ONE observation (batch 1, pi05) from ONE prefill —
+        `noise` is [N, S, action_dim], drawn from `rng` when absent, `inpaint=(known [1, S, ad], mask [1, S])` applies to every
+        candidate; the steps run on N * S rows and, on the skinny route, the attention reads the single prefix cache
+        (`share_prefix=False`, and the other routes, replicate it: same bits); the one-launch chain is not used.  Returns [N, S, ad].
+        `select="medoid"` or `select="coherence"` with `coherence=(known [S, ad], weights [S])` picks one candidate on the device
+        (`lap_amd/action_select.py` is the specification) and returns it as [1, S, ad]; `collect` then also receives `candidates`,
+        `scores` and `index`.  `num_samples` absent or 1 is the plain call.  ValueError: N outside 1 .. 8, N > 1 with a batch or with
+        pi0, `select` without candidates or without its arguments, wrong shapes."""
         with self._serving_weights():
             kw = {} if inpaint is None else {"inpaint": inpaint}
+            if num_samples is not None or select is not None or coherence is not None:
+                kw |= dict(num_samples=num_samples, select=select, coherence=coherence, share_prefix=share_prefix, **internal)
             return self._sample_actions(rng, observation, num_steps=num_steps, noise=noise, collect=collect, fused=fused, **kw)
 
     def _sample_actions(self, rng, observation, **kw):      # on the weights as they are (outside `_serving_weights`: base + adapters)

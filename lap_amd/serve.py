@@ -47,22 +47,53 @@ def graph_compatible(captured: CoTObservation, obs: CoTObservation) -> bool:
 class GraphedSampler:
     """hipGraph-replayed `LAP.sample_actions`.  `inpaint=True` (not in the reference) captures on the inpainting Euler tails with
     persistent `known` / `mask` buffers: ONE graph then serves every mask, the all-zero one (no row frozen) included, and a call
-    takes `inpaint=(known, mask)` or None.  Without the flag the sampler holds no such buffers and captures the plain launches."""
+    takes `inpaint=(known, mask)` or None.  Without the flag the sampler holds no such buffers and captures the plain launches.
 
-    def __init__(self, model: LAP, batch_size: int = 1, num_steps: int = 10, prompt_len: int | None = None, inpaint: bool = False):
+    `num_samples=N` (2 .. 8, batch_size 1; best-of-N, not in the reference): one capture holds the batch-1 prefill, the denoising of
+    N candidates and, with `select="medoid"` / `"coherence"`, the select launch.  A call takes noise [N, S, ad] and returns the
+    candidates [N, S, ad], or with `select` the chosen chunk [1, S, ad]; `last_candidates`, `last_scores` and `last_index` are
+    views of the captured outputs.  `select="coherence"` keeps persistent `known` [S, ad] / `weights` [S] buffers that
+    `__call__(..., coherence=(known, weights))` checks and copies in before the replay: one graph serves every pair."""
+
+    def __init__(self, model: LAP, batch_size: int = 1, num_steps: int = 10, prompt_len: int | None = None, inpaint: bool = False,
+                 num_samples=None, select=None, share_prefix: bool = True):
+        from lap_amd.action_select import MODES
+        from lap_amd.flow_sample import check_num_samples
+
         self.model, self.B, self.num_steps = model, batch_size, num_steps
         cfg = model.config
+        self.N = check_num_samples(num_samples, batch_size, cfg.pi05)
+        if select is not None and (select not in MODES or self.N < 2):
+            raise ValueError(f"GraphedSampler: select={select!r} needs 'medoid' or 'coherence' and num_samples > 1")
+        self.select, self.share_prefix = select, share_prefix
         self.obs = _placeholder_obs(model, batch_size, prompt_len)
-        self.noise = torch.zeros(batch_size, cfg.action_horizon, cfg.action_dim, device=model.device)
+        self.noise = torch.zeros(max(batch_size, self.N), cfg.action_horizon, cfg.action_dim, device=model.device)
         self.inpaint = None
         if inpaint:
-            self.inpaint = (torch.zeros_like(self.noise), torch.zeros(batch_size, cfg.action_horizon, dtype=torch.uint8, device=model.device))
+            self.inpaint = (torch.zeros(batch_size, cfg.action_horizon, cfg.action_dim, device=model.device),
+                            torch.zeros(batch_size, cfg.action_horizon, dtype=torch.uint8, device=model.device))
+        self.coherence = None
+        if select == "coherence":
+            self.coherence = (torch.zeros(cfg.action_horizon, cfg.action_dim, device=model.device), torch.zeros(cfg.action_horizon, device=model.device))
+        self._sel = {}
+        self.last_candidates = self.last_scores = self.last_index = None
         self.graph = None
         self.out = None
 
-    def _load(self, obs: CoTObservation, noise: torch.Tensor, inpaint=None):     # (unlike GraphedTokenDecoder._load: absent image masks and `state` keep the last request's)
+    def _load(self, obs: CoTObservation, noise: torch.Tensor, inpaint=None, coherence=None):     # (unlike GraphedTokenDecoder._load: absent image masks and `state` keep the last request's)
         if inpaint is not None and self.inpaint is None:
             raise ValueError("this GraphedSampler was built without inpaint=True")
+        if (coherence is None) != (self.coherence is None):
+            raise ValueError("coherence=(known, weights) goes with a GraphedSampler built with select='coherence', and is required there")
+        if tuple(noise.shape) != tuple(self.noise.shape):
+            raise ValueError(f"noise has shape {tuple(noise.shape)}, expected {tuple(self.noise.shape)}")
+        new_coh = None
+        if coherence is not None:       # (checked BEFORE anything is copied, like `inpaint`)
+            from lap_amd.action_select import check_coherence
+
+            new_coh = check_coherence(*coherence, *self.noise.shape[1:])
+            if not all(bool(torch.isfinite(torch.as_tensor(c, dtype=torch.float32)).all()) for c in new_coh):
+                raise ValueError("select: coherence known / weights have non-finite values")
         if self.inpaint is not None:
             from lap_amd.flow_sample import check_inpaint
 
@@ -70,9 +101,12 @@ class GraphedSampler:
             if inpaint is None:
                 mask.zero_()
             else:       # (checked BEFORE anything is copied: the capture itself cannot look at values)
-                k, m = check_inpaint(inpaint, *self.noise.shape, self.model.device)
+                k, m = check_inpaint(inpaint, *known.shape, self.model.device)
                 known.copy_(k)
                 mask.copy_(m)
+        if new_coh is not None:
+            for buf, c in zip(self.coherence, new_coh):
+                buf.copy_(torch.as_tensor(c).to(buf.device, torch.float32))
         for k in self.obs.images:
             self.obs.images[k].copy_(obs.images[k])
             if k in obs.image_masks and obs.image_masks[k] is not None:
@@ -92,19 +126,24 @@ class GraphedSampler:
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.out = self._sample()
+        if self.N > 1:
+            self.last_candidates = self._sel.get("candidates", self.out)
+            self.last_scores, self.last_index = self._sel.get("scores"), self._sel.get("index")
         return self
 
     def _sample(self):
         kw = {} if self.inpaint is None else {"inpaint": self.inpaint}
+        if self.N > 1:
+            kw |= dict(num_samples=self.N, select=self.select, coherence=self.coherence, share_prefix=self.share_prefix, _select_out=self._sel)
         return self.model.sample_actions(0, self.obs, num_steps=self.num_steps, noise=self.noise, **kw)
 
-    def __call__(self, obs: CoTObservation, noise: torch.Tensor, inpaint=None) -> torch.Tensor:
+    def __call__(self, obs: CoTObservation, noise: torch.Tensor, inpaint=None, coherence=None) -> torch.Tensor:
         if self.graph is None:
             self.capture()
         # parameter-derived caches the graph holds addresses of (adaRMS modulations, packed expert weights) follow the
         # parameters in place; a no-op unless a train step / restore / reload happened since the last call
         self.model.refresh_serve_caches(self.num_steps)
-        self._load(obs, noise, inpaint)
+        self._load(obs, noise, inpaint, coherence)
         self.graph.replay()
         return self.out
 
@@ -341,6 +380,19 @@ class Policy:
         # (pi0, `pi05=False`, runs on the generic layer loop with its suffix re-embedded by torch ops at every step: served eagerly)
         self._sampler = GraphedSampler(model, 1, self.num_steps) if (use_graph and model.config.pi05) else None
         self._inpaint_sampler = None        # GraphedSampler(inpaint=True), built at the first request with an "inpaint" key
+        # best-of-N (sample_kwargs "num_samples", "select", "rho"): candidates of one prefill, one chosen on the device
+        from lap_amd.action_select import MODES
+        from lap_amd.flow_sample import check_num_samples
+
+        self._N = check_num_samples(self._sample_kwargs.pop("num_samples", None), 1, model.config.pi05)
+        self._select = self._sample_kwargs.pop("select", None)
+        self._rho = float(self._sample_kwargs.pop("rho", 0.5))
+        if self._N > 1 and self._select not in MODES:
+            raise ValueError(f"Policy: num_samples = {self._N} needs sample_kwargs['select'] = 'medoid' or 'coherence', got {self._select!r}")
+        if self._N == 1 and self._select is not None:
+            raise ValueError("Policy: sample_kwargs['select'] needs num_samples > 1")
+        self._cand_samplers = {}            # (select mode, inpaint) -> GraphedSampler(num_samples=N, ...), built on first use
+        self.last_candidates = None         # [N, S, ad] of the last best-of-N request (device copy)
         self._chunker = RealTimeChunker()   # the last model-space chunk
         self._gen = torch.Generator(device=model.device).manual_seed(seed)
         self._has_transforms = bool(transforms) or bool(output_transforms)
@@ -377,19 +429,62 @@ class Policy:
             known, mask = nxt[0][None], nxt[1][None]
         return (known, mask), {"applied": True, "frozen_rows": int(np.count_nonzero(mask))}
 
+    def _infer_candidates(self, o, executed, inpaint, noise):
+        """One best-of-N request -> (the chosen chunk [1, S, ad], the note for `policy_timing["select"]`)."""
+        from lap_amd.action_select import coherence_weights
+        from lap_amd.chunking import shift_chunk
+
+        cfg, dev = self.model.config, self.model.device
+        S, ad = cfg.action_horizon, cfg.action_dim
+        if noise is None:
+            noise = torch.randn((self._N, S, ad), generator=self._gen, device=dev)
+        else:
+            noise = torch.as_tensor(np.asarray(noise), dtype=torch.float32, device=dev).reshape(self._N, S, ad)
+        mode, coh, fallback = self._select, None, False
+        if mode == "coherence":
+            if self._chunker.prev is None:      # nothing to be coherent with: the candidate closest to the others
+                mode, fallback = "medoid", True
+            else:
+                ex = 0 if executed is None else int(executed)
+                prev = self._chunker.prev if self._chunker.prev.ndim == 2 else self._chunker.prev[0]
+                coh = (torch.from_numpy(shift_chunk(prev, ex, 0)[0]), coherence_weights(S, ex, self._rho))
+        sel = {}
+        if self._sampler is not None and graph_compatible(self._sampler.obs, o):
+            key = (mode, inpaint is not None)
+            if key not in self._cand_samplers:
+                self._cand_samplers[key] = GraphedSampler(self.model, 1, self.num_steps, inpaint=key[1], num_samples=self._N, select=mode)
+            sampler = self._cand_samplers[key]
+            a = sampler(o, noise, inpaint, coh)
+            sel = dict(candidates=sampler.last_candidates, scores=sampler.last_scores, index=sampler.last_index)
+        else:
+            kw = {} if inpaint is None else {"inpaint": inpaint}
+            a = self.model.sample_actions(0, o, num_steps=self.num_steps, noise=noise, num_samples=self._N, select=mode, coherence=coh,
+                                          _select_out=sel, **kw)
+        self.last_candidates = sel["candidates"].clone()
+        return a, {"mode": mode, "index": int(sel["index"].item()), "scores": sel["scores"].cpu().tolist(), "fallback": fallback}
+
     def infer(self, obs: dict, *, noise=None) -> dict:
         t0 = time.perf_counter()
         dev = self.model.device
         request = dict(obs)
+        executed = request.pop("executed", None)        # (best-of-N coherence; an "inpaint" request's own "executed" comes first)
+        if isinstance(request.get("inpaint"), dict) and "executed" in request["inpaint"]:
+            executed = request["inpaint"]["executed"]
         inpaint, note = self._inpaint_request(request.pop("inpaint")) if "inpaint" in request else (None, None)
         inputs = self._input_transform(request)
         o, batched = self._to_observation(inputs)
         cfg = self.model.config
-        if noise is None:
+        select_note = None
+        if self._N > 1:
+            a, select_note = self._infer_candidates(o, executed, inpaint, noise)
+            noise = torch.zeros(0) if noise is None else torch.as_tensor(np.asarray(noise))
+        elif noise is None:
             noise = torch.randn((1, cfg.action_horizon, cfg.action_dim), generator=self._gen, device=dev)
         else:
             noise = torch.as_tensor(np.asarray(noise), dtype=torch.float32, device=dev).reshape(1, cfg.action_horizon, cfg.action_dim)
-        if inpaint is None:
+        if self._N > 1:
+            pass
+        elif inpaint is None:
             if self._sampler is not None and graph_compatible(self._sampler.obs, o):
                 a = self._sampler(o, noise)
             else:
@@ -405,13 +500,13 @@ class Policy:
             # A block of the one-launch denoise step (csrc/serve_chain.hpp) was not scheduled within its bounded wait — the GPU is
             # shared with work that holds compute units — so this chunk is invalid: go back to the separate launches for good.
             self.model.disable_serve_chain()
-            for sampler in (self._sampler, self._inpaint_sampler):
+            for sampler in (self._sampler, self._inpaint_sampler, *self._cand_samplers.values()):
                 if sampler is not None:
                     sampler.graph = None
-            return self.infer(obs, noise=noise.cpu().numpy())
-        self._chunker.update(actions)       # model space: before Unnormalize and the output transforms
+            return self.infer(obs, noise=noise.cpu().numpy() if noise.numel() else None)
+        self._chunker.update(actions)       # model space: before Unnormalize and the output transforms (best-of-N: the chosen chunk)
         model_ms = (time.perf_counter() - t0) * 1e3
-        timing = {"infer_ms": model_ms} | ({} if note is None else {"inpaint": note})
+        timing = {"infer_ms": model_ms} | ({} if note is None else {"inpaint": note}) | ({} if select_note is None else {"select": select_note})
         if not self._has_transforms:
             return {"actions": actions, "policy_timing": timing}
         outputs = self._output_transform({"state": batched["state"][0], "actions": actions})

@@ -5,7 +5,8 @@ Protocol: after the websocket handshake the server sends one binary frame with t
 then, per request, the client sends a packed observation dict and receives the packed result of `policy.infer(obs)` plus
 `server_timing` ({"infer_ms", "prev_total_ms"}).  An exception inside `infer` is reported as a text frame with the traceback
 followed by a close frame with code 1011.  `GET /healthz` answers a plain `200 OK`.  The request dict reaches `infer` untouched:
-an `"inpaint"` key in it (real-time chunking, `serve.Policy`) is the policy's to read, and requests without it are served as ever.
+an `"inpaint"` key in it (real-time chunking, `serve.Policy`) is the policy's to read, and requests without it are served as ever;
+so is a top-level `"executed"` key (best-of-N serving, `--num-samples N --select coherence`), and `policy_timing["select"]` comes back.
 
 The `websockets` package is not part of this image, so the RFC 6455 subset the protocol needs (handshake, masked client
 frames, fragmentation, ping / pong / close, unmasked server frames) is implemented on asyncio streams directly.  Requests are
@@ -212,6 +213,11 @@ def main(argv=None):
     ap.add_argument("--ar-sampler", choices=["host", "device"], default="host",
                     help="--type ar: 'device' draws with the counter-based noise of lap_amd/sampling.py; with --ar-graph the "
                          "captured decoder then serves sampled requests too ('host': the torch-generator stream, eager decode)")
+    ap.add_argument("--num-samples", type=int, default=None,
+                    help="--type flow: best-of-N action chunks per request from one prefill (needs --select)")
+    ap.add_argument("--select", choices=["medoid", "coherence"], default=None,
+                    help="--type flow: how the served chunk is chosen among the candidates ('coherence': against the chunk being executed)")
+    ap.add_argument("--rho", type=float, default=0.5, help="--select coherence: the decay of the per-row weights")
     a = ap.parse_args(argv)
     cfg = get_config(a.config)
     cfg = dataclasses.replace(cfg, model=dataclasses.replace(cfg.model, stop_action_to_vlm_grad=False))   # serve_policy.py:77-79
@@ -221,6 +227,10 @@ def main(argv=None):
         ap.error("--ar-temperature / --ar-sampler need --type ar")
     extra = {"ar_graph": True} if a.ar_graph else {}
     extra.update(_ar_sample_kwargs(a.ar_temperature, a.ar_sampler))
+    if a.num_samples is not None or a.select is not None:
+        if a.type != "flow":
+            ap.error("--num-samples / --select need --type flow")
+        extra["sample_kwargs"] = {"num_samples": a.num_samples, "select": a.select, "rho": a.rho}
     make = create_trained_policy_ar if a.type == "ar" else create_trained_policy
     policy = make(cfg, a.checkpoint_dir, tokenizer_model_path=a.tokenizer_model, default_prompt=a.default_prompt, **extra)
     logging.basicConfig(level=logging.INFO)
