@@ -1,6 +1,7 @@
-"""LAP_AR token decoding (lap.py:678-766) behind `LAP.sample_tokens`: the VLM-only prefill, the eager decode step on generic
-launches, the fused step on the single-token kernels of csrc/decode.hip with its device-side state (`DecodeCtx`), and the routing
-between them.  `serve.GraphedTokenDecoder` captures `prefill` + `DecodeCtx.first_token` and `DecodeCtx.step` into two graphs.
+"""LAP_AR token decoding (lap.py:678-766) behind `LAP.sample_tokens` and `LAP.score_tokens`: the request checks, the VLM-only
+prefill, the eager decode step on generic launches, the eager and the fused drivers, and the routing between them.  The fused step
+and its device-side state are `decode_ctx.DecodeCtx` (the single-token kernels of csrc/decode*.hip), which the fused drivers here
+and `serve.GraphedTokenDecoder` (`prefill` + `DecodeCtx.first_token` and `DecodeCtx.step` captured into two graphs) sequence.
 The weights are read through the model (`W`, `F`, `_dec_fp8`), as `LAP._serving_weights` presents them.
 """
 from __future__ import annotations
@@ -11,11 +12,13 @@ from typing import NamedTuple
 import torch
 
 from lap_amd import hip, prefill as serving_prefill
+from lap_amd.decode_ctx import DecodeCtx, check_decode_weights
+from lap_amd.grammar import check_grammar
 from lap_amd.joint_layers import llm_fwd
 from lap_amd.loss import lm_logits
 from lap_amd.model import LAP, _gen
 from lap_amd.observation import preprocess_observation
-from lap_amd.score import check_score_args, check_score_ctx
+from lap_amd.score import check_score_args
 from lap_amd.speculate import check_jump_forward, check_speculate
 
 DECODE_STEPS_PER_CHECK = 8      # fused steps between two host reads of the device stop flag (eager `decode="fused"`)
@@ -28,11 +31,6 @@ def check_fused_decode(model: LAP, B: int):
         v = model.v
         raise ValueError(f"fused decode serves the Gemma-2B widths at 1 <= B <= 8 (D 2048, 8 / 1 heads of 256, MLP 16384); got "
                          f"B {B}, D {v.width}, heads {v.num_heads} / {v.num_kv_heads} of {v.head_dim}, MLP {v.mlp_dim}")
-
-
-def check_decode_weights(weights):
-    if weights not in LAP.DECODE_WEIGHTS:
-        raise ValueError(f"decode_weights must be one of {LAP.DECODE_WEIGHTS}, got {weights!r}")
 
 
 def check_allowed_tokens(ids, vocab_size: int, eos_token: int) -> torch.Tensor:
@@ -109,34 +107,6 @@ def check_filter(top_k, top_p, *, sampler: str, temperature: float):
     if (k == 0 and p >= 1.0) or not temperature > 0.0:
         return None
     return k, p
-
-
-def check_grammar(grammar, vocab_size: int, eos_token: int, *, allowed_tokens=None, top_k=None, top_p=None, speculate=None,
-                  sampler: str = "device", temperature: float = 0.0):
-    """The host automaton of a grammar-constrained request (`grammar`: a grammar.TokenAutomaton or its `to_device` form), checked
-    (`grammar.check_automaton`) and compared with the model's vocabulary and EOS token; ValueError naming what it does not
-    combine with: allowed_tokens (the automaton's union replaces the set), top_k / top_p, speculate, and the host sampler at
-    temperature > 0 (the constrained draw is part of the device sampler)."""
-    from lap_amd.grammar import DeviceAutomaton, TokenAutomaton, check_automaton
-
-    host = grammar.host if isinstance(grammar, DeviceAutomaton) else grammar
-    if not isinstance(host, TokenAutomaton):
-        raise ValueError(f"grammar: expected a grammar.TokenAutomaton (or its to_device form), got {type(grammar).__name__}")
-    if allowed_tokens is not None:
-        raise ValueError("grammar does not combine with allowed_tokens: the union of the automaton's edges replaces the set")
-    if top_k is not None or top_p is not None:
-        raise ValueError("grammar does not combine with top_k / top_p")
-    if speculate is not None:
-        raise ValueError("grammar does not combine with speculate")
-    if sampler != "device" and temperature > 0.0:
-        raise ValueError(f"grammar at temperature > 0 needs sampler=\"device\" (the constrained draw is part of the device sampler), "
-                         f"got sampler={sampler!r}")
-    if (host.vocab_size, host.eos_token) != (vocab_size, eos_token):
-        raise ValueError(f"grammar: the automaton was built for vocab_size {host.vocab_size} and EOS token {host.eos_token}, the model "
-                         f"has vocab_size {vocab_size} and EOS token {eos_token}")
-    if not isinstance(grammar, DeviceAutomaton):        # (`to_device` has checked the other form)
-        check_automaton(host)
-    return host
 
 
 def _on_device(t: torch.Tensor, device) -> bool:
@@ -368,6 +338,15 @@ def _grammar_step(g, q, token):
     return torch.where(ok, g.next[pos].long(), q)       # (a token outside the segment: only from a row of -inf; the state stays)
 
 
+def _outside_mask(model: LAP, allowed):
+    """bool [V]: the ids outside the allowed set (int32 device ids), which the eager routes fill with -inf; None without a set."""
+    if allowed is None:
+        return None
+    outside = torch.ones((model.config.vocab_size,), dtype=torch.bool, device=model.device)
+    outside[allowed.long()] = False
+    return outside
+
+
 def _sample_eager(model: LAP, rng, observation, *, max_decoding_steps: int, temperature: float, collect, device_sampler: bool,
                   allowed=None, logprobs: bool = False, filt=None, grammar=None):
     """grammar: a DeviceAutomaton; the mask of every row's state is built with torch ops, the draw is the unconstrained one on the
@@ -384,10 +363,7 @@ def _sample_eager(model: LAP, rng, observation, *, max_decoding_steps: int, temp
     inv_t = float(hip.sampling_words(0, temperature)[2]) if logprobs else 0.0      # float32(1 / temperature); 0: greedy, scored at tau = 1
     gen = [(None, None)] * model.v.depth
     g = _gen(rng, dev) if temperature > 0.0 and not device_sampler else None
-    outside = None
-    if allowed is not None:
-        outside = torch.ones((model.config.vocab_size,), dtype=torch.bool, device=dev)
-        outside[allowed.long()] = False
+    outside = _outside_mask(model, allowed)
     gq = torch.zeros((B,), dtype=torch.int64, device=dev) if grammar is not None else None
     step = 0
     while step < max_decoding_steps:
@@ -437,10 +413,7 @@ def beam_decode_eager(model: LAP, observation, N: int, *, max_decoding_steps: in
 
     dev = model.device
     B, Pn, cache, kinfo_prefix, qinfo_d, plen, x_last = replicate_prefill(prefill(model, observation), N)
-    outside = None
-    if allowed is not None:
-        outside = torch.ones((model.config.vocab_size,), dtype=torch.bool, device=dev)
-        outside[allowed.long()] = False
+    outside = _outside_mask(model, allowed)
     gen = [(None, None)] * model.v.depth
     state = {"gen": gen}
 
@@ -482,16 +455,21 @@ def beam_decode_fused(model: LAP, observation, N: int, *, max_decoding_steps: in
     ctx = DecodeCtx(model, N, pre.Pn, max_decoding_steps, weights=weights, allowed=allowed, beams=N, early_stop=early_stop,
                     grammar=grammar)
     ctx.first_token(pre)
+    _steps_until_done(ctx, max_decoding_steps)
+    return ctx.beam_result()
+
+
+# ---- the fused drivers: `decode_ctx.DecodeCtx` steps, state on the device
+def _steps_until_done(ctx: DecodeCtx, max_decoding_steps: int):
+    """The steps after `first_token`: DECODE_STEPS_PER_CHECK at a time, then one host read of the device stop flag `state[1]`."""
     n = DECODE_STEPS_PER_CHECK
     for _ in range((max_decoding_steps - 1 + n - 1) // n):
         if bool(ctx.state[1].item()):
             break
         for _ in range(n):
             ctx.step()
-    return ctx.beam_result()
 
 
-# ---- the fused step: single-token kernels, state on the device (csrc/decode.hip)
 def _sample_fused(model: LAP, observation, *, max_decoding_steps: int, collect=None, sampling=None, weights: str = "bf16",
                   allowed=None, logprobs: bool = False, num_samples=None, filt=None, speculate=None, draft=None, grammar=None, jump=None):
     """grammar: None, or a DeviceAutomaton: a grammar context.  jump: None, or the rows S of a jump-forward step of that context
@@ -525,12 +503,7 @@ def _sample_fused(model: LAP, observation, *, max_decoding_steps: int, collect=N
             ctx.step(lg)
             collect[f"logit/{int(ctx.state[0].item()) - 1}"] = lg.clone()
         return (ctx.out, ctx.logp) if logprobs else ctx.out
-    n = DECODE_STEPS_PER_CHECK
-    for _ in range((max_decoding_steps - 1 + n - 1) // n):
-        if bool(ctx.state[1].item()):
-            break
-        for _ in range(n):
-            ctx.step()
+    _steps_until_done(ctx, max_decoding_steps)
     if speculate is not None or jump is not None:
         model.last_spec_stats = ctx.stats()
     return (ctx.out, ctx.logp) if logprobs else ctx.out
@@ -567,339 +540,3 @@ def score_tokens(model: LAP, observation, tokens, *, rows: int = 8, temperature:
             logp.append(lp)
             greedy.append(gr)
     return ScoreResult(logp, torch.stack([lp.sum() for lp in logp]), greedy)
-
-
-class DecodeCtx:
-    """One fused decode of `model` (B rows, `Pn` prefix keys, `cap` = max_decoding_steps): the device state, the token output,
-    the fixed-capacity generated K/V cache of every layer ([depth, 2, B, cap, head_dim] bf16, 7.2 MB per sample at 390 steps
-    for LAP-3B) and the step's activations.  The prefix K/V cache and kinfo come from the prefill (`first_token` -> `bind`).
-    filtering=True (needs sampling=True): the context draws through top-k / top-p filter words (`set_filter`): its LM head is the
-    plain greedy one, which stores its f32 logits in a [B, V] buffer the context owns, and lap_decode_filter_finish draws from that
-    buffer and does the finish's bookkeeping.  Every other context launches what it launched before.
-    speculate=S (2 <= S <= 8; B = 1, greedy, no log-probabilities): the context decodes ONE sequence on verify steps of S rows
-    (lap_amd/speculate.py, csrc/decode_spec.hip).  The state, `out`, `plen` and the generated cache stay those of B = 1; the
-    activations, the attention scratch and the LM partials hold S rows; a reference sequence and its length live in one device
-    buffer at a fixed address (`set_draft`).  `first_token` runs the B = 1 head and finish; `step` drafts S - 1 tokens from the
-    reference, runs the layers on the S positions t-1 .. t-1+S-1 and accepts the longest verified run; `stats` reads the
-    counters.  The tokens are those of the context without it.
-    grammar=DeviceAutomaton (not with allowed, filtering or speculate): the context draws every row's token among the edges of
-    the automaton state that row is in (lap_amd/grammar.py).  It owns `gstate` (int32 [B], zeroed by `first_token` with a device
-    op that a captured prefill replays) and a [B, V] f32 logits buffer, written to -inf once; its LM head is the plain SUBSET head
-    (bf16 or fp8) over the automaton's union, which stores its logits there, and lap_decode_grammar_finish draws from them, moves
-    `gstate` and does the finish's bookkeeping, with the log-probability over the state's set when logprobs is on.
-    jump_forward=S (2 <= S <= 8; needs grammar, B = 1; with or without sampling and logprobs): the grammar context decodes ONE
-    sequence on steps of S rows, in the arrangement of speculate=S (state, `out`, `logp`, `gstate` and the generated cache of
-    B = 1; activations, attention scratch, LM partials and the logits buffer of S rows).  `step` drafts from the reference
-    (`set_draft`), overwrites the drafts with the grammar's (lap_decode_grammar_draft: a state with one edge forces its token), runs
-    the layers on the S positions, the plain SUBSET head over the union on the S rows, and lap_decode_grammar_spec_finish, which
-    draws the rows in sequence with the single-row finish's bits and accepts the longest verified run.  Tokens and
-    log-probabilities are those of the grammar context without it; `stats` reads the counters.
-    beams=N (B = N; greedy, not with filtering, speculate or jump_forward; composes with weights, and with allowed or grammar): the rows are
-    the beams of one beam search (lap_amd/beam.py, csrc/decode_beam.hip).  The context owns the beam buffer (scores, finished,
-    parent, the `early_stop` flag; reset by `first_token` with a device copy that a captured prefill replays), the [N, V] f32 logits
-    of the step, the [N, N] candidates and `logp`.  Its LM head is the plain greedy one (plain / SUBSET / fp8), which stores its
-    logits; lap_decode_beam_topn and lap_decode_beam_select finish the step, and `step` starts with lap_decode_beam_reorder, which
-    moves the generated K / V rows to the parents the last select chose.  `beam_result` hands out all beams.
-    beams=N with grammar=DeviceAutomaton: the beams are the most probable sentences of the automaton (`beam.grammar_beam_step`).  The
-    context also owns `gstate` [N] (every beam's automaton state) and `cand_next`; the head is the SUBSET head over the automaton's
-    union, lap_decode_beam_grammar_topn reads only the edges of every row's state and lap_decode_beam_grammar_select carries the
-    states along the parent permutation.
-    score=S (1 <= S <= 8; B = 1; composes with weights and allowed, not with sampling, filtering, speculate, grammar, jump_forward
-    or beams): the context scores a GIVEN sequence instead of decoding one (lap_amd/score.py, csrc/decode_score.hip).  The
-    arrangement is that of speculate=S; the candidate lives in the reference buffer (`set_candidate`), `logp` [1, cap] receives the
-    log-probability of every given token and `greedy` [1, cap] the argmax id at its position; `out` stays zero.  `first_token`
-    scores token 0 from the prefill's last row, every `step` the next min(S, length - t) tokens on one pass over the weights; the
-    context is done when all are scored.  `set_score_temperature` sets the temperature of z; `stats` reads the counters."""
-
-    def __init__(self, model: LAP, B: int, Pn: int, cap: int, sampling: bool = False, weights: str = "bf16", allowed=None,
-                 logprobs: bool = False, filtering: bool = False, speculate=None, grammar=None, jump_forward=None, beams=None,
-                 early_stop: bool = True, score=None):
-        check_decode_weights(weights)
-        self.score = None
-        if score is not None:
-            self.score = check_score_ctx(score, B, sampling=sampling, filtering=filtering, speculate=speculate, grammar=grammar,
-                                         jump_forward=jump_forward, beams=beams)
-            logprobs = True
-        self.beams = None
-        if beams is not None:
-            from lap_amd.beam import check_num_beams
-
-            self.beams = check_num_beams(beams, 1, temperature=1.0 if sampling else 0.0, top_k=0 if filtering else None,
-                                         speculate=speculate, grammar=grammar, jump_forward=jump_forward)
-            if B != self.beams:
-                raise ValueError(f"DecodeCtx: beams={self.beams} are the rows of the batch, got B {B}")
-            logprobs = True
-        self.J = None
-        if jump_forward is not None:
-            self.J = check_jump_forward(jump_forward, B, grammar=grammar)
-        if grammar is not None:
-            check_grammar(grammar, model.config.vocab_size, model.EOS_TOKEN, allowed_tokens=allowed, top_k=0 if filtering else None,
-                          speculate=speculate)
-            if not grammar.ids.is_cuda:
-                raise ValueError("DecodeCtx: grammar must be the automaton on the device (TokenAutomaton.to_device)")
-        self.grammar = grammar          # None, or the device automaton (captured graphs keep its buffers' addresses)
-        self.S = None
-        if speculate is not None:
-            self.S = check_speculate(speculate, B, return_logprobs=logprobs, temperature=1.0 if sampling else 0.0)
-        R = self.S or self.J or self.score or B     # rows of a step's activations
-        if filtering and not sampling:
-            raise ValueError("DecodeCtx: filtering needs sampling=True (the filters are part of the device sampler)")
-        if allowed is not None and (allowed.dtype != torch.int32 or not allowed.is_cuda or allowed.dim() != 1):
-            raise ValueError("DecodeCtx: allowed must be the int32 device ids of check_allowed_tokens")
-        self.allowed = allowed          # None, or the allowed set of every token (captured graphs keep the buffer's address)
-        v = model.v
-        self.model = model
-        self.weights = weights          # what the steps stream: "bf16", "fp8" (projections + LM head) or "fp8_layers"
-        dev = model.device
-        bf = torch.bfloat16
-        self.B, self.Pn, self.cap = B, Pn, cap
-        self.state = hip.decode_state(B, dev)
-        self.plen = torch.zeros((B,), dtype=torch.int32, device=dev)
-        self.out = torch.zeros((B, cap), dtype=torch.int32, device=dev)
-        self.gen = torch.zeros((v.depth, 2, B, cap, v.head_dim), dtype=bf, device=dev)
-        self.x = torch.zeros((R, v.width), dtype=bf, device=dev)
-        self.xa = torch.zeros((R, v.width), dtype=bf, device=dev)
-        self.q = torch.zeros((R, v.num_heads * v.head_dim), dtype=bf, device=dev)
-        self.o = torch.zeros((R, v.num_heads * v.head_dim), dtype=bf, device=dev)
-        self.act = torch.zeros((R, v.mlp_dim), dtype=bf, device=dev)
-        self.attn_scratch = hip.decode_attn_scratch(R, Pn, cap, dev)
-        self.pval, self.pidx = hip.decode_lm_partials(R, dev)
-        # speculate: the reference sequence {length, ids[cap]} and the S - 1 drafted tokens of the step
-        # score: the same buffer holds the candidate, and nothing is drafted
-        self.ref = hip.decode_spec_ref(cap, dev) if R != B or self.score else None
-        self.draft = torch.full((R - 1,), -1, dtype=torch.int32, device=dev) if R != B and not self.score else None
-        # the sampling words {seed low, seed high, bits of 1 / temperature, 0} of the sampling LM head (zeros: greedy); None:
-        # the context decodes on the greedy LM head
-        self.sampling = hip.decode_sampling(dev) if sampling else None
-        # logprobs: the log-probability of every token of `out` beside it (f32 [B, cap], zeros where nothing was written) and the
-        # LM head's log-sum-exp partials; None: the context launches the heads without them
-        self.logp = torch.zeros((B, cap), dtype=torch.float32, device=dev) if logprobs else None
-        self.plp = hip.decode_lm_logp_partials(R, dev) if logprobs and grammar is None and self.beams is None else None
-        # score: the argmax id at every scored position beside `logp`, and the words that carry the temperature to the TARGET head
-        # (zeros: z = logit; `set_score_temperature`)
-        self.greedy = torch.zeros((B, cap), dtype=torch.int32, device=dev) if self.score else None
-        self.score_words = hip.decode_sampling(dev) if self.score else None
-        # filtering: the filter words {top_k, bits of top_p, 0, 0} (neutral until `set_filter`) and the f32 logits of the step, which
-        # keep -inf outside an allowed set (the constrained head writes the allowed columns only)
-        self.filter = hip.decode_filter(dev) if filtering else None
-        self.logits = None
-        if filtering:
-            self.logits = torch.empty((B, model.config.vocab_size), dtype=torch.float32, device=dev)
-            if allowed is not None:
-                self.logits.fill_(float("-inf"))
-        # grammar: the automaton state of every row, and the f32 logits of the step (-inf outside the union, written once: the
-        # SUBSET head writes the union's columns only)
-        self.gstate = None
-        if grammar is not None:
-            self.gstate = torch.zeros((B,), dtype=torch.int32, device=dev)
-            self.logits = torch.full((R, model.config.vocab_size), float("-inf"), dtype=torch.float32, device=dev)
-        # beams: the beam buffer and what a fresh decode copies over it, the f32 logits of the step (-inf outside an allowed set,
-        # written once) and the N best (log-probability, id) of every row
-        self.beam = None
-        if self.beams is not None:
-            self.beam_init = hip.decode_beam_init_words(B, early_stop, dev)
-            self.beam = self.beam_init.clone()
-            if grammar is None:         # (a grammar context has its logits already: -inf outside the union)
-                self.logits = torch.empty((B, model.config.vocab_size), dtype=torch.float32, device=dev)
-                if allowed is not None:
-                    self.logits.fill_(float("-inf"))
-            self.cand_logp = torch.zeros((B, B), dtype=torch.float32, device=dev)
-            self.cand_id = torch.full((B, B), -1, dtype=torch.int32, device=dev)
-            self.cand_next = torch.full((B, B), -1, dtype=torch.int32, device=dev) if grammar is not None else None
-        self.prefix = None
-        self.kinfo = None
-
-    def beam_result(self):
-        """All beams of the decode so far, in rank order: (tokens int32 [N, cap], logp f32 [N, cap], scores f32 [N]), fresh
-        tensors; `scores` is the device's running f32 sum of a beam's token log-probabilities (-inf: a padding beam)."""
-        if self.beam is None:
-            raise ValueError("this decode context was built without beams")
-        return self.out.clone(), self.logp.clone(), self.beam[:self.B].clone().view(torch.float32)
-
-    def beam_reorders(self) -> int:
-        """The steps of the decode so far whose parent permutation was not the identity (a host read)."""
-        if self.beam is None:
-            raise ValueError("this decode context was built without beams")
-        return int(self.beam[25].item())
-
-    def set_filter(self, top_k, top_p):
-        """top_k / top_p of the next decode (None: neutral; a host-to-device copy; captured graphs keep the buffer's address)."""
-        if self.filter is None:
-            raise ValueError("this decode context was built without filtering")
-        hip.decode_set_filter(self.filter, top_k, top_p)
-
-    def set_candidate(self, ids):
-        """The sequence the next `first_token` + `step`s score (any integer sequence of 1 .. cap ids): a host-to-device copy."""
-        if self.score is None:
-            raise ValueError("this decode context was built without score")
-        n = len(ids)
-        if not 1 <= n <= self.cap:
-            raise ValueError(f"set_candidate: a sequence of 1 <= length <= {self.cap} ids, got length {n}")
-        hip.decode_set_spec_ref(self.ref, ids)
-
-    def set_score_temperature(self, temperature: float):
-        """The temperature the next candidates are scored at (0: z = logit): a host-to-device copy."""
-        if self.score is None:
-            raise ValueError("this decode context was built without score")
-        hip.decode_set_sampling(self.score_words, 0, temperature)
-
-    def score_result(self):
-        """(logp f32 [n], greedy int32 [n]) of the n tokens scored so far (a host read of t): fresh tensors."""
-        if self.score is None:
-            raise ValueError("this decode context was built without score")
-        n = int(self.state[0].item())
-        return self.logp[0, :n].clone(), self.greedy[0, :n].clone()
-
-    def set_draft(self, ids):
-        """The reference sequence the next decode drafts from (any integer sequence, truncated to `cap`; None: no draft, every
-        verify step then emits one token): a host-to-device copy; captured graphs keep the buffer's address."""
-        if self.ref is None:
-            raise ValueError("this decode context was built without speculate or jump_forward")
-        hip.decode_set_spec_ref(self.ref, ids)
-
-    def stats(self):
-        """(verify_steps, accepted) of the decode so far: two words of the device state (a host read)."""
-        if self.ref is None:
-            raise ValueError("this decode context was built without speculate or jump_forward")
-        a, b = self.state[24:26].tolist()
-        return int(a), int(b)
-
-    def set_sampling(self, seed: int, temperature: float):
-        """Seed and temperature of the next decode (a host-to-device copy; captured graphs keep the buffer's address)."""
-        if self.sampling is None:
-            raise ValueError("this decode context was built without sampling")
-        hip.decode_set_sampling(self.sampling, seed, temperature)
-
-    def bind(self, cache, kinfo_prefix):
-        if kinfo_prefix.shape != (self.B, self.Pn):
-            raise ValueError(f"decode context for B {self.B}, {self.Pn} prefix keys; got kinfo {tuple(kinfo_prefix.shape)}")
-        self.prefix = list(cache)
-        self.kinfo = kinfo_prefix
-
-    def first_token(self, pre: Prefill, logits=None):
-        """Reset the device state for the prefill `pre` and decode the first token from its last rows."""
-        self.bind(pre.cache, pre.kinfo_prefix)
-        self.plen.copy_(pre.plen)
-        hip.decode_init(self.state, self.plen, self.out)
-        if self.logp is not None:
-            self.logp.zero_()
-        if self.greedy is not None:
-            self.greedy.zero_()
-        if self.gstate is not None:       # every request starts in state 0 (a device op: the prefill graph captures it)
-            self.gstate.zero_()
-        if self.beam is not None:         # every request starts from {0, -inf, ...} (a device copy: the prefill graph captures it)
-            self.beam.copy_(self.beam_init)
-        self._token(pre.x_last, logits)
-
-    def _w(self, name):
-        """A layer projection as the fused step streams it: (weight, {}) or (e4m3 codes, {"wscale": row scales})."""
-        if self.weights == "bf16":
-            return self.model.W(name), {}
-        codes, scales = self.model._dec_fp8(name)
-        return codes, {"wscale": scales}
-
-    def _token(self, x, logits=None, verify=False):
-        """final norm + LM head over the hi / lo planes + argmax -> out[:, t], EOS mask, t + 1 (lap.py:716-724).  A context
-        with sampling words runs the sampling LM head, which is the greedy one while the words hold inv_t = 0.
-        verify (a speculating context's step): the greedy head on the S rows of x, then the accept kernel."""
-        m = self.model
-        if self.weights == "fp8":         # one e4m3 plane of the f32 table
-            hi, scales = m._dec_fp8("llm/embed")
-            lo, kw = None, {"wscale": scales}
-        else:
-            hi, lo, kw = m.W("llm/embed"), m.ps.w16lo("llm/embed"), {}
-        if self.allowed is not None:      # the LM head streams the allowed rows only
-            kw["ids"] = self.allowed
-        if self.score is not None:        # the TARGET head on the rows of x (one: token 0), then the finish that writes their logp / greedy
-            hip.decode_lm_head_score(self.state, self.score_words, self.ref, x, m.F("llm/final_norm"), hi, lo, self.pval, self.pidx,
-                                     self.plp, logits, **kw)
-            hip.decode_score_finish(self.state, self.pval, self.pidx, self.plp, self.ref, self.logp.view(-1), self.greedy.view(-1),
-                                    x.shape[0])
-            return
-        if self.beam is not None and self.grammar is not None:    # the head over the union, then the top-N over every row's state
-            g = self.grammar
-            hip.decode_lm_head(self.state, x, m.F("llm/final_norm"), hi, lo, self.pval, self.pidx, self.logits, **(kw | {"ids": g.union}))
-            hip.decode_beam_grammar_topn(self.state, self.beam, self.gstate, g.offsets, g.ids, g.next, self.logits, self.cand_logp,
-                                         self.cand_id, self.cand_next, self.cap)
-            hip.decode_beam_grammar_select(self.state, self.beam, self.gstate, self.cand_logp, self.cand_id, self.cand_next, self.out,
-                                           self.logp, m.config.vocab_size, m.EOS_TOKEN)
-            return
-        if self.beam is not None:         # the plain head stores the logits, topn and select finish the step
-            hip.decode_lm_head(self.state, x, m.F("llm/final_norm"), hi, lo, self.pval, self.pidx, self.logits, **kw)
-            hip.decode_beam_topn(self.state, self.beam, self.logits, self.cand_logp, self.cand_id, self.cap)
-            hip.decode_beam_select(self.state, self.beam, self.cand_logp, self.cand_id, self.out, self.logp, m.config.vocab_size,
-                                   m.EOS_TOKEN)
-            return
-        if verify and self.J:             # the plain head over the union stores the S rows of logits, the finish draws them in sequence
-            g = self.grammar
-            hip.decode_lm_head(self.state, x, m.F("llm/final_norm"), hi, lo, self.pval, self.pidx, self.logits, **(kw | {"ids": g.union}))
-            hip.decode_grammar_spec_finish(self.state, self.sampling, self.gstate, g.offsets, g.ids, g.next, self.logits, self.draft,
-                                           self.out, m.EOS_TOKEN, logp=self.logp)
-            return
-        if verify:
-            hip.decode_lm_head(self.state, x, m.F("llm/final_norm"), hi, lo, self.pval, self.pidx, None, **kw)
-            hip.decode_spec_accept(self.state, self.pval, self.pidx, self.draft, self.out, m.EOS_TOKEN)
-            return
-        if self.grammar is not None:      # the plain head over the union stores the logits, the grammar kernel draws and moves gstate
-            g = self.grammar
-            lg = self.logits[:self.B]     # (a jump-forward context: row 0 of its S rows)
-            hip.decode_lm_head(self.state, x, m.F("llm/final_norm"), hi, lo, self.pval, self.pidx, lg, **(kw | {"ids": g.union}))
-            hip.decode_grammar_finish(self.state, self.sampling, self.gstate, g.offsets, g.ids, g.next, lg, self.out,
-                                      m.EOS_TOKEN, logp=self.logp)
-            if logits is not None:        # (debug: the caller's copy of what the draw saw)
-                logits.copy_(lg)
-            return
-        if self.filter is not None:       # the plain head stores the logits (its partials are not read), the filter kernel draws
-            hip.decode_lm_head(self.state, x, m.F("llm/final_norm"), hi, lo, self.pval, self.pidx, self.logits, **kw)
-            hip.decode_filter_finish(self.state, self.sampling, self.filter, self.logits, self.out, m.EOS_TOKEN, logp=self.logp)
-            if logits is not None:        # (debug: the caller's copy of what the draw saw)
-                logits.copy_(self.logits)
-            return
-        if self.logp is not None:         # the same head with the log-sum-exp partials, and the finish that turns them into logp[:, t]
-            hip.decode_lm_head_lp(self.state, self.sampling, x, m.F("llm/final_norm"), hi, lo, self.pval, self.pidx, self.plp, logits, **kw)
-            hip.decode_finish_lp(self.state, self.pval, self.pidx, self.plp, self.out, self.logp, m.EOS_TOKEN)
-            return
-        if self.sampling is not None:
-            hip.decode_lm_head_sample(self.state, self.sampling, x, m.F("llm/final_norm"), hi, lo, self.pval, self.pidx, logits, **kw)
-        else:
-            hip.decode_lm_head(self.state, x, m.F("llm/final_norm"), hi, lo, self.pval, self.pidx, logits, **kw)
-        hip.decode_finish(self.state, self.pval, self.pidx, self.out, m.EOS_TOKEN)
-
-    def step(self, logits=None):
-        """One decode step (lap.py:734-752) + its token, positions and stop condition from the device state: replays unchanged."""
-        m = self.model
-        v = m.v
-        NH, HD, KV = v.num_heads, v.head_dim, v.num_kv_heads
-        rows, lo, hi = m.ps.embed_rows()
-        rows_of_one = bool(self.S or self.J or (self.score or 0) >= 2)      # the rows are S >= 2 positions of one sequence
-        if self.beam is not None:         # the generated K / V of every beam become those of the parent the last select chose
-            hip.decode_beam_reorder(self.state, self.beam, self.gen)
-        if self.score:                    # row r feeds the candidate's ids[t-1+r]  (score=1: the plain B = 1 layers)
-            hip.decode_score_embed(self.state, rows, lo, hi, self.ref, self.x, math.sqrt(v.width))
-        elif rows_of_one:
-            hip.decode_spec_draft(self.state, self.ref, self.out, self.draft)
-            if self.J:
-                g = self.grammar
-                hip.decode_grammar_draft(self.state, self.gstate, g.offsets, g.ids, g.next, self.draft, self.out, m.config.vocab_size,
-                                         m.EOS_TOKEN)
-            hip.decode_spec_embed(self.state, rows, lo, hi, self.out, self.draft, self.x, math.sqrt(v.width))
-        else:
-            hip.decode_embed(self.state, rows, lo, hi, self.out, self.x, math.sqrt(v.width))
-        for l in range(v.depth):
-            p = f"llm/{l}/"
-            gk, gv = self.gen[l, 0], self.gen[l, 1]
-            w, kw = self._w(p + "wqkv0")
-            ck, cv = self.prefix[l]
-            if rows_of_one:
-                hip.decode_spec_qkv(self.state, self.x, m.F(p + "n_attn"), w, self.q, gk, gv, NH, HD, HD ** -0.5, **kw)
-                hip.decode_spec_attention(self.state, self.q, ck, cv, self.kinfo, self.Pn, gk, gv, self.o, self.attn_scratch, NH, KV, HD)
-            else:
-                hip.decode_qkv(self.state, self.x, m.F(p + "n_attn"), w, self.q, gk, gv, NH, HD, HD ** -0.5, **kw)
-                hip.decode_attention(self.state, self.q, ck, cv, self.kinfo, self.Pn, gk, gv, self.o, self.attn_scratch, NH, KV, HD)
-            w, kw = self._w(p + "wo0")
-            hip.decode_proj_residual(self.state, self.o, w, self.x, self.xa, **kw)
-            w, kw = self._w(p + "wgu0")
-            hip.decode_gate_up(self.state, self.xa, m.F(p + "n_ffw"), w, self.act, **kw)
-            w, kw = self._w(p + "wd0")
-            hip.decode_proj_residual(self.state, self.act, w, self.xa, self.x, kwaves=hip.DECODE_KWAVES_DOWN, **kw)
-        self._token(self.x, logits, verify=rows_of_one)

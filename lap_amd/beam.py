@@ -211,7 +211,7 @@ def check_num_beams(num_beams, batch: int, *, decode: str = "fused", temperature
         raise ValueError("num_beams is deterministic: top_k / top_p must be None")
     if speculate is not None:
         raise ValueError("num_beams does not combine with speculate")
-    if grammar is not None:         # (the automaton itself is checked by `ar_decode.check_grammar`, which also rejects allowed_tokens)
+    if grammar is not None:         # (the automaton itself is checked by `grammar.check_grammar`, which also rejects allowed_tokens)
         from lap_amd.grammar import DeviceAutomaton, TokenAutomaton
 
         if not isinstance(grammar.host if isinstance(grammar, DeviceAutomaton) else grammar, TokenAutomaton):

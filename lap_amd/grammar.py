@@ -147,6 +147,32 @@ def check_automaton(a: TokenAutomaton) -> TokenAutomaton:
     return a
 
 
+def check_grammar(grammar, vocab_size: int, eos_token: int, *, allowed_tokens=None, top_k=None, top_p=None, speculate=None,
+                  sampler: str = "device", temperature: float = 0.0):
+    """The host automaton of a grammar-constrained request (`grammar`: a TokenAutomaton or its `to_device` form), checked
+    (`check_automaton`) and compared with the model's vocabulary and EOS token; ValueError naming what it does not combine with:
+    allowed_tokens (the automaton's union replaces the set), top_k / top_p, speculate, and the host sampler at temperature > 0
+    (the constrained draw is part of the device sampler)."""
+    host = grammar.host if isinstance(grammar, DeviceAutomaton) else grammar
+    if not isinstance(host, TokenAutomaton):
+        raise ValueError(f"grammar: expected a grammar.TokenAutomaton (or its to_device form), got {type(grammar).__name__}")
+    if allowed_tokens is not None:
+        raise ValueError("grammar does not combine with allowed_tokens: the union of the automaton's edges replaces the set")
+    if top_k is not None or top_p is not None:
+        raise ValueError("grammar does not combine with top_k / top_p")
+    if speculate is not None:
+        raise ValueError("grammar does not combine with speculate")
+    if sampler != "device" and temperature > 0.0:
+        raise ValueError(f"grammar at temperature > 0 needs sampler=\"device\" (the constrained draw is part of the device sampler), "
+                         f"got sampler={sampler!r}")
+    if (host.vocab_size, host.eos_token) != (vocab_size, eos_token):
+        raise ValueError(f"grammar: the automaton was built for vocab_size {host.vocab_size} and EOS token {host.eos_token}, the model "
+                         f"has vocab_size {vocab_size} and EOS token {eos_token}")
+    if not isinstance(grammar, DeviceAutomaton):        # (`to_device` has checked the other form)
+        check_automaton(host)
+    return host
+
+
 def decode_reference(logits_per_step, automaton: TokenAutomaton, temperature: float, seed: int, rows: int | None = None, start=None):
     """The specification of the grammar-constrained draw (csrc/decode_grammar.hip), on float32 logits [T, B, V] of T steps.
     At step t, row b in state q takes `sampling.sample_from_logits` of its logits set to -inf outside `allowed(q)`: the argmax of

@@ -2094,7 +2094,7 @@ def decode_beam_select(state, beam, cand_logp, cand_id, out, logp, V, eos_token)
 
 
 def decode_beam_reorder(state, beam, gen):
-    """gen bf16 [depth, 2, N, cap, head_dim] (`DecodeCtx.gen`): row b of every layer's K and V becomes row parent[b], in place, at
+    """gen bf16 [depth, 2, N, cap, head_dim] (`decode_ctx.DecodeCtx.gen`): row b of every layer's K and V becomes row parent[b], in place, at
     the positions below t (lap_decode_beam_reorder); nothing moves when the parents are the identity."""
     _dreq(gen, torch.bfloat16, "gen")
     if gen.dim() != 5 or gen.shape[1] != 2 or gen.shape[4] % 8:

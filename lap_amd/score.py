@@ -55,7 +55,7 @@ def score_reference(logits_rows, targets, *, temperature: float = 0.0, allowed=N
 
 
 def check_score_rows(rows) -> int:
-    """`rows` of a scoring request (or `score` of a DecodeCtx) as the number of rows S of a step; ValueError naming the value."""
+    """`rows` of a scoring request (or `score` of a decode_ctx.DecodeCtx) as the number of rows S of a step; ValueError naming the value."""
     if isinstance(rows, bool) or not isinstance(rows, (int, np.integer)):
         raise ValueError(f"score rows must be an integer, got {rows!r}")
     S = int(rows)
@@ -66,7 +66,7 @@ def check_score_rows(rows) -> int:
 
 def check_score_ctx(score, B: int, *, sampling: bool = False, filtering: bool = False, speculate=None, grammar=None, jump_forward=None,
                     beams=None) -> int:
-    """`score=S` of a DecodeCtx as S; ValueError naming what a scoring context does not combine with."""
+    """`score=S` of a decode_ctx.DecodeCtx as S; ValueError naming what a scoring context does not combine with."""
     S = check_score_rows(score)
     if B != 1:
         raise ValueError(f"score needs B = 1 (the rows of a step are positions of one sequence), got B {B}")

@@ -308,6 +308,60 @@ def test_decode_ctx_graphed_decoder_and_policy_reject_at_construction():
             ARPolicy(Base(), sample_kwargs={"jump_forward": 4} | kw)
 
 
+def _cpu_ids(dtype="int32"):
+    import torch
+
+    return torch.tensor([1, 2, 3], dtype=getattr(torch, dtype))
+
+
+# (kind the keywords would make, keywords of DecodeCtx with "B" among them, the ValueError): what the CPU suites pin of the checks
+# the constructor runs (decode weights, `check_score_ctx`, `check_num_beams`, `check_speculate`, its own) in the constructor's order
+CTX_BAD = [
+    ("plain", {"weights": "int4"}, "decode_weights must be one of"),
+    ("plain", {"allowed": _cpu_ids("int64")}, "allowed must be the int32 device ids"),
+    ("sampling", {"sampling": True, "allowed": _cpu_ids()}, "allowed must be the int32 device ids"),
+    ("logprob", {"logprobs": True, "weights": "fp4"}, "decode_weights must be one of"),
+    ("logprob", {"logprobs": True, "sampling": True, "allowed": _cpu_ids()}, "allowed must be the int32 device ids"),
+    ("filter", {"filtering": True}, "filtering needs sampling=True"),
+    ("filter", {"filtering": True, "logprobs": True}, "filtering needs sampling=True"),
+    ("filter", {"filtering": True, "sampling": True, "allowed": _cpu_ids()}, "allowed must be the int32 device ids"),
+    ("speculate", {"speculate": 4, "B": 2}, "speculate needs an observation of batch 1"),
+    ("speculate", {"speculate": 1}, r"speculate must lie in \[2, 8\]"),
+    ("speculate", {"speculate": 2.5}, "speculate must be an integer"),
+    ("speculate", {"speculate": 4, "sampling": True}, "speculate is greedy"),
+    ("speculate", {"speculate": 4, "logprobs": True}, "speculate does not return log-probabilities"),
+    ("speculate", {"speculate": 4, "filtering": True}, "filtering needs sampling=True"),
+    ("speculate", {"speculate": 4, "allowed": _cpu_ids()}, "allowed must be the int32 device ids"),
+    ("speculate", {"speculate": 4, "weights": "fp16"}, "decode_weights must be one of"),
+    ("score", {"score": 4, "B": 2}, r"B = 1.*got B 2"),
+    ("score", {"score": 9}, r"\[1, 8\].*got 9"),
+    ("score", {"score": 4, "sampling": True}, "score does not combine with sampling"),
+    ("score", {"score": 4, "sampling": True, "filtering": True}, "score does not combine with sampling"),
+    ("score", {"score": 4, "filtering": True}, "score does not combine with filtering"),
+    ("score", {"score": 4, "speculate": 4}, "score does not combine with speculate"),
+    ("score", {"score": 4, "jump_forward": 4}, "score does not combine with jump_forward"),
+    ("score", {"score": 4, "beams": 2}, "score does not combine with beams"),
+    ("score", {"score": 4, "weights": "fp4", "sampling": True}, "decode_weights must be one of"),
+    ("score", {"score": 4, "allowed": _cpu_ids()}, "allowed must be the int32 device ids"),
+    ("beam", {"beams": 4, "B": 2}, "beams=4 are the rows of the batch, got B 2"),
+    ("beam", {"beams": 9, "B": 9}, r"num_beams must lie in \[1, 8\]"),
+    ("beam", {"beams": 2, "B": 2, "sampling": True}, "num_beams is deterministic: temperature must be 0"),
+    ("beam", {"beams": 2, "B": 2, "filtering": True}, "num_beams is deterministic: top_k / top_p must be None"),
+    ("beam", {"beams": 2, "B": 2, "speculate": 2}, "num_beams does not combine with speculate"),
+    ("beam", {"beams": 2, "B": 2, "jump_forward": 2}, "num_beams does not combine with jump_forward"),
+]
+
+
+@pytest.mark.parametrize("kind, kw, word", CTX_BAD, ids=[f"{k}-{i}" for i, (k, _, _) in enumerate(CTX_BAD)])
+def test_decode_ctx_of_every_kind_rejects_before_it_allocates(kind, kw, word):
+    """The stub has no device and no widths: a constructor that reached its first allocation would raise AttributeError."""
+    from lap_amd.ar_decode import DecodeCtx
+
+    kw = {"B": 1} | kw
+    with pytest.raises(ValueError, match=word):
+        DecodeCtx(_Stub(), kw.pop("B"), 8, 8, **kw)
+
+
 def test_signatures_default_to_no_jump_forward():
     import inspect
 
