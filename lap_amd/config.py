@@ -427,6 +427,22 @@ class TrainConfig:
     # the VLM expert's projections on e4m3 operands with per-tensor scaling (csrc/gemm_fp8.hip); weight gradients,
     # the action expert, SigLIP and every non-GEMM op stay bf16.
     gemm_dtype: str = "bf16"
+    # Engine option (not a reference field): every optimizer step runs this many forward + backward passes over
+    # batch_size / (ranks * grad_accum_steps) samples per rank and applies the sum of their gradients once, so a recipe's
+    # batch_size can be trained on fewer GPUs than it was written for.  `batch_size` stays the GLOBAL batch of one optimizer step.
+    grad_accum_steps: int = 1
+
+    def __post_init__(self):
+        if not isinstance(self.grad_accum_steps, int) or self.grad_accum_steps < 1:
+            raise ValueError(f"grad_accum_steps must be an integer >= 1, got {self.grad_accum_steps!r}")
+        self.micro_batch_size(1)
+
+    def micro_batch_size(self, world: int = 1) -> int:
+        """Samples per rank and micro-step: batch_size / (world * grad_accum_steps), which must divide."""
+        parts = int(world) * self.grad_accum_steps
+        if self.batch_size % parts:
+            raise ValueError(f"batch_size {self.batch_size} must be divisible by ranks x grad_accum_steps = {world} x {self.grad_accum_steps}")
+        return self.batch_size // parts
 
     def is_frozen(self, path: str) -> bool:
         f = self.freeze_filter

@@ -67,12 +67,17 @@ class UnitPipeline:
         self.lookahead = int(os.environ.get("LAP_OPT_LOOKAHEAD", "9"))
         self.pace_in_layer = os.environ.get("LAP_OPT_PACE", "gemm") == "gemm"
         self._todo_args = None
+        self._todo_accum = False
         # single rank: a weight gradient is final when its GEMM stores it, so the assembly weight-gradient kernels add its sum of squares
         # to the norm themselves (lap_gemm_wgrad_f32) and the per-unit pass skips those tensors; under FSDP the norm is that of the
         # REDUCED gradient and stays a pass over the shard.  LAP_FOLD_SUMSQ=0: off (A/B)
         self.fold_sumsq = self.is_cuda and self.world_size == 1 and os.environ.get("LAP_FOLD_SUMSQ", "1") != "0"
         self.folded = set()
         self._bwd_open = False      # a backward has added to `sumsq` and no optimizer pass has consumed it yet (before_backward)
+        # gradient accumulation (set_accum): micro-step k of K per optimizer step.  (0, 1): off — none of the K > 1 branches below is
+        # taken and no accumulator exists
+        self.accum = (0, 1)
+        self._fold_saved = self.fold_sumsq
         # release order = the order in which the forward first needs the units: the store's order, except that the adaRMS
         # bank (built last) is needed second — the model issues embed_suffix (on its second stream) ahead of the SigLIP tower
         sched = [u for u in store.units if u.name != "ada"]
@@ -101,13 +106,32 @@ class UnitPipeline:
         self.wait_unit("small")
         self.folded = set()      # tensors whose weight-gradient GEMM has already added sum(g^2) to the norm (fold_sumsq)
 
+    def set_accum(self, k: int, K: int):
+        """Step runner: the next backward is micro-step k of the K that make up one optimizer step.  With K > 1 every big unit's
+        gradient is folded into its f32 accumulator (`ParamStore.grad_accumulator`) where the norm pass ran before, the last fold
+        adds the accumulated gradient's sum of squares to the norm, and the optimizer reads the accumulator.  `fold_sumsq` is off
+        for such a step: a weight-gradient GEMM's own sum of squares is that of a micro-gradient."""
+        if not 0 <= k < K:
+            raise ValueError(f"micro-step {k} of {K}")
+        if K > 1 and self.accum[1] == 1:
+            self._fold_saved = self.fold_sumsq
+        self.accum = (int(k), int(K))
+        self.fold_sumsq = self._fold_saved and K == 1
+        if K > 1:
+            self.folded = set()
+
     def before_backward(self):
         """The previous optimizer pass must be done READING the gradient buffers before the backward rewrites them."""
         self.flush()
         if self.is_cuda and self._opt_done is not None:
             torch.cuda.current_stream().wait_event(self._opt_done)
             self._opt_done = None
-        if self._bwd_open:
+        if self.accum[0] > 0:
+            # a later micro-step of the same optimizer step: the partial sums stay (only the small unit's and the last folds' are added,
+            # all on the last micro-step), and the previous micro-step's folds must be done reading the gradient buffers
+            if self.is_cuda:
+                torch.cuda.current_stream().wait_stream(self.side)
+        elif self._bwd_open:
             # The previous backward was not followed by an optimizer pass (`LAP.loss_and_grad` used directly: gradient checks, an
             # exception mid-step, a future accumulation loop): its partial sums of squares would inflate the next global norm and
             # clip factor (ADVICE r3).  run_optimizer is the only place that clears them on the normal path; do it here, ordered
@@ -172,6 +196,11 @@ class UnitPipeline:
         if also is not None and self.is_cuda:
             for st in (also if isinstance(also, (list, tuple)) else [also]):
                 self.side.wait_stream(st)
+        k, K = self.accum
+        if K > 1:
+            self._accumulate(u, k, K)
+            self._pending = True
+            return
         with self._on_side():
             self._reduce_grads(u)
             if self.is_cuda:  # (the CPU/gloo tests exercise the collectives only; kernels need a GPU)
@@ -180,6 +209,29 @@ class UnitPipeline:
                 for a, b in self._unfolded(u, self.ps.local_train_ranges(u)):     # one range (the whole shard) unless a freeze filter is set
                     hip.sumsq_f32(g[a:b], self.sumsq[slot:slot + 1])
         self._pending = True
+
+    def _accumulate(self, u, k: int, K: int):
+        """grads_ready under gradient accumulation.  A big unit: its micro-gradient is reduced as always (under FSDP the
+        accumulator is the REDUCED shard) and folded into the f32 accumulator; the last fold adds the accumulated gradient's sum of
+        squares to the norm.  The replicated unit accumulates in its own f32 gradient buffer (atomics; zeroed before micro-step 0
+        only): it is reduced and its sum of squares taken once, on the last micro-step."""
+        if not u.big and k < K - 1:
+            return
+        last = k == K - 1
+        with self._on_side():
+            self._reduce_grads(u)
+            if not self.is_cuda:
+                return
+            slot = 0 if (self.ps.sharded(u) or self.world_size == 1) else 1
+            ss = self.sumsq[slot:slot + 1]
+            g = self.ps.gshard[u.name]
+            if not u.big:
+                for a, b in self.ps.local_train_ranges(u):
+                    hip.sumsq_f32(g[a:b], ss)
+                return
+            acc = self.ps.grad_accumulator(u.name)
+            for a, b in self.ps.local_train_ranges(u):
+                hip.grad_fold(acc[a:b], g[a:b], first=k == 0, sumsq=ss if last else None)
 
     def finish_grads(self):
         """Compute stream waits for every reduction / norm partial (needed for the returned grad_norm)."""
@@ -214,6 +266,7 @@ class UnitPipeline:
                 norm_ready.record(self.side)
         # the per-unit updates: build_specs puts the small replicated unit first, then forward order
         self._todo_args = opt
+        self._todo_accum = self.accum[1] > 1     # (kept with the pass: it is released while the NEXT step's forward runs)
         self._released = 0
         import os
         serial = os.environ.get("LAP_OPT_SERIAL", "0") == "1"     # A/B: the whole pass alone on the chip, the compute stream waits for it
@@ -238,10 +291,16 @@ class UnitPipeline:
                 lo, _ = ps.shard_range(u)
                 ema = ps.ema.get(u.name)
                 lo16 = ps.lo16.get(u.name)
+                # the gradient of this pass: the f32 accumulator where the step accumulated (big units), else the gradient shard
+                grad = ps.gshard[u.name]
+                if self._todo_accum and u.big and ps.unit_trainable(u):
+                    if u.name not in ps.gacc:     # (gshard holds the LAST micro-gradient only: never a silent fallback)
+                        raise RuntimeError(f"accumulated step: unit {u.name} was never declared complete (grads_ready), it has no accumulator")
+                    grad = ps.gacc[u.name]
                 for a, b in ps.local_train_ranges(u):   # shard coordinates; frozen tensors are skipped altogether
                     p16 = ps.full16[u.name][lo + a:lo + b] if u.big else None
                     hip.adamw_ema(ps.master[u.name][a:b], ps.m[u.name][a:b], ps.v[u.name][a:b], ema[a:b] if ema is not None else None,
-                                  ps.gshard[u.name][a:b], p16, self.scal, opt.b1, opt.b2, opt.eps, opt.weight_decay, opt.clip_gradient_norm,
+                                  grad[a:b], p16, self.scal, opt.b1, opt.b2, opt.eps, opt.weight_decay, opt.clip_gradient_norm,
                                   p16lo=lo16[lo + a:lo + b] if lo16 is not None else None)
                 if ps.unit_trainable(u):
                     self._after_unit_update(u)

@@ -205,6 +205,7 @@ SIGNATURES: dict[str, list] = {
     "lap_adamw_ema_hilo": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _f, _f, _f, _f, _f, _vp],
     "lap_sumsq_f32": [_vp, _ll, _vp, _vp],
     "lap_sumsq_bf16": [_vp, _ll, _vp, _vp],
+    "lap_grad_fold": [_vp, _vp, _i, _ll, _i, _vp, _vp],
     "lap_adamw_ema_g16": [_vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _f, _f, _f, _f, _f, _vp],
     "lap_argmax_rows_f32": [_vp, _i, _i, _i, _vp, _vp],
     "lap_gumbel_argmax_rows_f32": [_vp, _i, _i, _i, _f, C.c_uint, C.c_uint, _i, _vp, _vp],
@@ -1010,6 +1011,19 @@ def sumsq_f32(x, out):
         call("lap_sumsq_bf16", _p(x), x.numel(), _p(out))
         return
     call("lap_sumsq_f32", _p(x), x.numel(), _p(out))
+
+
+def grad_fold(acc, g, first, sumsq=None):
+    """Gradient accumulation: acc = g (`first`) or acc += g, element by element in f32; g a bf16 or an f32 gradient buffer of acc's
+    size.  `sumsq` (a one-element f32 tensor, on the last micro-step): sumsq[0] += sum of the squares of the values stored."""
+    _req(acc, torch.float32, "acc")
+    if g.dtype not in (torch.bfloat16, torch.float32) or not g.is_cuda:
+        raise TypeError(f"g: expected cuda bf16 or f32, got {g.device} {g.dtype}")
+    if g.numel() != acc.numel() or not (acc.is_contiguous() and g.is_contiguous()):
+        raise ValueError("grad_fold: acc and g must be contiguous and of one size")
+    if sumsq is not None:
+        _req(sumsq, torch.float32, "sumsq")
+    call("lap_grad_fold", _p(acc), _p(g), int(g.dtype == torch.bfloat16), acc.numel(), int(bool(first)), _p(sumsq))
 
 
 def adamw_ema(p, m, v, ema, g, p16, scalars, b1, b2, eps, wd, max_norm, p16lo=None):

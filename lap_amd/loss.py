@@ -247,28 +247,68 @@ class Mix(NamedTuple):
     extra_metrics: dict
 
 
+class KindMasks(NamedTuple):
+    sm: torch.Tensor            # [B] bool sample mask (all ones without one)
+    vqa_m: torch.Tensor         # [B] bool active VQA / prediction / language-action samples (with `mixing`, else None)
+    pred_m: torch.Tensor
+    lang_m: torch.Tensor
+    act_mask: torch.Tensor      # [B] bool: samples that carry the action loss
+    mixing: bool
+
+
+def sample_kind_masks(cfg, B: int, dev, sample_mask, is_vqa, is_pred, *, lang_on: bool) -> KindMasks:
+    """The sample masks of the loss (lap.py:400-409,480-486,557-566) from the batch's flags alone: what `mix_sample_weights`
+    weighs by and what the loss divides by (`global_denominators`)."""
+    sm = sample_mask.to(dev, torch.bool) if sample_mask is not None else torch.ones(B, dtype=torch.bool, device=dev)
+    vqa = is_vqa.to(dev, torch.bool) if is_vqa is not None else None
+    pred = is_pred.to(dev, torch.bool) if is_pred is not None else None
+    if not (lang_on and (cfg.enable_vqa_training or cfg.enable_prediction_training)):
+        # (also the langact-off branch: the VQA / prediction masks reach the action loss as they came, lap.py:557-566)
+        act_mask = torch.ones(B, dtype=torch.bool, device=dev)
+        if vqa is not None:
+            act_mask = act_mask & ~vqa
+        if pred is not None:
+            act_mask = act_mask & ~pred
+        return KindMasks(sm, None, None, None, act_mask, False)
+    vqa_m = (vqa if vqa is not None else torch.zeros(B, dtype=torch.bool, device=dev)) & sm      # lap.py:480-486
+    pred_m = (pred if pred is not None else torch.zeros(B, dtype=torch.bool, device=dev)) & sm
+    lang_m = ~((vqa if vqa is not None else vqa_m) | (pred if pred is not None else pred_m)) & sm
+    act_mask = ~vqa_m & ~pred_m          # the masks were AND-ed with the sample mask before this point (lap.py:484-485,562-566)
+    return KindMasks(sm, vqa_m, pred_m, lang_m, act_mask, True)
+
+
+def global_denominators(cfg, observations, comm=None, device=None):
+    """(n_active, n_action) of the K micro-batches `observations` taken together, as `LAP._loss_impl` counts them for one batch:
+    active samples (the batch size without a sample mask) and samples that carry the action loss, each summed over the
+    micro-batches and — one `comm.all_reduce_sum` for both — over the ranks, then clamped to >= 1.  f32 device scalars; n_action is
+    None without action training.  Passed as `denominators=` to every micro-step, they make the micro-steps' losses and gradients
+    sum to those of the whole batch."""
+    lang_on, act_on = cfg.enable_langact_training, cfg.enable_action_training
+    dev = torch.device(device) if device is not None else observations[0].tokenized_prompt.device
+    tot = torch.zeros(2, dtype=torch.float32, device=dev)
+    for obs in observations:
+        B = obs.tokenized_prompt.shape[0]
+        km = sample_kind_masks(cfg, B, dev, obs.sample_mask, obs.is_vqa_sample if cfg.enable_vqa_training else None,
+                               obs.is_prediction_sample if cfg.enable_prediction_training else None, lang_on=lang_on)
+        tot = tot + torch.stack([km.sm.to(torch.float32).sum(), km.act_mask.to(torch.float32).sum()])
+    if comm is not None:
+        tot = comm.all_reduce_sum(tot)
+    tot = torch.clamp(tot, min=1.0)
+    return tot[0], (tot[1] if act_on else None)
+
+
 def mix_sample_weights(cfg, lang_loss, sample_mask, is_vqa, is_pred, vqa_dataset_id, *, lang_on: bool) -> Mix:
     """Per-sample weights: language loss x {language, VQA (optionally per dataset), prediction} weight by sample kind; action loss
     only on samples that are neither VQA nor prediction samples.  `is_vqa` / `is_pred` are the reference's `vqa_mask` /
     `pred_mask` (lap.py:400-409): None unless that kind of training is on and the observation marks its samples."""
     dev, B = lang_loss.device, lang_loss.shape[0]
     fb = lambda t: t.to(torch.float32)
-    sm = sample_mask if sample_mask is not None else torch.ones(B, dtype=torch.bool, device=dev)
-    vqa = is_vqa.to(dev, torch.bool) if is_vqa is not None else None
-    pred = is_pred.to(dev, torch.bool) if is_pred is not None else None
-    if not (lang_on and (cfg.enable_vqa_training or cfg.enable_prediction_training)):
-        # (also the langact-off branch: the VQA / prediction masks reach the action loss as they came, lap.py:557-566)
+    km = sample_kind_masks(cfg, B, dev, sample_mask, is_vqa, is_pred, lang_on=lang_on)
+    sm, vqa_m, pred_m, lang_m, act_mask = km.sm, km.vqa_m, km.pred_m, km.lang_m, km.act_mask
+    if not km.mixing:
         wl = torch.full((B,), cfg.language_loss_weight if lang_on else 0.0, dtype=torch.float32, device=dev)
-        act_mask = torch.ones(B, dtype=torch.bool, device=dev)
-        if vqa is not None:
-            act_mask = act_mask & ~vqa
-        if pred is not None:
-            act_mask = act_mask & ~pred
         return Mix(wl, act_mask, False, {})
     extra_metrics = {}
-    vqa_m = (vqa if vqa is not None else torch.zeros(B, dtype=torch.bool, device=dev)) & sm      # lap.py:480-486
-    pred_m = (pred if pred is not None else torch.zeros(B, dtype=torch.bool, device=dev)) & sm
-    lang_m = ~((vqa if vqa is not None else vqa_m) | (pred if pred is not None else pred_m)) & sm
     vqa_w = torch.full((B,), cfg.vqa_loss_weight, dtype=torch.float32, device=dev)               # lap.py:526-543
     if cfg.enable_vqa_training and cfg.vqa_loss_weights and vqa_dataset_id is not None:
         ids = vqa_dataset_id.to(dev)
@@ -276,7 +316,6 @@ def mix_sample_weights(cfg, lang_loss, sample_mask, is_vqa, is_pred, vqa_dataset
             if name in VQA_DATASET_ID_MAP:
                 vqa_w = torch.where(ids == VQA_DATASET_ID_MAP[name], torch.full_like(vqa_w, float(wgt)), vqa_w)
     wl = vqa_w * fb(vqa_m) + cfg.prediction_loss_weight * fb(pred_m) + cfg.language_loss_weight * fb(lang_m)
-    act_mask = ~vqa_m & ~pred_m          # the masks were AND-ed with the sample mask before this point (lap.py:484-485,562-566)
     n_act_loc = fb(sm).sum()
     for pfx, msk in (("vqa_", vqa_m), ("pred_", pred_m), ("langact_", lang_m)):   # metrics.py:49-56 (per-rank values)
         if (pfx == "vqa_" and not cfg.enable_vqa_training) or (pfx == "pred_" and not cfg.enable_prediction_training):

@@ -516,7 +516,7 @@ class LAP:
 
     # ================================================================== training forward (+ backward)
     def _loss_impl(self, rng, observation: CoTObservation, actions: torch.Tensor, *, train: bool, noise=None, time=None,
-                   backward: bool, collect: dict | None = None, verbose: bool = False):
+                   backward: bool, collect: dict | None = None, verbose: bool = False, denominators=None):
         cfg = self.config
         # lap.py:426-462,557-596: three branches — both losses (LAP-3B); enable_action_training=False: `llm([prefix])` and the
         # cross entropy only (VLA-0 style configs); enable_langact_training=False: both streams, flow matching only (pi0 style)
@@ -573,8 +573,13 @@ class LAP:
         wl, act_mask, mixing, extra_metrics = mix_sample_weights(
             cfg, lang_loss, sm, obs.is_vqa_sample if cfg.enable_vqa_training else None,
             obs.is_prediction_sample if cfg.enable_prediction_training else None, obs.vqa_dataset_id, lang_on=lang_on)
-        n_active = torch.clamp(self.comm.all_reduce_sum(fb(sm).sum().view(1)), min=1.0) if obs.sample_mask is not None else \
-            self.comm.all_reduce_sum(torch.tensor([float(B)], device=dev))
+        # `denominators` (gradient accumulation, loss.global_denominators): the counts of the WHOLE batch of the optimizer step in place
+        # of this micro-batch's, so that the micro-steps' losses and gradients sum to the big batch's
+        if denominators is not None:
+            n_active = denominators[0].to(dev, torch.float32).view(1)
+        else:
+            n_active = torch.clamp(self.comm.all_reduce_sum(fb(sm).sum().view(1)), min=1.0) if obs.sample_mask is not None else \
+                self.comm.all_reduce_sum(torch.tensor([float(B)], device=dev))
         # lang_term: sum / active samples, or the batch mean without a sample mask (lap.py:579-596; the action-off branch's
         # `final_loss` is the same expression)
         lang_term = (wl * lang_loss).sum() / n_active
@@ -582,7 +587,10 @@ class LAP:
         action_term = 0.0
         dv = None
         if act_on:
-            n_action = torch.clamp(self.comm.all_reduce_sum(fb(act_mask).sum().view(1)), min=1.0)
+            if denominators is not None:
+                n_action = denominators[1].to(dev, torch.float32).view(1)
+            else:
+                n_action = torch.clamp(self.comm.all_reduce_sum(fb(act_mask).sum().view(1)), min=1.0)
             coef = cfg.action_loss_weight * fb(act_mask) / n_action
             act_loss, dv = hip.mse_fwd_bwd(v_t.view(B, S * ad), u_t.view(B, S * ad), coef, need_grad=backward)
             action_term = (cfg.action_loss_weight * act_loss * fb(act_mask)).sum() / n_action
@@ -629,19 +637,23 @@ class LAP:
         return loss, metrics
 
     def compute_loss(self, rng, observation, actions, *, train: bool = False, stage_config=None, verbose_mode=None,
-                     return_augmented_images: bool = False, noise=None, time=None, collect=None):
+                     return_augmented_images: bool = False, noise=None, time=None, collect=None, denominators=None):
         """lap.py:380-602.  rng: int seed or torch.Generator.  `noise` / `time` may be given explicitly (parity tests).
-        verbose_mode (None: the config's, lap.py:393-394) adds the token-accuracy metrics and `per_sample_loss` (loss._token_metrics)."""
+        verbose_mode (None: the config's, lap.py:393-394) adds the token-accuracy metrics and `per_sample_loss` (loss._token_metrics).
+        `denominators`: see `loss_and_grad`."""
         verbose = bool(self.config.verbose_mode if verbose_mode is None else verbose_mode)
         return self._loss_impl(rng, observation, actions, train=train, noise=noise, time=time, backward=False, collect=collect,
-                               verbose=verbose)
+                               verbose=verbose, denominators=denominators)
 
-    def loss_and_grad(self, rng, observation, actions, *, train: bool = True, noise=None, time=None, collect=None):
+    def loss_and_grad(self, rng, observation, actions, *, train: bool = True, noise=None, time=None, collect=None, denominators=None):
         """Forward + backward; gradients land in self.ps.grad (engine layout; bf16 for the GEMM-weight units, f32 for the embedding table and
         the small unit: ParamStore.grad_dtype).  The caller zeroes the accumulated (f32) units first.  Verbose metrics follow the
-        config's `verbose_mode` (the reference's train step runs with the class attribute, scripts/train.py:351)."""
+        config's `verbose_mode` (the reference's train step runs with the class attribute, scripts/train.py:351).
+        `denominators=(n_active, n_action)`: f32 device scalars (n_action None where the action loss is off) that replace the two
+        counts the loss divides by — taken from this batch's masks and all-reduced when absent — in the loss and in both cotangents
+        (gradient accumulation: `loss.global_denominators` over the micro-batches of one optimizer step)."""
         return self._loss_impl(rng, observation, actions, train=train, noise=noise, time=time, backward=True, collect=collect,
-                               verbose=bool(self.config.verbose_mode))
+                               verbose=bool(self.config.verbose_mode), denominators=denominators)
 
     # ================================================================== serving
     @torch.no_grad()

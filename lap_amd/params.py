@@ -194,6 +194,7 @@ class ParamStore:
         self.ema: dict[str, torch.Tensor] = {}
         self.grad: dict[str, torch.Tensor] = {}     # unit -> full gradient buffer [padded numel], f32 or bf16 (grad_dtype)
         self.gshard: dict[str, torch.Tensor] = {}   # unit -> gradient shard of the same dtype (aliases grad when N == 1)
+        self.gacc: dict[str, torch.Tensor] = {}     # unit -> f32 accumulator shaped like gshard (gradient accumulation only: grad_accumulator)
         self.version = 0                            # bumped whenever parameter values change (derived copies re-quantise)
         self.frozen: dict[str, bool] = {}           # engine tensor -> excluded from gradient / optimizer (set_frozen)
         self._train_ranges: dict[str, list] = {}    # unit -> [(a, b)] trainable ranges in unit coordinates
@@ -308,6 +309,18 @@ class ParamStore:
             if a < b:
                 out.append((a - lo, b - lo))
         return out
+
+    def grad_accumulator(self, name: str) -> torch.Tensor:
+        """f32 accumulator of a trainable big unit's gradient shard over the micro-steps of one optimizer step (`grad_accum_steps`
+        > 1), allocated on first use: nothing exists while accumulation is off.  Shard-sized and indexed like `gshard[name]`; only
+        the unit's `local_train_ranges` are ever written or read (lap_amd/fsdp.py)."""
+        acc = self.gacc.get(name)
+        if acc is None:
+            u = self.unit_by_name[name]
+            if not u.big or not self.unit_trainable(u):
+                raise ValueError(f"unit {name} has no gradient accumulator (replicated units accumulate in `grad`; frozen units have no gradient)")
+            acc = self.gacc[name] = torch.zeros(self.gshard[name].numel(), dtype=torch.float32, device=self.device)
+        return acc
 
     # ---- views
     def _view(self, buf: torch.Tensor, name: str) -> torch.Tensor:

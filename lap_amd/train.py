@@ -160,7 +160,28 @@ class TrainingStepRunner:
         self.config = config
         self._scalars = None
 
+    @staticmethod
+    def micro_seed(rng, step: int, k: int, K: int):
+        """Seed of micro-step k of K: fold_in(rng, step), and with K > 1 fold_in of that with k.  A torch.Generator is passed on."""
+        if isinstance(rng, torch.Generator):
+            return rng
+        seed = int(rng) * 1_000_003 + step  # fold_in(rng, step)
+        return seed if K == 1 else seed * 1_000_003 + k
+
     def __call__(self, rng, state: TrainState, batch, step: int | None = None, *, noise=None, time=None):
+        """`batch`: one `(observation, actions)` pair, or with `grad_accum_steps = K > 1` a list of K such pairs, the micro-batches
+        of one optimizer step (`noise` / `time`, where given, are then lists of K too).  The K forward + backward passes divide by
+        the counts of the whole batch (`loss.global_denominators`), their gradients are summed in f32 (lap_amd/fsdp.py) and the
+        optimizer runs once: `state.step` counts optimizer steps.  In the returned info `loss` is the SUM of the micro-steps'
+        losses (= the loss of the whole batch), `grad_norm` the norm of the accumulated gradient, and every other metric the MEAN
+        over the micro-steps (non-scalar metrics: the last micro-step's)."""
+        K = self.config.grad_accum_steps
+        if K > 1:
+            return self._accumulated_step(rng, state, batch, step, noise, time)
+        if isinstance(batch, list) and len(batch) == 1:     # a list of one pair; anything else is the pair itself, as it always was
+            batch = batch[0]
+            noise = noise[0] if isinstance(noise, (list, tuple)) else noise
+            time = time[0] if isinstance(time, (list, tuple)) else time
         cfg = self.config
         model, ps = state.model, state.model.ps
         observation, actions = batch
@@ -182,6 +203,49 @@ class TrainingStepRunner:
         t = state.step + 1
         ema_decay, ema_on = cfg.get_ema_decay_for_step(step)
         grad_norm = pipe.run_optimizer(cfg.lr_schedule(step), 1.0 - opt.b1 ** t, 1.0 - opt.b2 ** t, ema_decay, ema_on, opt)
+        info = {"loss": loss, "grad_norm": grad_norm, "grad_norm_f32": grad_norm, **metrics}
+        return dataclasses.replace(state, step=state.step + 1), info
+
+    def _accumulated_step(self, rng, state: TrainState, batches, step, noise, time):
+        """One optimizer step over K micro-batches (see __call__)."""
+        from lap_amd.loss import global_denominators
+
+        cfg = self.config
+        K = cfg.grad_accum_steps
+        model, ps = state.model, state.model.ps
+        if not isinstance(batches, (list, tuple)) or len(batches) != K or not all(isinstance(b, (list, tuple)) and len(b) == 2 for b in batches):
+            raise ValueError(f"grad_accum_steps = {K}: the batch must be a list of {K} (observation, actions) pairs")
+        for nm, v in (("noise", noise), ("time", time)):
+            if v is not None and (not isinstance(v, (list, tuple)) or len(v) != K):
+                raise ValueError(f"grad_accum_steps = {K}: `{nm}` must be a list of {K} tensors")
+        step = state.step if step is None else int(step)
+        pipe = model.comm
+        if not hasattr(pipe, "run_optimizer") or not hasattr(pipe, "set_accum"):
+            raise RuntimeError("train step needs a UnitPipeline / FsdpComm (use init_train_state)")
+        den = global_denominators(model.config, [b[0] for b in batches], pipe, model.device)
+        pipe.begin_step()
+        for u in ps.units:       # the replicated f32 unit accumulates over ALL micro-steps: zeroed once
+            if not u.big:
+                ps.grad[u.name].zero_()
+        loss, infos = None, []
+        try:
+            for k, (observation, actions) in enumerate(batches):
+                pipe.set_accum(k, K)
+                lk, mk = model.loss_and_grad(self.micro_seed(rng, state.step, k, K), observation, actions, train=True,
+                                             noise=None if noise is None else noise[k], time=None if time is None else time[k],
+                                             denominators=den)
+                loss = lk if loss is None else loss + lk
+                infos.append(mk)
+            opt = cfg.optimizer
+            t = state.step + 1
+            ema_decay, ema_on = cfg.get_ema_decay_for_step(step)
+            grad_norm = pipe.run_optimizer(cfg.lr_schedule(step), 1.0 - opt.b1 ** t, 1.0 - opt.b2 ** t, ema_decay, ema_on, opt)
+        finally:
+            pipe.set_accum(0, 1)     # (the pass just scheduled keeps reading the accumulators: UnitPipeline._todo_accum)
+        metrics = {}
+        for key, v in infos[-1].items():
+            scalar = torch.is_tensor(v) and v.numel() == 1 and all(key in m for m in infos)
+            metrics[key] = torch.stack([m[key].float().reshape(()) for m in infos]).mean() if scalar else v
         info = {"loss": loss, "grad_norm": grad_norm, "grad_norm_f32": grad_norm, **metrics}
         return dataclasses.replace(state, step=state.step + 1), info
 
@@ -318,6 +382,8 @@ def main(config: TrainConfig, *, data_loader=None, val_data_loader=None, device:
         dist.init_process_group("nccl" if torch.device(device).type == "cuda" else "gloo", rank=rank, world_size=world)
     if config.batch_size % world:
         raise ValueError(f"batch_size {config.batch_size} must be divisible by the number of ranks {world}")
+    K = config.grad_accum_steps
+    per_rank = config.micro_batch_size(world)     # samples per rank and micro-step (raises unless ranks x grad_accum_steps divides)
     # rank 0 alone looks at / wipes / creates the directory and decides whether this is a resume; everyone else waits
     # and takes its verdict (each rank deciding for itself races: a late rank would see the directory rank 0 just made)
     if rank == 0:
@@ -338,7 +404,7 @@ def main(config: TrainConfig, *, data_loader=None, val_data_loader=None, device:
         mngr = ck.CheckpointManager(pathlib.Path(config.checkpoint_dir), keep_period=config.keep_period)
     state = init_train_state(config, device=device, world_size=world, rank=rank, use_fsdp=world > 1, resume=resuming)
     if data_loader is None:
-        data_loader = SyntheticDataLoader(config.model, config.batch_size // world, device, seed=config.seed, rank=rank, world_size=world)
+        data_loader = SyntheticDataLoader(config.model, per_rank, device, seed=config.seed, rank=rank, world_size=world)
     if resuming:
         state = ck.restore_state(mngr, state, data_loader)
         log(f"resumed from step {state.step} ({mngr.directory})")
@@ -348,13 +414,15 @@ def main(config: TrainConfig, *, data_loader=None, val_data_loader=None, device:
         if val_data_loader is None:
             if not isinstance(data_loader, SyntheticDataLoader):
                 raise ValueError("use_validation=True needs a `val_data_loader` (split='val' of the training data)")
-            val_data_loader = SyntheticDataLoader(config.model, config.batch_size // world, device, seed=config.seed + 7919, rank=rank,
+            val_data_loader = SyntheticDataLoader(config.model, per_rank, device, seed=config.seed + 7919, rank=rank,
                                                   world_size=world, num_batches=2)
         val_runner = ValidationStepRunner(config)
     it = iter(data_loader)
     infos, t_last, start = [], _time.perf_counter(), state.step
     for step in range(start, config.num_train_steps):
-        state, info = runner(config.seed, state, next(it), step)
+        # K draws per optimizer step; the loader's state is saved below after whole steps only, so a resumed run goes on with the
+        # batches an uninterrupted run would have drawn
+        state, info = runner(config.seed, state, next(it) if K == 1 else [next(it) for _ in range(K)], step)
         infos.append(info)
         last = step == config.num_train_steps - 1
         if (step + 1) % config.log_interval == 0 or last:   # mean of the interval's step infos (metrics_logging.py:181-237)
